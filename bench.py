@@ -6,7 +6,7 @@ synthetic 1920x1080 frames, batch 8 per GPU, fp16 NHWC input already resident in
 1e-3 of the reference's fp32 path (raw logits <= 1e-4, tests/test_gpu_precise.py).  Rounds 1-5 quoted it in the 'fp16' mode
 (sigma within 2.5e-3: outside that tolerance); that mode is still measured, by the same timed region, under `fp16_mode`.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -40,6 +40,8 @@ TARGET_K = 256            # candidates per image (SURVEY 8d "sparse-realistic" l
 MFMA_PEAK_TFLOPS = 2500.0  # dense fp16 (MI355X_MICROARCH.md)
 HBM_PEAK_GBS = 8000.0
 HEADLINE_MODE = 'fp32_storage'   # the precision mode `value` is quoted in: the one inside north_star's 1e-3 (round 6)
+DUMP_KEYS = ('dets', 'labels', 'cand', 'point', 'counts')     # the arrays of ops.DetectOutputs a caller reads
+DUMP_MAX_BYTES = 64 << 20
 PMC_SOURCE_PRECISE = ('profiles/pmc_traffic_precise.json: HBM bytes per launch of the fp32_storage kernels (FETCH_SIZE x 2 + WRITE_SIZE, separate '
                       'rocprofv3 --pmc passes, tools/collect_profiles_p2.sh) committed with the kernels -- not re-measured on this box')
 PMC_SOURCE = ('profiles/pmc_traffic.json: HBM bytes per launch (FETCH_SIZE + WRITE_SIZE, separate rocprofv3 --pmc passes, '
@@ -747,6 +749,9 @@ def timed_region(model, xs, meta, args, P, streams, dev, sync_ranks):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    # what the caller of the last timed step received (--dump-outputs), taken before any later step can overwrite it
+    o_ = dets[(args.steps - 1) % NBUF]
+    last = {k: getattr(o_, k).clone() for k in DUMP_KEYS}
     if sync_ranks and dist.is_initialized():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -796,7 +801,26 @@ def timed_region(model, xs, meta, args, P, streams, dev, sync_ranks):
             sustained[name] = dict(images_per_s=round(BATCH * n / el, 1), ms_per_step=round(el / n * 1e3, 4), steps=n, seconds=round(el, 2),
                                    wall_clock_window=[round(w0, 3), round(w0 + el, 3)])      # (tools/power_trace_r6.py joins rocm-smi samples on it)
         sustained['note'] = 'gap-free replays for >= %.1f s of device time (no host synchronisation inside), this rank' % args.sustained_s
-    return dict(dt=dt, dt_serial=dt_serial, ev_ms=ev_ms, counts=counts, sustained=sustained)
+    return dict(dt=dt, dt_serial=dt_serial, ev_ms=ev_ms, counts=counts, sustained=sustained, last=last)
+
+
+def dump_outputs(last, d):
+    """--dump-outputs DIR: the ops.DetectOutputs that LFD.detect_resident handed its caller in the last timed step, as
+    DIR/<name>.npy -- dets [N,R,5] float32 (x1, y1, x2, y2, score; score-descending), labels / cand / point [N,R] and
+    counts [N,4] as float64 (exact for int32).  Rows past an image's kept count are unspecified in the C ABI and are
+    written as 0.  R = the capacity (--max-candidates), cut to the leading rows that keep the files within 64 MB."""
+    counts = last['counts'].cpu().numpy()
+    n, cap = last['labels'].shape
+    rows = min(cap, (DUMP_MAX_BYTES - 4096 - counts.size * 8) // (n * (5 * 4 + 3 * 8)))     # (4096: the .npy headers)
+    valid = np.arange(rows)[None, :] < counts[:, 1:2]
+    arrs = {'counts': counts.astype(np.float64),
+            'dets': np.where(valid[..., None], last['dets'][:, :rows].cpu().numpy(), 0).astype(np.float32)}
+    for k in ('labels', 'cand', 'point'):
+        arrs[k] = np.where(valid, last[k][:, :rows].cpu().numpy(), 0).astype(np.float64)
+    assert sum(a.nbytes for a in arrs.values()) <= DUMP_MAX_BYTES
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + '.npy'), a)
 
 
 def fp16_mode_report(model, fast, x, dev, args, P, world):
@@ -885,7 +909,11 @@ def main():
     ap.add_argument('--clock-warmup-s', type=float, default=0.3, help='untimed replays before the W warm-up steps: an idle MI355X needs '
                     'milliseconds to ramp its clocks (DESIGN 3, lesson 11)')
     ap.add_argument('--pipeline', type=int, default=2, help='batches in flight per GPU (HIP streams with their own buffers)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="after the timed steps, write what rank 0's last timed step returned "
+                    'as DIR/<name>.npy (same arguments -> same inputs: builds can be compared output for output)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     global HEADLINE_MODE
     HEADLINE_MODE = args.headline_mode
     if HEADLINE_MODE == 'fp16':
@@ -944,6 +972,8 @@ def main():
         #      the 'fp16' mode (sigma within 2.5e-3) -- that figure is measured the same way below and reported as `fp16_mode`.
         model.precision = HEADLINE_MODE
         hl = timed_region(model, xs, meta, args, P, streams, dev, sync_ranks=True)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(hl['last'], args.dump_outputs)
         model.precision = 'fp16'
         fast = None
         if world == 1 and not args.no_fp16:

@@ -62,7 +62,14 @@ def main():
         model._head_indexes_to_feature_map_sizes[i] = tuple(s)
     ann = cases.train_annotations()
     pts = model.generate_point_coordinates(model.head_indexes_to_feature_map_sizes)
-    ct, rt = model.annotation_to_target(pts, [torch.from_numpy(a[0]) for a in ann], [torch.from_numpy(a[1]) for a in ann])
+    # the target scores with sqrt correctly rounded (tests/conftest.py ieee_sqrt): torch's CPU sqrt is MKL's <= 1 ulp vector
+    # routine, whose last bit depends on the host CPU -- the IEEE result is the one every host and csrc/targets.hip reproduce
+    real_sqrt = torch.sqrt
+    torch.sqrt = lambda x: real_sqrt(x.double()).float() if x.dtype == torch.float32 else real_sqrt(x)
+    try:
+        ct, rt = model.annotation_to_target(pts, [torch.from_numpy(a[0]) for a in ann], [torch.from_numpy(a[1]) for a in ann])
+    finally:
+        torch.sqrt = real_sqrt
     assert tuple(ct.shape) == (n, sum(a * b for a, b in sizes), 1)
     out['train/cls_target_sha'] = hashlib.sha256(ct.numpy().tobytes()).hexdigest()
     out['train/reg_target_sha'] = hashlib.sha256(rt.numpy().tobytes()).hexdigest()

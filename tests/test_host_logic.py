@@ -181,7 +181,7 @@ def test_point_grid_and_gray_ranges():
     assert m._gray_ranges == [(3, 22), (18, 44), (36, 88), (72, 176), (144, 352)]
 
 
-def test_target_assignment_and_loss_match_golden_on_cpu_tensors():
+def test_target_assignment_and_loss_match_golden_on_cpu_tensors(ieee_sqrt):
     """annotation_to_target / get_loss glue (tensor algebra) against the reference's outputs; the
     focal/IoU kernels need the GPU, so only targets are checked here."""
     from conftest import load_golden

@@ -178,7 +178,7 @@ def test_sibling_oracle_get_results_on_seeded_predictions_vs_reference(ci):
 
 
 @pytest.mark.parametrize('name', NAMES)
-def test_host_target_assignment_vs_reference(name):
+def test_host_target_assignment_vs_reference(name, ieee_sqrt):
     """FCOS.annotation_to_target (fcos.py:108-209) / LFDv2.annotation_to_target (lfdv2.py:232-418): host tensor algebra, as in
     the reference -- exact"""
     g = load_golden('ref_sibling_%s.npz' % name)
