@@ -583,6 +583,18 @@ LFD_API int lfd_pl_conv2d(const lfd_pl_conv_desc_t* desc, const void* in, void* 
                           const float* ds_bias, void* ds_out, void* gn_sums, float* f_out0, float* f_out1, const float* scale1,
                           const void* gn_in_sums, const float* gn_in_gamma, const float* gn_in_beta, const void* zeros,
                           lfd_stream_t stream);
+/* lfd_pl_block64: one residual block of the planes mode (lfd_resnet.py:96-154 without a downsample branch) in ONE launch:
+ *   m = planes(ReLU(conv3x3(in) + b1)),  out = planes(ReLU(conv3x3(m) + b2 + in)),  64 -> 64 -> 64 channels, stride 1, pad 1.
+ *   in / out: planes [n,h,w,64] (hi plane, the lo plane in_plane_halfs / out_plane_halfs behind it), not overlapping;
+ *   w1_packed / w2_packed: lfd_pl_conv2d order [2][2][36][64] x 8 halfs; b1 / b2: [>= 64] fp32; zeros: the 4 KB line of
+ *   lfd_conv2d_nhwc_f16.  csrc/planes_block.hip (k_pl_blk64: a row stream down strips of 30 output columns, the
+ *   intermediate m in LDS only).  Bit-identical to two lfd_pl_conv2d launches (conv1, then conv2 with residual = in) under
+ *   the default tuning of
+ *   the 3x3 plane convs (k_pl_c3p).  Any n, h, w >= 1; LFD_ERR_INVALID_ARGUMENT for null / misaligned / overlapping
+ *   buffers or short planes. */
+LFD_API int lfd_pl_block64(int32_t n, int32_t h, int32_t w, const void* in, int64_t in_plane_halfs, void* out,
+                           int64_t out_plane_halfs, const void* w1_packed, const float* b1, const void* w2_packed,
+                           const float* b2, const void* zeros, lfd_stream_t stream);
 typedef struct lfd_pl_level {
   const void* in;                 /* planes [n, h, w, cin] */
   void* out;                      /* planes [n, h, w, cout] (out_mode 0 | 1) */

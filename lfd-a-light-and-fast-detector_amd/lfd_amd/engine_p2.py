@@ -111,6 +111,12 @@ def _stem2x_enabled():
     return os.environ.get('LFD_P2_STEM2X', '1') != '0'
 
 
+def _block_enabled():
+    """LFD_P2_BLOCK=0: the residual blocks of the 64-channel stages as two lfd_pl_conv2d launches instead of one
+    lfd_pl_block64 (A/B timing, tests)"""
+    return os.environ.get('LFD_P2_BLOCK', '1') != '0'
+
+
 def _pad_bias(b, mult=32):
     n = -(-b.numel() // mult) * mult
     out = b.new_zeros(n, dtype=torch.float32)
@@ -180,6 +186,7 @@ class PlanesPlan(object):
         self.head_start = None      # index into self.ops of the first neck / head launch
         self.level_ops = []         # [(first, last + 1)] launch ranges of the pyramid levels' neck + head
         self.tap_ready = []         # index of the backbone launch that produces level i's input
+        self.block_pairs = {}       # conv1 index -> conv2 index of the 64-channel residual blocks lfd_pl_block64 runs
         with torch.no_grad():
             self._build(model)
 
@@ -302,6 +309,11 @@ class PlanesPlan(object):
                     if ci == 1 and blk._downsample is None and st != 1:
                         raise Unsupported('strided block without a downsample branch')
                     op = self._conv(y, w, b, ks, st, True, res=ident if last else None, ds=ds)
+                    if (ci == 2 and last and blk._downsample is None and self.ops[-2].dst == y and self.ops[-2].src == ident and
+                            op.res == ident and
+                            all(q.ks == 3 and q.stride == 1 and q.cin == 64 and q.cout == 64 and q.relu and q.tail is None
+                                and q.ds is None and q.out_mode == 0 for q in self.ops[-2:])):
+                        self.block_pairs[len(self.ops) - 2] = len(self.ops) - 1
                     y = op.dst
                     if ds is not None:
                         ident = op.ds_dst
@@ -590,9 +602,18 @@ class PlanesPlan(object):
         for d, arr, n in st.level_calls:
             check(l.lfd_pl_conv2d_levels(C.byref(d), arr, n, zeros, sp), 'lfd_pl_conv2d_levels')
 
+    def _fused_block(self, st):
+        """the dispatch rule of lfd_pl_block64: conv1 + conv2 of a 64-channel residual block as one launch.  Bit-identical to
+        the two k_pl_c3p launches it replaces, so only under their tuning (LFD_TUNE_PL_C3 = 2)"""
+        return bool(self.block_pairs) and _block_enabled() and _lib.tune('PL_C3') == 2
+
     def _launch(self, x, fmt, st, indices):
         l, sp = lib(), stream_ptr()
         zeros = ptr(ops.zero_line(self.device))
+        # the fused block runs when its conv1 is launched and writes conv2's output; conv2 is then a no-op whether or not it is
+        # launched in the same call (the per-op breakdown launches one index at a time).  conv1's output is never touched
+        fblk = self._fused_block(st)
+        blk_second = set(self.block_pairs.values()) if fblk else ()
         # the one-launch stem where its frame patches arrive by LDS-DMA (fp16 / uint8 NHWC, fp32 NCHW, 16-byte aligned rows: the row-stream
         # kernel); other layouts keep the two launches, whose loaders prefetch (lfd_pl_stem2x takes them too, by plain loads)
         fused = (self.stem2x is not None and _stem2x_enabled() and
@@ -600,6 +621,16 @@ class PlanesPlan(object):
                   (x.data_ptr() % 16 == 0 and ((fmt == 1 and st.w % 8 == 0) or (fmt == 2 and st.w % 16 == 0) or (fmt == 0 and st.w % 4 == 0)))))
         for i in indices:
             o = self.ops[i]
+            if fblk:
+                if i in blk_second:
+                    continue
+                j = self.block_pairs.get(i)
+                if j is not None:
+                    o2 = self.ops[j]
+                    src, dst = st.bufs[o.src], st.bufs[o2.dst]
+                    check(l.lfd_pl_block64(st.n, src.shape[2], src.shape[3], ptr(src), src[0].numel(), ptr(dst), dst[0].numel(),
+                                           ptr(o.w), ptr(o.b), ptr(o2.w), ptr(o2.b), zeros, sp), 'lfd_pl_block64')
+                    continue
             if fused and i < 2:
                 if i == 0:
                     f, c2 = self.stem2x, self.stem2x.tail
