@@ -472,10 +472,11 @@ LFD_API int lfd_conv2d_nhwc_f16_acc32(const lfd_conv_desc_t* desc, const void* i
  * fp32 accumulation, epilogue out = relu?( scale * (conv + bias (+ residual)) ) in fp32.
  *   in_format < 0: `in` is fp32 NHWC [n,h,w,cin], cin a multiple of 32; ks 1|3, stride 1|2, pad ks/2.
  *   in_format 0|1|2 (NCHW fp32 / NHWC fp16 / NHWC uint8 + simple_normalize): the first stem conv, 3x3 stride 2 on the
- *     3-channel frame (cin = 3); the 27 taps are one 32-wide k chunk gathered from the frame.
+ *     3-channel frame (cin = 3); the 27 taps are one 32-wide k chunk gathered from the frame.  cin = 1: a one-channel frame
+ *     (NCHW [n,1,h,w] and NHWC [n,h,w,1] are the same bytes), its 9 taps k = dy*3 + dx in the same 32-wide chunk.
  *   w_packed: lfd_p32_conv_packed_weight_halfs() fp16 values, [cout/32 slabs][cin/32 chunks][ks*ks taps][2 k-steps]
  *     [hi | 2^11 lo][64 lanes][8]; lane = 32 * khalf + cout_local, element j = channel 32 chunk + 16 kstep + 8 khalf + j
- *     (first conv: k = (dy*3 + dx)*3 + c, zero above 27); bias [32 * slabs] fp32 (zero padded).
+ *     (first conv: k = (dy*3 + dx)*cin + c, zero from 9*cin on); bias [32 * slabs] fp32 (zero padded).
  *   out: channel c of pixel (oy, ox) of image i at out[i * out_image_stride + (oy*OW + ox) * out_pixel_stride + c]
  *     (0 = dense: out_pixel_stride = cout, out_image_stride = OH*OW*cout) -- the head's output convs write straight into
  *     the level-concatenated [N,P,C'] / [N,P,4] tensors (lfd.py:526-542); residual: dense fp32 [n,OH,OW,cout] or NULL;
@@ -666,6 +667,24 @@ LFD_API int lfd_pl_head_levels(const lfd_pl_head_desc_t* desc, const lfd_pl_head
 LFD_API int lfd_stem_conv_f16(const void* in, int32_t in_format, int32_t n, int32_t h, int32_t w,
                               int32_t channels, const void* w1_packed, const float* b1,
                               const void* w2_packed, const float* b2, void* out, lfd_stream_t stream);
+
+/* First stem unit of a one-channel (grayscale, input_channels = 1) model: conv3x3 s2 (1 -> C) + BN + ReLU, chained with
+ * conv1x1 (C -> C) + BN + ReLU when w2_packed != NULL (lfd_resnet.py:356-374 'fast' stem; first half of the 'faster' stem
+ * :376-395; csrc/stem_gray.hip).  The frame is one [n, h, w] plane -- NCHW [n,1,h,w] and NHWC [n,h,w,1] are the same bytes:
+ * in_format 0 = fp32, 1 = fp16, 2 = uint8 with simple_normalize (x/255-0.5)/0.5 in fp32 on the load.  channels 32 | 64.
+ * w1_packed: [C/32][64 lanes][8] fp16, lane (h, co) slot j = tap k = 8 h + j (k = 3 ky + kx < 9, other slots zero;
+ * engine.pack_stem_gray_weight); w2_packed: lfd_conv2d 1x1 order (ops.pack_conv_weight), b1 / b2 fp32 [C].
+ * lfd_stem_gray_f16: out NHWC fp16 [n, (h+1)/2, (w+1)/2, C], the numerics of lfd_stem_conv_f16.
+ * lfd_pl_stem_gray_pair: out hi/lo planes (the plane layout of lfd_pl_stem_pair, out_plane_halfs a multiple of 8 and at least
+ *   one plane's size); w1 / w2 [2 = hi | 2^11 lo][...] as above per plane; uint8 / fp32 frames keep their low parts.
+ * out, b1, b2: 16-byte aligned.  LFD_ERR_INVALID_ARGUMENT: a null pointer (b2 must be given iff w2_packed is), sizes < 1, an
+ * in_format other than 0..2, misalignment, a bad plane stride; LFD_ERR_UNSUPPORTED: channels not 32 | 64. */
+LFD_API int lfd_stem_gray_f16(const void* in, int32_t in_format, int32_t n, int32_t h, int32_t w, int32_t channels,
+                              const void* w1_packed, const float* b1, const void* w2_packed, const float* b2, void* out,
+                              lfd_stream_t stream);
+LFD_API int lfd_pl_stem_gray_pair(const void* in, int32_t in_format, int32_t n, int32_t h, int32_t w, int32_t channels,
+                                  const void* w1_packed, const float* b1, const void* w2_packed, const float* b2, void* out,
+                                  int64_t out_plane_halfs, lfd_stream_t stream);
 
 /* The whole 'faster' stem (lfd_resnet.py:376-413) in one kernel: conv3x3 s2 (3->C), conv1x1, conv3x3 s2
  * (C->C), conv1x1, each + BN + ReLU.  The stride-2 intermediate (the largest activation of the

@@ -57,9 +57,10 @@ __device__ __forceinline__ void split8(const float4 a, const float4 b, half8& hi
   }
 }
 
+template <int CIN>
 __device__ __forceinline__ float frame_value(const void* in, int fmt, int n, int c, int y, int x, int H, int W) {
-  if (fmt == 0) return reinterpret_cast<const float*>(in)[(((size_t)n * 3 + c) * H + y) * W + x];
-  const size_t i = (((size_t)n * H + y) * W + x) * 3 + c;
+  if (fmt == 0) return reinterpret_cast<const float*>(in)[(((size_t)n * CIN + c) * H + y) * W + x];
+  const size_t i = (((size_t)n * H + y) * W + x) * CIN + c;
   if (fmt == 1) return (float)reinterpret_cast<const _Float16*>(in)[i];
   const float v = (float)reinterpret_cast<const uint8_t*>(in)[i];
   return (v / 255.f - 0.5f) / 0.5f;
@@ -71,7 +72,8 @@ __device__ __forceinline__ float frame_value(const void* in, int fmt, int n, int
 // conv3x3 + BN + ReLU -> conv1x1 + BN + ReLU): the first conv's fp32 results (bias, ReLU applied) are split into hi / lo planes
 // straight into LDS -- wave (slab s) fills channel chunk s of its 64 pixels -- and contracted again; the 64-channel fp32
 // intermediate (1.06 GB per 8 x 1080p for the first pair) never reaches HBM.  Needs cout == 64 (one workgroup = both slabs).
-template <int KS, int S, int NG, bool PATCH, bool TAIL = false>
+// PCIN: channels of the frame a PATCH conv gathers from (3 = RGB, 1 = gray)
+template <int KS, int S, int NG, bool PATCH, bool TAIL = false, int PCIN = 3>
 __global__ __launch_bounds__(256) void k_p32_conv(const P32Args a) {
   constexpr int TW = 16, TH = 4 * NG;
   constexpr int IH = (TH - 1) * S + KS, IW = (TW - 1) * S + KS;
@@ -108,11 +110,11 @@ __global__ __launch_bounds__(256) void k_p32_conv(const P32Args a) {
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const int k = cg * 8 + j;                    // k = (dy * 3 + dx) * 3 + channel; 27..31: zero weights
-          const int tap = k / 3, ch = k - tap * 3, dy = tap / 3, dx = tap - dy * 3;
+          const int k = cg * 8 + j;                    // k = (dy * 3 + dx) * PCIN + channel; 9 PCIN..31: zero weights
+          const int tap = k / PCIN, ch = k - tap * PCIN, dy = tap / 3, dx = tap - dy * 3;
           const int gy = 2 * oy + dy - 1, gx = 2 * ox + dx - 1;
-          const bool ok = k < 27 && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-          const float f = frame_value(a.in, a.fmt, n, ok ? ch : 0, ok ? gy : 0, ok ? gx : 0, a.H, a.W);
+          const bool ok = k < 9 * PCIN && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+          const float f = frame_value<PCIN>(a.in, a.fmt, n, ok ? ch : 0, ok ? gy : 0, ok ? gx : 0, a.H, a.W);
           v[j] = ok ? f : 0.f;
         }
         half8 hi, lo;
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(256) void k_p32_conv(const P32Args a) {
   }
 }
 
-template <int KS, int S, int NG, bool PATCH, bool TAIL = false>
+template <int KS, int S, int NG, bool PATCH, bool TAIL = false, int PCIN = 3>
 int launch_p32(P32Args a, hipStream_t st) {
   constexpr int TH = 4 * NG, TW = 16;
   constexpr int IH = (TH - 1) * S + KS, IW = (TW - 1) * S + KS;
@@ -267,7 +269,7 @@ int launch_p32(P32Args a, hipStream_t st) {
   a.tiles_y = (a.OH + TH - 1) / TH;
   const long tiles = (long)a.tiles_x * a.tiles_y * a.N;
   if (tiles > 0x7fffffffL) return LFD_ERR_UNSUPPORTED;
-  auto kern = k_p32_conv<KS, S, NG, PATCH, TAIL>;
+  auto kern = k_p32_conv<KS, S, NG, PATCH, TAIL, PCIN>;
   if (lds > 64 * 1024) {
     static unsigned long long set_mask = 0;   // (idempotent; races only repeat the same call)
     const int set_dev = lfd_device_ordinal();
@@ -369,7 +371,7 @@ int lfd_p32_conv2d_nhwc_f32(const lfd_p32_conv_desc_t* d, const void* in, float*
   if (d->n < 1 || d->h < 1 || d->w < 1 || d->cout < 1) return LFD_ERR_INVALID_ARGUMENT;
   const bool patch = d->in_format >= 0;
   if (patch) {
-    if (d->in_format > 2 || d->cin != 3 || d->ks != 3 || d->stride != 2) return LFD_ERR_UNSUPPORTED;
+    if (d->in_format > 2 || (d->cin != 3 && d->cin != 1) || d->ks != 3 || d->stride != 2) return LFD_ERR_UNSUPPORTED;
   } else {
     if (d->cin < 32 || d->cin % 32) return LFD_ERR_UNSUPPORTED;
     if ((d->ks != 1 && d->ks != 3) || (d->stride != 1 && d->stride != 2)) return LFD_ERR_UNSUPPORTED;
@@ -383,7 +385,7 @@ int lfd_p32_conv2d_nhwc_f32(const lfd_p32_conv_desc_t* d, const void* in, float*
   a.OW = (d->w + 2 * pad - d->ks) / d->stride + 1;
   a.out_pix_stride = d->out_pixel_stride > 0 ? d->out_pixel_stride : d->cout;
   a.out_img_stride = d->out_image_stride > 0 ? d->out_image_stride : (long)a.OH * a.OW * a.out_pix_stride;
-  if (patch) return launch_p32<1, 1, 2, true>(a, st);
+  if (patch) return d->cin == 1 ? launch_p32<1, 1, 2, true, false, 1>(a, st) : launch_p32<1, 1, 2, true>(a, st);
   switch (d->ks * 10 + d->stride) {
     case 31: return launch_p32<3, 1, 2, false>(a, st);
     case 32: return launch_p32<3, 2, 1, false>(a, st);
@@ -402,7 +404,7 @@ int lfd_p32_conv2d_tail_nhwc_f32(const lfd_p32_conv_desc_t* d, const void* in, f
   if (d->cout != 64) return LFD_ERR_UNSUPPORTED;          // both 32-channel slabs in one workgroup; the chained 1x1 is 64 -> 64
   const bool patch = d->in_format >= 0;
   if (patch) {
-    if (d->in_format > 2 || d->cin != 3 || d->ks != 3 || d->stride != 2) return LFD_ERR_UNSUPPORTED;
+    if (d->in_format > 2 || (d->cin != 3 && d->cin != 1) || d->ks != 3 || d->stride != 2) return LFD_ERR_UNSUPPORTED;
   } else if (d->cin < 32 || d->cin % 32 || d->ks != 3 || d->stride != 2) {
     return LFD_ERR_UNSUPPORTED;                           // the stem pairs: 3x3 stride 2 -> 1x1
   }
@@ -414,7 +416,7 @@ int lfd_p32_conv2d_tail_nhwc_f32(const lfd_p32_conv_desc_t* d, const void* in, f
   a.OW = (d->w + 2 - 3) / 2 + 1;
   a.out_pix_stride = d->out_pixel_stride > 0 ? d->out_pixel_stride : 64;
   a.out_img_stride = d->out_image_stride > 0 ? d->out_image_stride : (long)a.OH * a.OW * a.out_pix_stride;
-  if (patch) return launch_p32<1, 1, 2, true, true>(a, st);
+  if (patch) return d->cin == 1 ? launch_p32<1, 1, 2, true, true, 1>(a, st) : launch_p32<1, 1, 2, true, true>(a, st);
   return launch_p32<3, 2, 1, false, true>(a, st);
 }
 

@@ -54,10 +54,12 @@ ARCHS = {
 }
 
 
-def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, iou_cls, ce_cls, seed=666, qfl_cls=None):
+def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, iou_cls, ce_cls, seed=666, qfl_cls=None,
+                  input_channels=3):
     """Instantiates (backbone, neck, head, LFD) from `arch` with the given classes (this package's
     or the reference's -- identical kwargs), under torch.manual_seed(seed) (= the config seed,
-    WIDERFACE_LFD_S.py:51)."""
+    WIDERFACE_LFD_S.py:51).  input_channels=1: the grayscale twin (the task scripts' `input_channels`, BGR--3, gray--1,
+    TT100K_LFD_L.py:77-78)."""
     torch.manual_seed(seed)
     if arch['classification_loss_type'] == 'CrossEntropyLoss':
         cls_loss = ce_cls(reduction='mean', loss_weight=1.0)
@@ -66,7 +68,7 @@ def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, io
     else:
         cls_loss = focal_cls(use_sigmoid=True, gamma=2.0, alpha=0.25, reduction='mean', loss_weight=1.0)
     reg_loss = iou_cls(eps=1e-6, reduction='mean', loss_weight=1.0)
-    bb = backbone_cls(block_mode=arch['block_mode'], stem_mode=arch['stem_mode'], body_mode=None, input_channels=3,
+    bb = backbone_cls(block_mode=arch['block_mode'], stem_mode=arch['stem_mode'], body_mode=None, input_channels=input_channels,
                       stem_channels=arch['stem_channels'], body_architecture=list(arch['body_architecture']),
                       body_channels=list(arch['body_channels']), out_indices=arch['out_indices'], frozen_stages=-1,
                       activation_cfg=dict(type='ReLU', inplace=True), norm_cfg=dict(type='BatchNorm2d'),
@@ -88,15 +90,17 @@ def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, io
     return model
 
 
-def build_model(name_or_arch, seed=666):
-    """This package's LFD for a named configuration."""
+def build_model(name_or_arch, seed=666, input_channels=3):
+    """This package's LFD for a named configuration; input_channels=1 builds its grayscale twin (same ARCHS entry, a
+    one-channel first stem conv)."""
     from .model.backbone import LFDResNet
     from .model.head import LFDHead
     from .model.lfd import LFD
     from .model.losses import CrossEntropyLoss, FocalLoss, IoULoss, QualityFocalLoss
     from .model.neck import SimpleNeck
     arch = ARCHS[name_or_arch] if isinstance(name_or_arch, str) else name_or_arch
-    return build_modules(arch, LFDResNet, SimpleNeck, LFDHead, LFD, FocalLoss, IoULoss, CrossEntropyLoss, seed, QualityFocalLoss)
+    return build_modules(arch, LFDResNet, SimpleNeck, LFDHead, LFD, FocalLoss, IoULoss, CrossEntropyLoss, seed, QualityFocalLoss,
+                         input_channels=input_channels)
 
 
 def perturb_weights(model, seed=1):
@@ -208,12 +212,13 @@ SIBLINGS = {
 }
 
 
-def build_sibling(spec, B, N, H, M, L, seed=1):
+def build_sibling(spec, B, N, H, M, L, seed=1, input_channels=3):
     """Instantiate a SIBLINGS entry from module namespaces B (backbone), N (neck), H (head), M (meta-architectures) and L
-    (losses) -- this package's or the reference's (identical kwargs) -- and give it synthetic_weights(seed)."""
+    (losses) -- this package's or the reference's (identical kwargs) -- and give it synthetic_weights(seed).
+    input_channels=1: a grayscale LFDResNet."""
     spec = SIBLINGS[spec] if isinstance(spec, str) else spec
     bbk = spec['backbone']
-    bb = B.LFDResNet(block_mode=bbk['block_mode'], stem_mode=bbk['stem_mode'], body_mode=None, input_channels=3,
+    bb = B.LFDResNet(block_mode=bbk['block_mode'], stem_mode=bbk['stem_mode'], body_mode=None, input_channels=input_channels,
                      stem_channels=bbk['stem_channels'], body_architecture=list(bbk['body_architecture']),
                      body_channels=list(bbk['body_channels']), out_indices=bbk['out_indices'], frozen_stages=-1,
                      activation_cfg=dict(type='ReLU', inplace=True), norm_cfg=dict(type='BatchNorm2d'),
@@ -257,8 +262,8 @@ def build_sibling(spec, B, N, H, M, L, seed=1):
     return synthetic_weights(model, seed)
 
 
-def build_sibling_model(name, seed=1):
-    """This package's model for a SIBLINGS entry."""
+def build_sibling_model(name, seed=1, input_channels=3):
+    """This package's model for a SIBLINGS entry (input_channels=1: on a grayscale LFDResNet)."""
     from .model import backbone as B, head as H, losses as L, neck as N
     from . import model as M
-    return build_sibling(name, B, N, H, M, L, seed)
+    return build_sibling(name, B, N, H, M, L, seed, input_channels=input_channels)

@@ -40,8 +40,8 @@ def pad_channels(c):
     """The MFMA kernels are instantiated for 32 / 64 / 128 channels.  Any other width (TL_LFD_S: a 48-channel stem and first
     stage, TrafficLight_train/TL_LFD_S.py) runs zero-padded to the next one: padded output channels have zero weights and a
     zero bias, so they stay exactly 0 through ReLU / residual adds and meet zero weights in every consumer -- the real
-    channels are bit-identical to an unpadded evaluation.  3 (the image) is left alone."""
-    if c == 3:
+    channels are bit-identical to an unpadded evaluation.  3 and 1 (an RGB / a grayscale image) are left alone."""
+    if c in (1, 3):
         return c
     for a in (32, 64, 128):
         if c <= a:
@@ -105,6 +105,16 @@ def pack_stem_weight(w):
     out[:, 1, 1, :, 1] = wt[:, :, 1, 8]
     out[:, 1, 1, :, 2] = wt[:, :, 2, 8]
     return out.reshape(c // 32, 2, 64, 8).half().contiguous()
+
+
+def pack_stem_gray_weight(w):
+    """[C,1,3,3] -> [C/32][64][8] fp16 in the k-slot order of csrc/stem_gray.hip (one k-step): lane (h, co) slot j holds tap
+    k = 8 h + j, k = 3 ky + kx; slots k >= 9 are zero."""
+    c = w.shape[0]
+    assert tuple(w.shape[1:]) == (1, 3, 3) and c % 32 == 0
+    out = torch.zeros(c // 32, 32, 16, dtype=torch.float32, device=w.device)     # [tile][co_l][k]
+    out[:, :, :9] = w.detach().float().reshape(c // 32, 32, 9)
+    return out.reshape(c // 32, 32, 2, 8).permute(0, 2, 1, 3).reshape(c // 32, 64, 8).half().contiguous()
 
 
 def _pad_rows(w, b, rows):
@@ -180,8 +190,9 @@ class EnginePlan(object):
     def _build_backbone(self):
         bb = self.backbone
         dev = self.device
-        if bb._input_channels != 3:
-            _unsupported('input_channels != 3')
+        if bb._input_channels not in (1, 3):
+            _unsupported('input_channels not in (1, 3)')
+        self.input_channels = bb._input_channels
         if bb._norm_cfg is not None and bb._norm_cfg['type'] != 'BatchNorm2d':
             _unsupported('backbone norm must be BatchNorm2d (or None)')
         if type(bb._stem[2 if bb._norm_cfg is not None else 1]).__name__ != 'ReLU':
@@ -207,15 +218,17 @@ class EnginePlan(object):
         k, s, cin, c0, w, b = stem_convs[0]
         if c0 not in (32, 64):
             _unsupported('first stem conv must have 32 or 64 output channels')
+        # the first unit: csrc/stem.hip on RGB frames, csrc/stem_gray.hip on one-channel frames
+        w1 = (pack_stem_gray_weight(w) if self.input_channels == 1 else pack_stem_weight(w)).to(dev)
         idx = 1
         if len(stem_convs) > 1 and stem_convs[1][0] == 1:   # 'fast' / 'faster': chained 1x1
             _, _, _, c1, w2, b2 = stem_convs[1]
             if c1 != c0:
                 _unsupported('stem 1x1 must keep the channel count')
-            self.stem_first = (c0, pack_stem_weight(w).to(dev), b.to(dev), ops.pack_conv_weight(w2).to(dev), b2.to(dev))
+            self.stem_first = (c0, w1, b.to(dev), ops.pack_conv_weight(w2).to(dev), b2.to(dev))
             idx = 2
         else:
-            self.stem_first = (c0, pack_stem_weight(w).to(dev), b.to(dev), None, None)
+            self.stem_first = (c0, w1, b.to(dev), None, None)
         cur = new_buf()
         self.stem_out = cur
         self.buf_channels = {cur: c0}
@@ -234,7 +247,8 @@ class EnginePlan(object):
         self.stem_fused = None
         self.stem_second = None
         import os
-        if (bb._stem_mode == 'faster' and c0 in (32, 64) and self.stem_first[3] is not None and len(self.convs) == 1
+        # (RGB only: the one-launch stem gathers 3-channel frames; a gray 'faster' stem runs its second pair on lfd_conv2d)
+        if (self.input_channels == 3 and bb._stem_mode == 'faster' and c0 in (32, 64) and self.stem_first[3] is not None and len(self.convs) == 1
                 and self.convs[0].tail is not None and self.convs[0].cin == c0 and self.convs[0].cout == c0
                 and os.environ.get('LFD_FUSED_STEM', '1') == '1'):
             # one kernel for the whole stem (csrc/stem_fused.hip, k_stem2x): the 540x960x64 intermediate never
@@ -457,6 +471,10 @@ class EnginePlan(object):
             check(l.lfd_stem_faster_fused_f16(ptr(x), fmt, st.n, st.h, st.w, c0, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
                                               ptr(w3), ptr(b3), ptr(w4), ptr(b4), ptr(st.bufs[dst]), sp),
                   'lfd_stem_faster_fused_f16')
+        elif self.input_channels == 1:
+            c0, w1, b1, w2, b2 = self.stem_first
+            check(l.lfd_stem_gray_f16(ptr(x), fmt, st.n, st.h, st.w, c0, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
+                                      ptr(st.bufs[self.stem_out]), sp), 'lfd_stem_gray_f16')
         else:
             c0, w1, b1, w2, b2 = self.stem_first
             check(l.lfd_stem_conv_f16(ptr(x), fmt, st.n, st.h, st.w, c0, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
@@ -761,15 +779,32 @@ def get_plan(owner, backbone, neck, head, device):
     return plan
 
 
-def _input_format(x):
+def _input_format(x, channels=3):
+    """(in_format, n, h, w) of an image batch for a model with `channels` input channels (the backbone's input_channels).
+    RGB: NCHW float32 [N,3,H,W], NHWC float16 / uint8 [N,H,W,3]; gray: float32 [N,1,H,W], float16 / uint8 [N,H,W,1] (for one
+    channel NCHW and NHWC are the same bytes: the kernels read one [N,H,W] plane)."""
     if x.dim() != 4:
         raise RuntimeError('expected a 4-D image batch')
+    if channels == 1:
+        if x.dtype == torch.float32 and x.shape[1] == 1:
+            return IN_NCHW_F32, x.shape[0], x.shape[2], x.shape[3]
+        if x.dtype == torch.float16 and x.shape[3] == 1:
+            return IN_NHWC_F16, x.shape[0], x.shape[1], x.shape[2]
+        if x.dtype == torch.uint8 and x.shape[3] == 1:
+            return IN_NHWC_U8, x.shape[0], x.shape[1], x.shape[2]
+        raise RuntimeError('unsupported input for a one-channel (input_channels=1) model: float32 [N,1,H,W], '
+                           'float16 [N,H,W,1] or uint8 [N,H,W,1] (got %s %s)' % (x.dtype, tuple(x.shape)))
+    if channels != 3:
+        _unsupported('input_channels not in (1, 3)')
     if x.dtype == torch.float32 and x.shape[1] == 3:
         return IN_NCHW_F32, x.shape[0], x.shape[2], x.shape[3]
     if x.dtype == torch.float16 and x.shape[3] == 3:
         return IN_NHWC_F16, x.shape[0], x.shape[1], x.shape[2]
     if x.dtype == torch.uint8 and x.shape[3] == 3:
         return IN_NHWC_U8, x.shape[0], x.shape[1], x.shape[2]
+    if (x.dtype == torch.float32 and x.shape[1] == 1) or (x.dtype in (torch.float16, torch.uint8) and x.shape[3] == 1):
+        raise RuntimeError('unsupported input: a one-channel batch %s %s for an RGB (input_channels=3) model; expected NCHW '
+                           'float32 [N,3,H,W], NHWC float16 [N,H,W,3] or NHWC uint8 [N,H,W,3]' % (x.dtype, tuple(x.shape)))
     raise RuntimeError('unsupported input: NCHW float32 [N,3,H,W], NHWC float16 [N,H,W,3] or NHWC uint8 [N,H,W,3]')
 
 
@@ -780,7 +815,7 @@ def lfd_forward(model, x, use_graph=False, slot=0):
     _lib.require_cuda(x, 'LFD.forward')
     if not x.is_contiguous():
         x = x.contiguous()
-    fmt, n, h, w = _input_format(x)
+    fmt, n, h, w = _input_format(x, model._backbone._input_channels)
     plan = get_plan(model, model._backbone, model._neck, model._head, x.device)
     st = plan.state_for(n, h, w, slot)
     with torch.cuda.device(x.device):
@@ -798,7 +833,7 @@ def lfd_forward_detect(model, x, desc, meta, out, slot=0):
     _lib.require_cuda(x, 'LFD.forward')
     if not x.is_contiguous():
         x = x.contiguous()
-    fmt, n, h, w = _input_format(x)
+    fmt, n, h, w = _input_format(x, model._backbone._input_channels)
     plan = get_plan(model, model._backbone, model._neck, model._head, x.device)
     st = plan.state_for(n, h, w, slot)
     if plan.head is None or not plan.decode_supported(st, desc):
@@ -835,7 +870,7 @@ def backbone_only_forward(backbone, x):
     """LFDResNet.forward stand-alone: tuple of tapped maps as NCHW fp32 (reference return type,
     lfd_resnet.py:488-501).  The layout/precision conversion is plain tensor plumbing."""
     _lib.require_cuda(x, 'LFDResNet.forward')
-    fmt, n, h, w = _input_format(x.contiguous())
+    fmt, n, h, w = _input_format(x.contiguous(), backbone._input_channels)
     plan = get_plan(backbone, backbone, None, None, x.device)
     st = plan.state_for(n, h, w)
     with torch.cuda.device(x.device):

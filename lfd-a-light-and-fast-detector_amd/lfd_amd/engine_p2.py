@@ -6,6 +6,7 @@ tensor csrc/precise.hip stores, in the form the matrix cores consume -- and the 
 engine rebuilt on three MFMAs per k-step:
 
   stem        lfd_pl_stem_pair (frame -> conv3x3 s2 -> conv1x1) ; lfd_pl_conv2d 3x3 s2 + chained 1x1     lfd_resnet.py:376-413
+              (gray frames, input_channels=1: lfd_pl_stem_gray_pair, csrc/stem_gray.hip, in place of lfd_pl_stem_pair)
   stage entry lfd_pl_conv2d 3x3 s2 with the 1x1 s2 identity branch as second output                       lfd_resnet.py:458-468
   block convs lfd_pl_conv2d 3x3 s1 (+ residual + ReLU)                                                    lfd_resnet.py:96-154
   head        neck 1x1 chained into the first tower 1x1 (GroupNorm sums from the epilogue); second tower 1x1 normalises +
@@ -57,6 +58,12 @@ def pack_planes_stem_weight(w):
     """[C, 3, 3, 3] fp32 -> [2][C/32][2][64][8] (engine.pack_stem_weight order per plane)"""
     hi, lo = _split(w)
     return torch.stack([engine.pack_stem_weight(hi), engine.pack_stem_weight(lo)], 0).contiguous()
+
+
+def pack_planes_stem_gray_weight(w):
+    """[C, 1, 3, 3] fp32 -> [2][C/32][64][8] (engine.pack_stem_gray_weight order per plane; csrc/stem_gray.hip)"""
+    hi, lo = _split(w)
+    return torch.stack([engine.pack_stem_gray_weight(hi), engine.pack_stem_gray_weight(lo)], 0).contiguous()
 
 
 def pack_planes_stem2x_weight(w, b):
@@ -246,7 +253,7 @@ class PlanesPlan(object):
         bb, neck, head = model._backbone, model._neck, model._head
         if type(neck).__name__ != 'SimpleNeck' or type(head).__name__ != 'LFDHead':
             raise Unsupported('SimpleNeck + LFDHead')
-        if bb._input_channels != 3 or (bb._norm_cfg is not None and bb._norm_cfg['type'] != 'BatchNorm2d'):
+        if bb._input_channels not in (1, 3) or (bb._norm_cfg is not None and bb._norm_cfg['type'] != 'BatchNorm2d'):
             raise Unsupported('backbone')
         # the consumer kernels hard-wire ReLU (lfd_resnet.py / simple_neck.py / lfd_head.py build their activation from
         # activation_cfg): any other leaf module than conv / norm / ReLU / Scale falls back to the fp32-tensor plan's checks
@@ -265,9 +272,12 @@ class PlanesPlan(object):
         c = folded[0][0].shape[0]
         if c not in (32, 64) or tuple(folded[1][0].shape[:2]) != (c, c):
             raise Unsupported('stem channels')
-        o = _Op('stem')
+        # one-channel frames: the gray stem unit (lfd_pl_stem_gray_pair, csrc/stem_gray.hip), one k-step of 9 taps
+        gray = bb._input_channels == 1
+        o = _Op('stem_gray' if gray else 'stem')
         o.channels = c
-        o.w1, o.b1 = pack_planes_stem_weight(folded[0][0]).to(self.device), _pad_bias(folded[0][1]).to(self.device)
+        o.w1 = (pack_planes_stem_gray_weight if gray else pack_planes_stem_weight)(folded[0][0]).to(self.device)
+        o.b1 = _pad_bias(folded[0][1]).to(self.device)
         o.w2, o.b2 = pack_planes_weight(folded[1][0]).to(self.device), _pad_bias(folded[1][1]).to(self.device)
         o.dst = self._new_buf(c, 2)
         self.ops.append(o)
@@ -278,7 +288,7 @@ class PlanesPlan(object):
                 raise Unsupported('stem channels')
             pair2 = self._conv(cur, folded[2][0], folded[2][1], 3, 2, True, tail=(folded[3][0], folded[3][1], True))
             cur = pair2.dst
-            if c == 64:
+            if c == 64 and not gray:
                 # the whole stem as one launch (lfd_pl_stem2x) in place of ops[0:2]; the two-launch form stays for A/B
                 f = _Op('stem2x')
                 f.w1 = pack_planes_stem2x_weight(folded[0][0], folded[0][1]).to(self.device)
@@ -642,6 +652,11 @@ class PlanesPlan(object):
                 dst = st.bufs[o.dst]
                 check(l.lfd_pl_stem_pair(ptr(x), fmt, st.n, st.h, st.w, o.channels, ptr(o.w1), ptr(o.b1), ptr(o.w2), ptr(o.b2),
                                          ptr(dst), dst[0].numel(), sp), 'lfd_pl_stem_pair')
+                continue
+            if o.kind == 'stem_gray':
+                dst = st.bufs[o.dst]
+                check(l.lfd_pl_stem_gray_pair(ptr(x), fmt, st.n, st.h, st.w, o.channels, ptr(o.w1), ptr(o.b1), ptr(o.w2),
+                                              ptr(o.b2), ptr(dst), dst[0].numel(), sp), 'lfd_pl_stem_gray_pair')
                 continue
             d, src, dst, res, dsd, f0, f1 = self._desc(o, st)
             gi = o.gnin

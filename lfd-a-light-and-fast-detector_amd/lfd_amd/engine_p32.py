@@ -86,9 +86,10 @@ class PrecisePlan(object):
         o.cout = w.shape[0]
         o.ref_w = w
         if patch:
-            o.cin = 3
-            w27 = w.permute(0, 2, 3, 1).reshape(w.shape[0], 27)
-            w = torch.cat([w27, w27.new_zeros((w.shape[0], 5))], 1).reshape(w.shape[0], 32, 1, 1)
+            # the frame's 3x3 taps (k = (dy*3 + dx)*cin + c: 27 for RGB, 9 for gray) as one 32-wide k chunk
+            o.cin = w.shape[1]
+            wk = w.permute(0, 2, 3, 1).reshape(w.shape[0], 9 * o.cin)
+            w = torch.cat([wk, wk.new_zeros((w.shape[0], 32 - 9 * o.cin))], 1).reshape(w.shape[0], 32, 1, 1)
         else:
             o.cin = w.shape[1]
         o.w = pack_weight(w).to(dev)
@@ -114,8 +115,8 @@ class PrecisePlan(object):
         bb, neck, head = model._backbone, model._neck, model._head
         if type(neck).__name__ != 'SimpleNeck' or type(head).__name__ != 'LFDHead':
             engine._unsupported("precision='fp32_storage' covers SimpleNeck + LFDHead (every shipped configuration)")
-        if bb._input_channels != 3:
-            engine._unsupported('input_channels != 3')
+        if bb._input_channels not in (1, 3):
+            engine._unsupported('input_channels not in (1, 3)')
         if bb._norm_cfg is not None and bb._norm_cfg['type'] != 'BatchNorm2d':
             engine._unsupported('backbone norm must be BatchNorm2d (or None)')
         has_norm = bb._norm_cfg is not None
@@ -135,8 +136,8 @@ class PrecisePlan(object):
                     and tuple(folded[i + 1][0].shape[:2]) == (64, 64)):
                 tail = folded[i + 1]
             if i == 0:
-                if (k, s, cin) != (3, 2, 3):
-                    engine._unsupported('first stem conv must be 3x3 stride 2 on 3 channels')
+                if (k, s, cin) != (3, 2, bb._input_channels):
+                    engine._unsupported('first stem conv must be 3x3 stride 2 on the frame')
                 cur = self._conv(cur, w, b, 3, 2, True, patch=True, tail=tail)
             else:
                 cur = self._conv(cur, w, b, k, s, True, tail=tail)
@@ -299,7 +300,7 @@ def lfd_forward(model, x, use_graph=False, slot=0):
     _lib.require_cuda(x, "LFD.forward (precision='fp32_storage')")
     if not x.is_contiguous():
         x = x.contiguous()
-    fmt, n, h, w = engine._input_format(x)
+    fmt, n, h, w = engine._input_format(x, model._backbone._input_channels)
     plan = get_plan(model, x.device)
     st = plan.state_for(n, h, w, slot)
     with torch.cuda.device(x.device):

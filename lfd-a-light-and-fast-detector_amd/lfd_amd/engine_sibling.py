@@ -291,7 +291,7 @@ def get_plan(owner, backbone, neck, head, device):
 
 def backbone_taps(plan, x):
     """image batch -> the backbone's tapped maps, NHWC fp16 (engine-owned buffers, padded channels)"""
-    fmt, n, h, w = engine._input_format(x)
+    fmt, n, h, w = engine._input_format(x, plan.bb_plan.input_channels)
     st = plan.bb_plan.state_for(n, h, w)
     plan.bb_plan.run_backbone(x, fmt, st)
     return [st.bufs[t] for t in plan.bb_plan.taps]

@@ -106,7 +106,10 @@ class LFD(nn.Module):
         'fp32_storage'  every inter-layer tensor as fp16 hi + 2^-11 lo planes (the bytes of fp32), weights split the same
                         way, three MFMAs per k-step, fp32 accumulation and epilogues (engine_p2.py, csrc/planes*.hip;
                         engine_p32.py / csrc/precise.hip for layer shapes without a plane kernel); raw logits within 1e-4
-                        of the fp32 reference (north_star: "tensors within 1e-3"; measured 8e-6), ~3.5x the time."""
+                        of the fp32 reference (north_star: "tensors within 1e-3"; measured 8e-6), ~3.5x the time.
+        Both modes take the frames of the model's input_channels: RGB (3) float32 [N,3,H,W], float16 / uint8 [N,H,W,3];
+        grayscale (input_channels=1) float32 [N,1,H,W], float16 / uint8 [N,H,W,1] (the first stem unit of csrc/stem_gray.hip);
+        uint8 frames get the reference's simple_normalize on the load."""
         return self.__dict__.get('_precision', 'fp16')
 
     @precision.setter
@@ -166,7 +169,8 @@ class LFD(nn.Module):
 
     def forward(self, x):
         """lfd.py:511-542.  eval mode: HIP engine.  Returns fresh fp32 tensors (clone of the
-        engine's resident output buffers) and records (h, w) per level (:532)."""
+        engine's resident output buffers) and records (h, w) per level (:532).  x: float32 [N,3,H,W] or NHWC float16 / uint8
+        [N,H,W,3]; for a grayscale model (backbone input_channels=1) float32 [N,1,H,W] or float16 / uint8 [N,H,W,1]."""
         if self.training:
             return self._forward_train(x)
         cls, reg = self.forward_resident(x)
