@@ -987,6 +987,35 @@ LFD_API int lfd_stem_conv0_bn_bwd_wgrad_rows(const float* x_nchw, const void* dz
                                      int32_t accumulate, int32_t sum_rows, void* workspace, size_t workspace_bytes, float* dgamma,
                                      float* dbeta, float* dw, lfd_stream_t stream);
 
+/* The first stem conv of a ONE-channel (grayscale) model in training (csrc/stem_gray_train.hip): Conv2d(1, channels, 3, 2, 1,
+ * bias=False) -> train-mode BatchNorm2d -> ReLU, lfd_resnet.py:354-439 with input_channels = 1 (lfd_resnet.py:358 'fast' stem,
+ * :378 'faster' stem).  The gray twins of the four RGB entry points above, same arguments and numerics: x_nchw is fp32 [n,1,h,w],
+ * weight_oihw / dw fp32 [channels,1,3,3], y / dy / dz NHWC fp16 [n,(h+1)/2,(w+1)/2,channels] (16-byte aligned), channels in
+ * {32, 64}; image values rounded to fp16 for the MFMA, fp32 accumulation, dw and dgamma / dbeta unscaled (x inv_scale),
+ * accumulate: += instead of =; every reduction in a fixed order (deterministic).
+ *   lfd_stem_gray_train_fwd            y = conv(x, W), pre-norm
+ *   lfd_stem_gray_train_fwd_bn_stats   the same y, bit for bit, + the batch statistics as lfd_stem_conv0_train_fwd_bn_stats
+ *   lfd_stem_gray_wgrad                dw (+)= inv_scale * sum_px dy[px][co] * patch[px][t]
+ *   lfd_stem_gray_bn_bwd_wgrad_rows    BatchNorm backward (ReLU mask recomputed from y) + dw without a dy tensor: the values of
+ *                                      lfd_bn_train_bwd_f16 followed by lfd_stem_gray_wgrad, bit for bit; sum_rows as
+ *                                      lfd_stem_conv0_bn_bwd_wgrad_rows (0: with the sums pass)
+ * LFD_ERR_INVALID_ARGUMENT for null or misaligned pointers, channels not in {32, 64}, n, h or w < 1, sum_rows outside 0..1024;
+ * LFD_ERR_UNSUPPORTED for an image or output map of 2^31 elements or more; LFD_ERR_WORKSPACE_TOO_SMALL below
+ * lfd_train_workspace_bytes().  Nothing is launched when a status code is returned. */
+LFD_API int lfd_stem_gray_train_fwd(const float* x_nchw, int32_t n, int32_t h, int32_t w, int32_t channels,
+                                    const float* weight_oihw, void* y, lfd_stream_t stream);
+LFD_API int lfd_stem_gray_train_fwd_bn_stats(const float* x_nchw, int32_t n, int32_t h, int32_t w, int32_t channels,
+                                             const float* weight_oihw, void* y, float eps, float momentum, float* running_mean,
+                                             float* running_var, void* workspace, size_t workspace_bytes, float* stats,
+                                             lfd_stream_t stream);
+LFD_API int lfd_stem_gray_wgrad(const float* x_nchw, const void* dy, int32_t n, int32_t h, int32_t w, int32_t channels,
+                                float inv_scale, int32_t accumulate, void* workspace, size_t workspace_bytes, float* dw,
+                                lfd_stream_t stream);
+LFD_API int lfd_stem_gray_bn_bwd_wgrad_rows(const float* x_nchw, const void* dz, const void* y, int32_t n, int32_t h, int32_t w,
+                                            int32_t channels, const float* stats, const float* gamma, const float* beta,
+                                            float inv_scale, int32_t accumulate, int32_t sum_rows, void* workspace,
+                                            size_t workspace_bytes, float* dgamma, float* dbeta, float* dw, lfd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Neck + head of ALL pyramid levels.  Replaces SimpleNeck.forward (simple_neck.py:67-74),
  * LFDHead.forward (lfd_head.py:164-185: GroupNorm towers + cls/reg convs + Scale) and the

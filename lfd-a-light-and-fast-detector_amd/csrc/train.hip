@@ -13,6 +13,7 @@
 //              dx = conv(dy, W^T flipped)  the forward conv kernel again (stride 2: after lfd_zero_insert2_nhwc_f16)
 // All reductions use per-block partials + a fixed-order final stage (deterministic, no atomics).
 #include "common.h"
+#include "train_bn.h"
 
 namespace {
 
@@ -388,10 +389,10 @@ __device__ __forceinline__ void bn_bwd_apply_body(const __half* __restrict__ dz,
     h8 o, go;
     for (int e = 0; e < 8; ++e) {
       float g = (float)d[e];
-      const float xh = ((float)yy[e] - mean[e]) * rstd[e];
+      const float xh = LFD_BN_XHAT((float)yy[e], mean[e], rstd[e]);     // (train_bn.h: shared with stem_gray_train.hip)
       if (z && !((float)zz[e] > 0.f)) g = 0.f;
-      if (relu_y && !(ga[e] * xh + be[e] > 0.f)) g = 0.f;
-      o[e] = (_Float16)(a[e] * (g - mg[e] - xh * mgx[e]));
+      if (relu_y && !LFD_BN_RELU_OPEN(ga[e], be[e], xh)) g = 0.f;
+      o[e] = LFD_BN_BWD_DY(a[e], g, mg[e], xh, mgx[e]);
       go[e] = (_Float16)g;
     }
     st8(dy, v, o);
@@ -2120,3 +2121,31 @@ int lfd_stem_conv0_bn_bwd_wgrad_rows(const float* x_nchw, const void* dz, const 
 }
 
 }  // extern "C"
+
+static_assert(kLfdBnSumsAt == (size_t)kMaxBlocks * 2 * kMaxC && kLfdBnWpartAt == kLfdBnSumsAt + 2 * kMaxC,
+              "train_bn.h: workspace layout of lfd_stem_conv0_bn_bwd_wgrad_rows");
+
+int lfd_first_unit_bn_bwd_sums(const void* dz, const void* y, int64_t pixels, int32_t channels, const float* stats,
+                               const float* gamma, const float* beta, float inv_scale, int32_t accumulate, int32_t sum_rows,
+                               float* workspace, float* dgamma, float* dbeta, hipStream_t st) {
+  const int64_t vecs = pixels * (channels / 8);
+  const unsigned g = grid_for_vecs(vecs);
+  float* partials = workspace;
+  if (!sum_rows) {
+    hipLaunchKernelGGL(k_bn_bwd_partial, dim3(g), dim3(kThreads), 0, st, (const __half*)dz, (const __half*)y, (const __half*)nullptr,
+                       vecs, channels, stats, gamma, beta, 1, partials, RowMap{});
+    LFD_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(k_bn_bwd_final, dim3(channels), dim3(64), 0, st, partials, sum_rows ? sum_rows : (int)g, channels, inv_scale,
+                     accumulate, workspace + kLfdBnSumsAt, dgamma, dbeta);
+  LFD_CHECK_LAUNCH();
+  return LFD_OK;
+}
+
+int lfd_bn_stats_final_rows(const float* partials, int nblocks, int32_t channels, int64_t pixels, float eps, float momentum,
+                            float* running_mean, float* running_var, float* stats, hipStream_t st) {
+  hipLaunchKernelGGL(k_bn_stats_final, dim3(channels), dim3(64), 0, st, partials, nblocks, channels, (double)pixels, eps,
+                     momentum, running_mean, running_var, stats);
+  LFD_CHECK_LAUNCH();
+  return LFD_OK;
+}

@@ -1267,31 +1267,48 @@ def head_out_grad(y, segs, grads, point0, loss_scale):
     return dy
 
 
+def _stem_conv0_cin(x_nchw, weight, what):
+    """input channels of a first-stem-conv call: 3 (RGB, csrc/train.hip) or 1 (gray, csrc/stem_gray_train.hip); anything else,
+    or a weight whose in_channels disagree with the batch, raises before any launch"""
+    if x_nchw.dim() != 4 or x_nchw.size(1) not in (1, 3):
+        raise RuntimeError('%s: expected an NCHW float32 image batch [N,1,H,W] or [N,3,H,W], got %s'
+                           % (what, tuple(x_nchw.shape)))
+    cin = x_nchw.size(1)
+    if weight is not None and (weight.dim() != 4 or weight.size(1) != cin):
+        raise RuntimeError('%s: weight %s does not take a %d-channel batch %s'
+                           % (what, tuple(weight.shape), cin, tuple(x_nchw.shape)))
+    return cin
+
+
 def stem_conv0_train_fwd(x_nchw, weight):
     require_cuda(x_nchw, 'stem_conv0_train_fwd')
+    cin = _stem_conv0_cin(x_nchw, weight, 'stem_conv0_train_fwd')
     x = x_nchw.contiguous().float()
     n, _, h, w_ = x.shape
     c = weight.size(0)
     y = torch.empty((n, (h + 1) // 2, (w_ + 1) // 2, c), dtype=torch.float16, device=x.device)
+    fn, name = ((lib().lfd_stem_conv0_train_fwd, 'lfd_stem_conv0_train_fwd') if cin == 3 else
+                (lib().lfd_stem_gray_train_fwd, 'lfd_stem_gray_train_fwd'))
     with torch.cuda.device(x.device):
-        check(lib().lfd_stem_conv0_train_fwd(ptr(x), n, h, w_, c, ptr(weight.detach().contiguous().float()), ptr(y),
-                                             stream_ptr()), 'lfd_stem_conv0_train_fwd')
+        check(fn(ptr(x), n, h, w_, c, ptr(weight.detach().contiguous().float()), ptr(y), stream_ptr()), name)
     return y
 
 
 def stem_conv0_train_fwd_bn_stats(x_nchw, weight, eps, momentum, running_mean=None, running_var=None):
     """stem_conv0_train_fwd + the batch statistics of its output from the conv's own stores -> (y, float32[2*C])"""
     require_cuda(x_nchw, 'stem_conv0_train_fwd_bn_stats')
+    cin = _stem_conv0_cin(x_nchw, weight, 'stem_conv0_train_fwd_bn_stats')
     x = x_nchw.contiguous().float()
     n, _, h, w_ = x.shape
     c = weight.size(0)
     ws = train_workspace(x.device)
+    fn, name = ((lib().lfd_stem_conv0_train_fwd_bn_stats, 'lfd_stem_conv0_train_fwd_bn_stats') if cin == 3 else
+                (lib().lfd_stem_gray_train_fwd_bn_stats, 'lfd_stem_gray_train_fwd_bn_stats'))
     with torch.cuda.device(x.device):
         y = torch.empty((n, (h + 1) // 2, (w_ + 1) // 2, c), dtype=torch.float16, device=x.device)
         stats = torch.empty(2 * c, dtype=torch.float32, device=x.device)
-        check(lib().lfd_stem_conv0_train_fwd_bn_stats(ptr(x), n, h, w_, c, ptr(weight.detach().contiguous().float()), ptr(y),
-                                                      float(eps), float(momentum), ptr(running_mean), ptr(running_var), ptr(ws),
-                                                      ws.numel(), ptr(stats), stream_ptr()), 'lfd_stem_conv0_train_fwd_bn_stats')
+        check(fn(ptr(x), n, h, w_, c, ptr(weight.detach().contiguous().float()), ptr(y), float(eps), float(momentum),
+                 ptr(running_mean), ptr(running_var), ptr(ws), ws.numel(), ptr(stats), stream_ptr()), name)
     return y, stats
 
 
@@ -1300,14 +1317,16 @@ def stem_conv0_bn_bwd_wgrad(x_nchw, dz, y, stats, gamma, beta, inv_scale, dgamma
     no dy tensor (lfd_stem_conv0_bn_bwd_wgrad).  sum_rows > 0: BatchNorm's partial sums are already in the training workspace
     (conv1x1_dgrad_bn_bwd_sums left them): no pass over (dz, y) for them."""
     require_cuda(x_nchw, 'stem_conv0_bn_bwd_wgrad')
+    cin = _stem_conv0_cin(x_nchw, dw, 'stem_conv0_bn_bwd_wgrad')
     x = x_nchw.contiguous().float()
     n, _, h, w_ = x.shape
     c = y.size(3)
     ws = train_workspace(x.device)
+    fn, name = ((lib().lfd_stem_conv0_bn_bwd_wgrad_rows, 'lfd_stem_conv0_bn_bwd_wgrad_rows') if cin == 3 else
+                (lib().lfd_stem_gray_bn_bwd_wgrad_rows, 'lfd_stem_gray_bn_bwd_wgrad_rows'))
     with torch.cuda.device(x.device):
-        check(lib().lfd_stem_conv0_bn_bwd_wgrad_rows(ptr(x), ptr(dz), ptr(y), n, h, w_, c, ptr(stats), ptr(gamma), ptr(beta),
-                                                     float(inv_scale), 1, int(sum_rows), ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta),
-                                                     ptr(dw), stream_ptr()), 'lfd_stem_conv0_bn_bwd_wgrad_rows')
+        check(fn(ptr(x), ptr(dz), ptr(y), n, h, w_, c, ptr(stats), ptr(gamma), ptr(beta), float(inv_scale), 1, int(sum_rows),
+                 ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta), ptr(dw), stream_ptr()), name)
 
 
 def conv1x1_dgrad_bn_bwd_sums(dy, w_packed_dgrad, zero_bias, y_unit, unit_stats, unit_gamma, unit_beta):
@@ -1347,13 +1366,18 @@ def bn_train_backward_rows(dz, y, stats, gamma, beta, inv_scale, dgamma, dbeta, 
 
 
 def stem_conv0_wgrad(x_nchw, dy, inv_scale, out=None, accumulate=False):
+    """weight gradient of the first stem conv -> out [C, cin, 3, 3] fp32 (cin = x_nchw.size(1): 3 or 1)"""
+    require_cuda(x_nchw, 'stem_conv0_wgrad')
+    cin = _stem_conv0_cin(x_nchw, out, 'stem_conv0_wgrad')
     x = x_nchw.contiguous().float()
     n, _, h, w_ = x.shape
     c = dy.size(3)
     if out is None:
-        out = torch.empty((c, 3, 3, 3), dtype=torch.float32, device=x.device)
+        out = torch.empty((c, cin, 3, 3), dtype=torch.float32, device=x.device)
     ws = train_workspace(x.device)
+    fn, name = ((lib().lfd_stem_conv0_wgrad, 'lfd_stem_conv0_wgrad') if cin == 3 else
+                (lib().lfd_stem_gray_wgrad, 'lfd_stem_gray_wgrad'))
     with torch.cuda.device(x.device):
-        check(lib().lfd_stem_conv0_wgrad(ptr(x), ptr(dy), n, h, w_, c, float(inv_scale), int(bool(accumulate)), ptr(ws),
-                                         ws.numel(), ptr(out), stream_ptr()), 'lfd_stem_conv0_wgrad')
+        check(fn(ptr(x), ptr(dy), n, h, w_, c, float(inv_scale), int(bool(accumulate)), ptr(ws), ws.numel(), ptr(out),
+                 stream_ptr()), name)
     return out

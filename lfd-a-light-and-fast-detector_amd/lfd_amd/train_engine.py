@@ -46,30 +46,44 @@ class _Out(object):
     __slots__ = ('level', 'convs', 'src', 'scale')
 
 
-def _conv_ok(m):
+def _conv_ok(m, first=False):
+    """first: the backbone's first stem conv, which may also read ONE input plane (a grayscale model, csrc/stem_gray_train.hip)"""
+    if first and m.in_channels == 1:
+        return True
     return m.in_channels == 3 or (m.in_channels in (32, 64, 128) and m.out_channels in (32, 64, 128))
 
 
 def supported(backbone):
-    """The HIP training path covers BatchNorm2d + ReLU backbones with 32/64/128-channel convs, nothing frozen."""
+    """The HIP training path covers BatchNorm2d + ReLU backbones with 32/64/128-channel convs, nothing frozen; RGB or
+    grayscale (input_channels 3 or 1)."""
     if backbone._norm_cfg is None or backbone._norm_cfg.get('type') != 'BatchNorm2d':
         return False
     if backbone._activation_cfg.get('type') != 'ReLU' or backbone._frozen_stages > 0 or backbone._norm_eval:
         return False
-    if backbone._input_channels != 3:
+    if backbone._input_channels not in (1, 3):
         return False
     # the hand-written backward accumulates into EVERY covered parameter's .grad: a frozen parameter (requires_grad=False,
     # however it was frozen) sends the module through PyTorch-ROCm autograd instead
     if not all(p.requires_grad for p in backbone.parameters()):
         return False
+    first = backbone._stem[0]
     for m in backbone.modules():
-        if isinstance(m, nn.Conv2d) and not _conv_ok(m):
+        if isinstance(m, nn.Conv2d) and not _conv_ok(m, m is first):
             return False
         if isinstance(m, nn.BatchNorm2d) and (m.momentum is None or not m.affine or not m.track_running_stats
                                               or not m.training):
             return False          # incl. norm layers switched to eval() inside a training model: batch statistics only here
-    first = backbone._stem[0]
-    return first.out_channels in (32, 64) and first.kernel_size == (3, 3) and first.stride == (2, 2)
+    return (first.in_channels == backbone._input_channels and first.out_channels in (32, 64) and first.kernel_size == (3, 3)
+            and first.stride == (2, 2))
+
+
+def check_train_input(backbone, x):
+    """The HIP training path reads an NCHW float32 batch of the model's input_channels; an RGB batch for a gray model (or the
+    reverse) raises here, before any kernel reads it."""
+    c = backbone._input_channels
+    if x.dim() != 4 or x.dtype != torch.float32 or x.size(1) != c:
+        raise RuntimeError('training input: expected an NCHW float32 batch [N,%d,H,W] for an input_channels=%d model, got %s %s'
+                           % (c, c, x.dtype, tuple(x.shape)))
 
 
 def network_supported(model):
@@ -228,12 +242,14 @@ class _Packs(object):
                     ws.append(w.detach())
             if ws:
                 key = (id(units), data_gradient)
-                pb = _pack_batches.get(key)
+                pb = _pack_batches.pop(key, None)
                 if pb is None or not pb.matches(ws):
-                    if len(_pack_batches) > 32:
-                        _pack_batches.clear()
+                    # least recently used first: clearing the whole cache here could drop the OTHER pass of the schedule
+                    # just packed eagerly, and rebuild its job table (a host -> device copy) inside a graph capture
+                    while len(_pack_batches) >= 32:
+                        _pack_batches.pop(next(iter(_pack_batches)))
                     pb = ops.PackBatch(ws, data_gradient)
-                    _pack_batches[key] = pb
+                _pack_batches[key] = pb
                 for w, out in zip(ws, pb.run()):
                     self.c[(w.data_ptr(), data_gradient)] = out
 
@@ -1131,6 +1147,7 @@ class NetworkTrainFunction(torch.autograd.Function):
 
 
 def backbone_train_forward(backbone, x):
+    check_train_input(backbone, x)
     plan = backbone.__dict__.get('_lfd_train_plan')
     if plan is None:
         plan = build_units(backbone)
@@ -1140,6 +1157,7 @@ def backbone_train_forward(backbone, x):
 
 def network_train_forward(model, x):
     """-> (cls, reg, [(h, w)] per level)"""
+    check_train_input(model._backbone, x)
     plan = model.__dict__.get('_lfd_train_plan')
     if plan is None:
         units, outs = build_network(model)

@@ -1,5 +1,6 @@
 """Training-step timing (BASELINE.json configs[4]: WIDERFACE_LFD_S, synthetic 640x640, bs 32 per GPU): forward, fused
-get_loss, backward, gradient clipping + SGD.  Prints one JSON line per mode:
+get_loss, backward, gradient clipping + SGD.  --input-channels 1 times the model's grayscale twin on [N,1,H,W] batches.
+Prints one JSON line per mode:
   hip   : the whole network on the hand-written kernels (train_engine) + fused loss + flat SGD
   graph : the same iteration replayed as one HIP graph (lfd_amd.train.GraphedTrainStep)
   torch : the same nn.Modules through PyTorch-ROCm autograd (LFD_HIP_TRAIN=0), op-by-op loss, torch.optim.SGD
@@ -31,11 +32,11 @@ def run(mode, args):
     os.environ['LFD_HIP_TRAIN'] = '1' if hip else '0'
     os.environ['LFD_FUSED_LOSS'] = '1' if hip else '0'
     torch.manual_seed(0)
-    m = configs.build_model(args.model).cuda().train()
+    m = configs.build_model(args.model, input_channels=args.input_channels).cuda().train()
     kw = dict(lr=0.01, momentum=0.9, weight_decay=1e-4)
     opt = optim.SGD(m.parameters(), **kw) if hip else torch.optim.SGD(m.parameters(), **kw)
     rng = np.random.default_rng(0)
-    x = torch.randn(args.batch, 3, args.size, args.size, device='cuda')
+    x = torch.randn(args.batch, args.input_channels, args.size, args.size, device='cuda')
     ann = annotations(rng, args.batch, (args.size, args.size))
     clip = dict(max_norm=10, norm_type=2)
     if mode == 'graph':
@@ -51,7 +52,7 @@ def run(mode, args):
         lv, _ = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
-    print(json.dumps(dict(mode=mode, model=args.model, batch=args.batch, size=args.size, ms_per_step=round(dt * 1e3, 3),
+    print(json.dumps(dict(mode=mode, model=args.model, input_channels=args.input_channels, batch=args.batch, size=args.size, ms_per_step=round(dt * 1e3, 3),
                           images_per_s=round(args.batch / dt, 1), loss=lv['loss'],
                           peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))))
 
@@ -64,6 +65,7 @@ if __name__ == '__main__':
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--modes', default='hip,torch')
+    ap.add_argument('--input-channels', type=int, default=3, choices=(1, 3), help='3: RGB, 1: the grayscale twin')
     ap.add_argument('--concat', type=int, default=-1, help='train_engine.CONCAT_HEAD: 1 = shared head towers once over all pyramid '
                     'levels, 0 = level by level (default: the module\'s setting)')
     a = ap.parse_args()
