@@ -1095,6 +1095,40 @@ LFD_API int lfd_groupnorm_finalize_fold(const lfd_head_desc_t* desc, const float
                                         const float* const* gamma, const float* const* beta, float eps, float* ab,
                                         const lfd_head_level_ptrs_t* levels, int32_t which, lfd_stream_t stream);
 
+/* ---- training batch assembly (csrc/batch_assemble.hip) --------------------------------------------------------------------
+ * The device tail of the reference loader for RandomBBoxCropRegionSampler / IdleRegionSampler
+ * (lfd/data_pipeline/sampler/region_sampler.py:92-144,261-300, data_loader.py:68-124, augmentation_pipeline.py:14-36):
+ * uint8 HWC source pixels -> cv2 INTER_LINEAR resize (8-bit fixed-point scalar path) -> crop (uint8 0 outside the resized
+ * image) -> optional horizontal flip -> per-channel 256-entry fp32 table -> fp32 NCHW batch [n, c_out, h_out, w_out], 0.0f
+ * outside each image's valid_w x valid_h extent (the batch padding).
+ *
+ * Each image reads only its source WINDOW: window pixel (x, y) is at src + src_offset + y * src_pitch + x * c_src, for
+ * 0 <= x < win_w, 0 <= y < win_h, and holds source pixel (win_x0 + x, win_y0 + y).  The caller guarantees that every window
+ * lies inside the memory behind `src`; the kernel clamps every table index into its window, so a wrong table gives wrong
+ * pixels, never a read outside the window. */
+typedef struct lfd_batch_desc {
+  int64_t src_offset;       /* bytes from `src` to the window's first pixel */
+  int32_t src_pitch;        /* bytes between window rows, >= win_w * c_src; win_h * src_pitch < 2^31 */
+  int32_t win_x0, win_y0;   /* source coordinates of the window's first pixel */
+  int32_t win_w, win_h;     /* window extent in pixels, >= 1 */
+  int32_t valid_w, valid_h; /* the image's extent in the output (<= w_out, h_out); 0.0f beyond it */
+  int32_t flip;             /* 1: output column x (< valid_w) reads crop column valid_w - 1 - x */
+  int32_t reserved_;
+} lfd_batch_desc_t;
+
+/* coef: int32, image i at coef + 4 * i * (w_out + h_out): first w_out columns {sx0, sx1, a0, a1} (source columns of the two
+ * taps and their 11-bit weights, indexed by crop column, i.e. before the flip), then h_out rows {r0, r1, b0, b1}.  A crop
+ * column or row outside the resized image has zero weights (its value is uint8 0, as crop_from_image fills it).
+ * Per channel c of the output: v = clamp((H(r0) * b0 + H(r1) * b1 + 2^21) >> 22, 0, 255) with
+ * H(r) = S[r][sx0][map[c]] * a0 + S[r][sx1][map[c]] * a1, then out = lut[c * 256 + v].
+ * lut: fp32 [c_out][256]; map: int32 [c_out], the source channel of each output channel (BGR2RGB = {2, 1, 0}, a gray
+ * source tiled to 3 channels = {0, 0, 0}).
+ * desc, map: 8-byte aligned; coef, lut, out: 16-byte aligned.  LFD_ERR_INVALID_ARGUMENT: a null or misaligned pointer,
+ * c_src or c_out outside {1, 3}, n, h_out or w_out < 1; LFD_ERR_UNSUPPORTED: an output of 2^31 elements or more. */
+LFD_API int lfd_batch_assemble_f32(const uint8_t* src, const lfd_batch_desc_t* desc /*[n], device*/,
+                                   const int32_t* coef, const float* lut, const int32_t* map, int32_t n, int32_t c_src,
+                                   int32_t c_out, int32_t h_out, int32_t w_out, float* out, lfd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,13 @@ class WgradJob(C.Structure):
                 ('first_block', C.c_int32), ('next', C.c_int32), ('accumulate', C.c_int32), ('inv_scale', C.c_float)]
 
 
+class BatchDesc(C.Structure):
+    """lfd_batch_desc_t"""
+    _fields_ = [('src_offset', C.c_int64), ('src_pitch', C.c_int32), ('win_x0', C.c_int32), ('win_y0', C.c_int32),
+                ('win_w', C.c_int32), ('win_h', C.c_int32), ('valid_w', C.c_int32), ('valid_h', C.c_int32),
+                ('flip', C.c_int32), ('reserved_', C.c_int32)]
+
+
 class RowsumJob(C.Structure):
     """lfd_rowsum_job_t"""
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('nrows', C.c_int32), ('row_stride', C.c_int32),
@@ -289,6 +296,7 @@ _SIGNATURES = {
     'lfd_p32_groupnorm_workspace_bytes': (_SZ, [_I32, _I32]),
     'lfd_p32_groupnorm_relu_f32': (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _P, _F, _I32, _P, _SZ, _P]),
     'lfd_conv2d_downsample_nhwc_f16': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'lfd_batch_assemble_f32': (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
 }
 
 
