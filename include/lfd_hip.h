@@ -1129,6 +1129,87 @@ LFD_API int lfd_batch_assemble_f32(const uint8_t* src, const lfd_batch_desc_t* d
                                    const int32_t* coef, const float* lut, const int32_t* map, int32_t n, int32_t c_src,
                                    int32_t c_out, int32_t h_out, int32_t w_out, float* out, lfd_stream_t stream);
 
+/* ---- detection evaluation: COCO-style bbox AP (csrc/evaluate.hip) -----------------------------------------------------------
+ * The device side of lfd_amd/evaluation.py (the reference's COCOEvaluator, lfd/evaluation/coco_evaluator.py:13-82, which hands
+ * its detections to pycocotools).  The definition implemented is written out in DESIGN.md ("Evaluation"); it restates
+ * COCOeval (iouType 'bbox', useCats 1) from knowledge of pycocotools 2.0.x and is NOT verified against pycocotools itself.
+ * All IoU / precision / recall arithmetic is float64, evaluated operation for operation as that text states it.
+ *
+ * Images are addressed by their ordinal in ascending image id, categories by their index in ascending category id; a
+ * (image, category) pair is p = image * num_categories + category.  Boxes are {x, y, w, h}.
+ * Everything behind lfd_eval_bufs_t is device memory owned by the caller.  The entry points enqueue on `stream` and never
+ * synchronise; what only the device knows (the number of stored detections, capacity overflows) is kept in `state`:
+ *   state[0] detections stored; state[1] error bits (LFD_EVAL_ERR_*), sticky until the caller clears them;
+ *   state[2] detections that take part in the last lfd_eval_match (known category, evaluated image); state[3] active pairs.
+ * The caller zeroes state and img_mask to start (or restart) an accumulation. */
+#define LFD_EVAL_MAX_MAXDETS 8
+#define LFD_EVAL_MAX_RECTHRS 256
+#define LFD_EVAL_ERR_CAPACITY 1   /* an append did not fit det_capacity: nothing of that append was stored */
+#define LFD_EVAL_ERR_IMAGE 2      /* an image ordinal outside [0, num_images) */
+#define LFD_EVAL_ERR_LABEL 4      /* a label without a category (lfd_eval_append_dets_f32): the detection was dropped */
+typedef struct lfd_eval_desc {
+  int32_t num_images, num_categories, num_gt, det_capacity;
+  int32_t num_iou_thrs, num_area_rngs;   /* T, A; T * A <= 64 */
+  int32_t num_rec_thrs, num_max_dets;    /* R <= LFD_EVAL_MAX_RECTHRS, M <= LFD_EVAL_MAX_MAXDETS */
+  int32_t max_dets[LFD_EVAL_MAX_MAXDETS]; /* ascending; detections of a pair beyond max_dets[M-1] are not matched */
+} lfd_eval_desc_t;
+typedef struct lfd_eval_bufs {
+  /* the detection store, in insertion order */
+  double* det_box;            /* [det_capacity, 4] */
+  double* det_score;          /* [det_capacity] */
+  int32_t* det_img;           /* [det_capacity] image ordinal */
+  int32_t* det_cat;           /* [det_capacity] category index, -1: no category (never evaluated) */
+  int32_t* state;             /* [4], see above */
+  int32_t* img_mask;          /* [num_images] 1: the image is evaluated */
+  /* ground truth, sorted by pair (stable: annotation order inside a pair) */
+  const double* gt_box;       /* [num_gt, 4] */
+  const double* gt_area;      /* [num_gt] */
+  const int32_t* gt_crowd;    /* [num_gt] */
+  const int32_t* gt_pair_start; /* [num_images * num_categories + 1] first ground truth of each pair */
+  /* parameters, computed by the caller (numpy linspace) and only read here */
+  const double* iou_thrs;     /* [T] */
+  const double* area_rng;     /* [A, 2] {lo, hi} */
+  const double* rec_thrs;     /* [R] */
+  /* lfd_eval_match -> lfd_eval_accumulate: one entry per participating detection, pair-major, rank order inside a pair */
+  int32_t* order;             /* [det_capacity] index into the store */
+  uint64_t* sort_key;         /* [det_capacity] descending-score key */
+  int32_t* sorted_cat;        /* [det_capacity] */
+  int32_t* sorted_rank;       /* [det_capacity] rank inside the pair (score descending, ties in insertion order) */
+  uint64_t* match_bits;       /* [det_capacity] bit t * A + a: matched at threshold t in area range a */
+  uint64_t* ignore_bits;      /* [det_capacity] same layout: ignored */
+  int32_t* npig;              /* [num_categories, A] non-ignored ground truth of the evaluated images */
+  int32_t* cat_start;         /* [num_categories + 1] first entry of each category once sorted by category */
+  /* results */
+  double* precision;          /* [T, R, K, A, M], -1: no non-ignored ground truth */
+  double* recall;             /* [T, K, A, M] */
+} lfd_eval_bufs_t;
+
+/* Append the kept boxes of a detection step (lfd_detect_batched outputs: dets [n, cap, 5] = {x1, y1, x2, y2, score},
+ * labels [n, cap], counts [n, 4] with the number kept in counts[i][1], read on the device) as {x1, y1, x2 - x1 + 1,
+ * y2 - y1 + 1} (fp32 arithmetic, then widened).  label_map [num_labels]: category index of each label, -1: none.
+ * img_ord [n] (device): image ordinal of each batch entry.  An image is marked for evaluation when it contributed a box,
+ * or always with mark_all != 0. */
+LFD_API int lfd_eval_append_dets_f32(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t* bufs, const float* dets,
+                                     const int32_t* labels, const int32_t* counts, int32_t n, int32_t cap,
+                                     const int32_t* label_map, int32_t num_labels, const int32_t* img_ord,
+                                     int32_t mark_all, lfd_stream_t stream);
+/* Append m rows {image ordinal, category index, score, x, y, w, h} (float64, device) and mark their images; `mark`
+ * [num_mark] (device, may be NULL with num_mark 0) lists further image ordinals to mark. */
+LFD_API int lfd_eval_append_rows_f64(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t* bufs, const double* rows, int64_t m,
+                                     const int32_t* mark, int32_t num_mark, lfd_stream_t stream);
+/* Stage 1: groups the stored detections by pair, ranks each pair's detections by score (stable) and runs the greedy
+ * matching of every pair that has a detection or a ground-truth box, for all T thresholds and A area ranges.  One
+ * workgroup per active pair (a persistent grid walks the compacted pair list, never the dense images x categories grid);
+ * ground truth is processed in tiles of 64, any number per pair. */
+LFD_API size_t lfd_eval_match_workspace_bytes(const lfd_eval_desc_t* desc);
+LFD_API int lfd_eval_match(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t* bufs, void* workspace, size_t workspace_bytes,
+                           lfd_stream_t stream);
+/* Stage 2: stable sort by (category, score descending) of what stage 1 left, then per (category, area range, max_dets
+ * entry, threshold) the running true / false positive counts, the precision envelope and its samples at the recall points. */
+LFD_API size_t lfd_eval_accumulate_workspace_bytes(const lfd_eval_desc_t* desc);
+LFD_API int lfd_eval_accumulate(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t* bufs, void* workspace,
+                                size_t workspace_bytes, lfd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,21 @@ class BatchDesc(C.Structure):
                 ('flip', C.c_int32), ('reserved_', C.c_int32)]
 
 
+class EvalDesc(C.Structure):
+    """lfd_eval_desc_t"""
+    _fields_ = [('num_images', C.c_int32), ('num_categories', C.c_int32), ('num_gt', C.c_int32), ('det_capacity', C.c_int32),
+                ('num_iou_thrs', C.c_int32), ('num_area_rngs', C.c_int32), ('num_rec_thrs', C.c_int32),
+                ('num_max_dets', C.c_int32), ('max_dets', C.c_int32 * 8)]
+
+
+class EvalBufs(C.Structure):
+    """lfd_eval_bufs_t"""
+    _fields_ = [(k, C.c_void_p) for k in ('det_box', 'det_score', 'det_img', 'det_cat', 'state', 'img_mask', 'gt_box', 'gt_area',
+                                          'gt_crowd', 'gt_pair_start', 'iou_thrs', 'area_rng', 'rec_thrs', 'order', 'sort_key',
+                                          'sorted_cat', 'sorted_rank', 'match_bits', 'ignore_bits', 'npig', 'cat_start',
+                                          'precision', 'recall')]
+
+
 class RowsumJob(C.Structure):
     """lfd_rowsum_job_t"""
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('nrows', C.c_int32), ('row_stride', C.c_int32),
@@ -297,6 +312,12 @@ _SIGNATURES = {
     'lfd_p32_groupnorm_relu_f32': (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _P, _F, _I32, _P, _SZ, _P]),
     'lfd_conv2d_downsample_nhwc_f16': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'lfd_batch_assemble_f32': (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    'lfd_eval_append_dets_f32': (C.c_int, [C.POINTER(EvalDesc), C.POINTER(EvalBufs), _P, _P, _P, _I32, _I32, _P, _I32, _P, _I32, _P]),
+    'lfd_eval_append_rows_f64': (C.c_int, [C.POINTER(EvalDesc), C.POINTER(EvalBufs), _P, _I64, _P, _I32, _P]),
+    'lfd_eval_match_workspace_bytes': (_SZ, [C.POINTER(EvalDesc)]),
+    'lfd_eval_match': (C.c_int, [C.POINTER(EvalDesc), C.POINTER(EvalBufs), _P, _SZ, _P]),
+    'lfd_eval_accumulate_workspace_bytes': (_SZ, [C.POINTER(EvalDesc)]),
+    'lfd_eval_accumulate': (C.c_int, [C.POINTER(EvalDesc), C.POINTER(EvalBufs), _P, _SZ, _P]),
 }
 
 

@@ -1,0 +1,350 @@
+"""Detection evaluation on the device: the reference's `Evaluator` / `COCOEvaluator` (lfd/evaluation/base_evaluator.py,
+coco_evaluator.py:13-82) over csrc/evaluate.hip instead of pycocotools.
+
+The definition of the numbers is written out in DESIGN.md ("Evaluation"): COCOeval with iouType 'bbox', useCats 1 and
+maxDets [100, 300, 1000], restated from knowledge of pycocotools 2.0.x.  pycocotools is not a dependency and was never run
+against this code: AGREEMENT WITH PYCOCOTOOLS ITSELF IS NOT VERIFIED.  tests/golden/coco_eval_oracle.py is the same
+definition as plain numpy loops; the kernels are tested against it.
+
+Importing this module and constructing an evaluator need no GPU (the ground truth is parsed on the host and uploaded when a
+device is first needed); update / update_resident / a non-empty evaluate run on the MI355X only.
+"""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+
+__all__ = ['Evaluator', 'COCOEvaluator']
+
+METRIC_ITEMS = ['mAP', 'mAP_50', 'mAP_75', 'mAP_s', 'mAP_m', 'mAP_l']
+MAX_DETS = (100, 300, 1000)
+ERR_CAPACITY, ERR_IMAGE, ERR_LABEL = 1, 2, 4      # LFD_EVAL_ERR_*
+
+
+class Evaluator(object):
+
+    def update(self, results):
+        raise NotImplementedError
+
+    def evaluate(self):
+        raise NotImplementedError
+
+
+def coco_params():
+    """(iouThrs [10], recThrs [101], areaRng [4, 2]) as float64, computed on the host exactly as pycocotools' Params does."""
+    iou_thrs = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+    rec_thrs = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+    area_rng = np.array([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], np.float64)
+    return iou_thrs, rec_thrs, area_rng
+
+
+def summarize(precision, recall):
+    """The 12 `stats` of COCOeval.summarize for maxDets [100, 300, 1000]: stats[0] is taken at maxDets[0] = 100 while the
+    other precision entries use maxDets[-1] = 1000 -- pycocotools' behaviour with this list, not a typo."""
+    def mean(x):
+        x = x[x > -1]
+        return float(np.mean(x)) if x.size else -1.0
+    M = precision.shape[4]
+    ap = lambda a, m, t=None: mean(precision[:, :, :, a, m] if t is None else precision[t, :, :, a, m])   # noqa: E731
+    ar = lambda a, m: mean(recall[:, :, a, m])   # noqa: E731
+    last = M - 1
+    return np.array([ap(0, 0), ap(0, last, 0), ap(0, last, 5), ap(1, last), ap(2, last), ap(3, last),
+                     ar(0, 0), ar(0, min(1, last)), ar(0, last), ar(1, last), ar(2, last), ar(3, last)], np.float64)
+
+
+def format_display(stats):
+    """The reference's display string (coco_evaluator.py:57-77); stats None: nothing was detected."""
+    s = '\n'
+    if stats is None:
+        return s + 'No bboxes detected! Evaluation abort!\n'
+    for i, metric in enumerate(METRIC_ITEMS):
+        s += '{:<10}:{:.5f}\n'.format(metric, stats[i])
+    return s
+
+
+class COCOEvaluator(Evaluator):
+    """Drop-in for the reference's COCOEvaluator (config_dict['evaluator']): same constructor arguments, `update`,
+    `evaluate`, `get_eval_display_str`; plus `update_resident` for ops.DetectOutputs that never leave the device.
+
+    annotation_path: a COCO instances_*.json; annotations: the same structure as a dict (one of the two).
+    all_images=False keeps the reference's quirk: an image is evaluated only if it produced at least one detection
+    (coco_evaluator.py:47-53), so an image with ground truth and no detection does not count against recall;
+    all_images=True evaluates every image passed to update / update_resident."""
+
+    def __init__(self, annotation_path=None, label_indexes_to_category_ids=None, annotations=None, device=None, all_images=False):
+        if (annotation_path is None) == (annotations is None):
+            raise ValueError('give exactly one of annotation_path and annotations')
+        if not isinstance(label_indexes_to_category_ids, dict):
+            raise TypeError('label index to category id must be a dict!!!')
+        if annotation_path is not None:
+            if not os.path.isfile(annotation_path):
+                raise FileNotFoundError('annotation file does not exist!!! (%s)' % annotation_path)
+            with open(annotation_path) as f:
+                annotations = json.load(f)
+        if not isinstance(annotations, dict) or 'annotations' not in annotations:
+            raise ValueError("annotations must be a COCO dict with an 'annotations' list")
+        self._label_indexes_to_category_ids = dict(label_indexes_to_category_ids)
+        self._all_images = bool(all_images)
+        self._device = device
+        self._eval_display_str = ''
+        self._parse(annotations)
+        self.iou_thrs, self.rec_thrs, self.area_rng = coco_params()
+        self.max_dets = MAX_DETS
+        self.stats = self.precision = self.recall = None
+        self._dev = None           # device state, built on first use
+        self._host_rows = 0        # rows appended through update()
+        self._resident_calls = 0
+        self._upper = 0            # upper bound of the detections stored on the device
+        self._last = None
+        import torch
+        if torch.cuda.is_available():
+            self._state()          # the ground truth is uploaded once, here
+
+    # ------------------------------------------------------------------ ground truth (host)
+    def _parse(self, ann):
+        anns = ann['annotations']
+        image_ids = set(im['id'] for im in ann.get('images', ())) | set(a['image_id'] for a in anns)
+        cat_ids = set(c['id'] for c in ann.get('categories', ())) | set(a['category_id'] for a in anns)
+        if not image_ids or not cat_ids:
+            raise ValueError('the annotations name no image or no category')
+        self.image_ids = sorted(image_ids)
+        self.category_ids = sorted(cat_ids)
+        self._img_ord = {v: i for i, v in enumerate(self.image_ids)}
+        self._cat_idx = {v: i for i, v in enumerate(self.category_ids)}
+        for lab, cid in self._label_indexes_to_category_ids.items():
+            if cid not in self._cat_idx:
+                raise ValueError('label %r maps to category id %r, which the annotations do not have' % (lab, cid))
+        I, K, G = len(self.image_ids), len(self.category_ids), len(anns)
+        pair = np.array([self._img_ord[a['image_id']] * K + self._cat_idx[a['category_id']] for a in anns], np.int64).reshape(G)
+        order = np.argsort(pair, kind='stable')
+        box = np.array([a['bbox'] for a in anns], np.float64).reshape(G, 4)
+        area = np.array([a['area'] if 'area' in a else a['bbox'][2] * a['bbox'][3] for a in anns], np.float64).reshape(G)
+        crowd = np.array([int(a.get('iscrowd', 0)) for a in anns], np.int32).reshape(G)
+        self.gt_pair = pair[order]
+        self.gt_box, self.gt_area, self.gt_crowd = box[order], area[order], crowd[order]
+        self.gt_pair_start = np.searchsorted(self.gt_pair, np.arange(I * K + 1), side='left').astype(np.int32)
+        lmax = max([int(l) for l in self._label_indexes_to_category_ids] + [0])
+        self._label_map = np.full(lmax + 1, -1, np.int32)
+        for lab, cid in self._label_indexes_to_category_ids.items():
+            if int(lab) >= 0:
+                self._label_map[int(lab)] = self._cat_idx[cid]
+
+    # ------------------------------------------------------------------ device state
+    def _state(self):
+        if self._dev is not None:
+            return self._dev
+        import torch
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError('COCOEvaluator: the evaluation kernels run on the MI355X only; there is no CPU implementation')
+        dev = torch.device(self._device) if self._device is not None else torch.device('cuda', torch.cuda.current_device())
+        d = type('EvalDeviceState', (), {})()
+        d.torch, d.lib, d.dev = torch, _lib, dev
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+        G = len(self.gt_area)
+        d.gt_box = up(self.gt_box if G else np.zeros((1, 4)))
+        d.gt_area = up(self.gt_area if G else np.zeros(1))
+        d.gt_crowd = up(self.gt_crowd if G else np.zeros(1, np.int32))
+        d.gt_pair_start = up(self.gt_pair_start)
+        d.iou_thrs, d.rec_thrs, d.area_rng = up(self.iou_thrs), up(self.rec_thrs), up(self.area_rng)
+        d.label_map = up(self._label_map)
+        d.state = torch.zeros(4, dtype=torch.int32, device=dev)
+        d.img_mask = torch.zeros(len(self.image_ids), dtype=torch.int32, device=dev)
+        d.cap = 0
+        d.det_box = d.det_score = d.det_img = d.det_cat = None
+        self._dev = d
+        self._reserve(1 << 16)
+        return d
+
+    def _reserve(self, need):
+        """grow the detection store to hold `need` entries (device-to-device copies on the current stream, no sync)"""
+        d = self._dev
+        if need <= d.cap:
+            return
+        torch = d.torch
+        cap = max(int(need), 2 * d.cap)
+        new = [torch.empty((cap, 4), dtype=torch.float64, device=d.dev), torch.empty(cap, dtype=torch.float64, device=d.dev),
+               torch.empty(cap, dtype=torch.int32, device=d.dev), torch.empty(cap, dtype=torch.int32, device=d.dev)]
+        if d.cap:
+            for n, o in zip(new, (d.det_box, d.det_score, d.det_img, d.det_cat)):
+                n[:d.cap].copy_(o)
+        d.det_box, d.det_score, d.det_img, d.det_cat = new
+        d.cap = cap
+
+    def _desc(self):
+        d = self._dev
+        desc = d.lib.EvalDesc()
+        desc.num_images, desc.num_categories = len(self.image_ids), len(self.category_ids)
+        desc.num_gt, desc.det_capacity = len(self.gt_area), d.cap
+        desc.num_iou_thrs, desc.num_area_rngs = len(self.iou_thrs), len(self.area_rng)
+        desc.num_rec_thrs, desc.num_max_dets = len(self.rec_thrs), len(self.max_dets)
+        for i, m in enumerate(self.max_dets):
+            desc.max_dets[i] = int(m)
+        return desc
+
+    def _bufs(self, **extra):
+        d = self._dev
+        b = d.lib.EvalBufs()
+        for k in ('det_box', 'det_score', 'det_img', 'det_cat', 'state', 'img_mask', 'gt_box', 'gt_area', 'gt_crowd',
+                  'gt_pair_start', 'iou_thrs', 'area_rng', 'rec_thrs'):
+            setattr(b, k, getattr(d, k).data_ptr())
+        for k, t in extra.items():
+            setattr(b, k, t.data_ptr())
+        return b
+
+    def _ordinals(self, meta_batch):
+        try:
+            return [self._img_ord[m['image_id']] for m in meta_batch]
+        except KeyError as e:
+            raise ValueError('image id %s is not in the annotations' % e)
+
+    # ------------------------------------------------------------------ accumulation
+    def update(self, results):
+        """results: tuple(predict_bboxes, meta_batch); predict_bboxes[i] is a list of [label, score, x, y, w, h] rows for
+        image meta_batch[i]['image_id'] (what LFD.get_results returns)."""
+        if not (isinstance(results, tuple) and len(results) == 2):
+            raise TypeError('update info should contain two parts: predict bboxes and meta info.')
+        predict_bboxes, meta_batch = results
+        if len(predict_bboxes) != len(meta_batch):
+            raise ValueError('%d prediction lists for %d meta entries' % (len(predict_bboxes), len(meta_batch)))
+        ords = self._ordinals(meta_batch)
+        rows = []
+        for o, boxes in zip(ords, predict_bboxes):
+            for r in boxes:
+                cid = self._label_indexes_to_category_ids[r[0]]      # KeyError for an unknown label, as the reference
+                rows.append((o, self._cat_idx[cid], r[1], r[2], r[3], r[4], r[5]))
+        mark = ords if self._all_images else []
+        if not rows and not mark:
+            return
+        d = self._state()
+        torch = d.torch
+        self._upper += len(rows)
+        self._reserve(self._upper)
+        with torch.cuda.device(d.dev):
+            rows_t = torch.from_numpy(np.array(rows, np.float64).reshape(len(rows), 7)).to(d.dev) if rows else None
+            mark_t = torch.tensor(mark, dtype=torch.int32).to(d.dev) if mark else None
+            desc, bufs = self._desc(), self._bufs()
+            d.lib.check(d.lib.lib().lfd_eval_append_rows_f64(C.byref(desc), C.byref(bufs), d.lib.ptr(rows_t), len(rows),
+                                                             d.lib.ptr(mark_t), len(mark), d.lib.stream_ptr()),
+                        'lfd_eval_append_rows_f64')
+        self._host_rows += len(rows)
+
+    def update_resident(self, outputs, meta_batch):
+        """Appends the kept boxes of an ops.DetectOutputs (LFD.detect / detect_resident) on the device: no .item(),
+        .tolist(), .cpu() or synchronisation; the number of kept boxes is read from outputs.counts by the kernel.  The only
+        host -> device traffic is the batch's image ordinals (pinned, asynchronous)."""
+        n, cap = int(outputs.dets.size(0)), int(outputs.dets.size(1))
+        if len(meta_batch) != n:
+            raise ValueError('%d meta entries for a batch of %d' % (len(meta_batch), n))
+        ords = self._ordinals(meta_batch)
+        d = self._state()
+        torch = d.torch
+        if outputs.dets.device != d.dev:
+            raise RuntimeError('update_resident: the outputs live on %s, the evaluator on %s' % (outputs.dets.device, d.dev))
+        self._upper += n * cap
+        self._reserve(self._upper)
+        with torch.cuda.device(d.dev):
+            host = torch.empty(n, dtype=torch.int32, pin_memory=True)
+            host.numpy()[:] = ords
+            ord_t = host.to(d.dev, non_blocking=True)
+            desc, bufs = self._desc(), self._bufs()
+            d.lib.check(d.lib.lib().lfd_eval_append_dets_f32(C.byref(desc), C.byref(bufs), d.lib.ptr(outputs.dets),
+                                                             d.lib.ptr(outputs.labels), d.lib.ptr(outputs.counts), n, cap,
+                                                             d.lib.ptr(d.label_map), int(d.label_map.numel()), d.lib.ptr(ord_t),
+                                                             int(self._all_images), d.lib.stream_ptr()),
+                        'lfd_eval_append_dets_f32')
+        self._resident_calls += 1
+
+    # ------------------------------------------------------------------ evaluation
+    def _run(self, timing=None):
+        """enqueue both stages; returns the device tensors (no synchronisation)"""
+        d = self._state()
+        torch, lib = d.torch, d.lib
+        T, R, K, A, M = len(self.iou_thrs), len(self.rec_thrs), len(self.category_ids), len(self.area_rng), len(self.max_dets)
+        with torch.cuda.device(d.dev):
+            i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=d.dev)   # noqa: E731
+            i64 = lambda *s: torch.empty(s, dtype=torch.int64, device=d.dev)   # noqa: E731
+            out = dict(order=i32(d.cap), sort_key=i64(d.cap), sorted_cat=i32(d.cap), sorted_rank=i32(d.cap),
+                       match_bits=i64(d.cap), ignore_bits=i64(d.cap), npig=i32(K, A), cat_start=i32(K + 1),
+                       precision=torch.empty((T, R, K, A, M), dtype=torch.float64, device=d.dev),
+                       recall=torch.empty((T, K, A, M), dtype=torch.float64, device=d.dev))
+            desc, bufs = self._desc(), self._bufs(**out)
+            wm = lib.lib().lfd_eval_match_workspace_bytes(C.byref(desc))
+            wa = lib.lib().lfd_eval_accumulate_workspace_bytes(C.byref(desc))
+            if wm == 0 or wa == 0:
+                raise RuntimeError('COCOEvaluator: this problem size is not supported by the evaluation kernels')
+            ws_m = torch.empty(wm, dtype=torch.uint8, device=d.dev)
+            ws_a = torch.empty(wa, dtype=torch.uint8, device=d.dev)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
+            if ev:
+                ev[0].record()
+            lib.check(lib.lib().lfd_eval_match(C.byref(desc), C.byref(bufs), lib.ptr(ws_m), wm, lib.stream_ptr()), 'lfd_eval_match')
+            if ev:
+                ev[1].record()
+            lib.check(lib.lib().lfd_eval_accumulate(C.byref(desc), C.byref(bufs), lib.ptr(ws_a), wa, lib.stream_ptr()),
+                      'lfd_eval_accumulate')
+            if ev:
+                ev[2].record()
+                timing.append(ev)
+        out['ws'] = (ws_m, ws_a)
+        return out
+
+    def evaluate(self, keep_matches=False):
+        """Runs both stages on what update / update_resident accumulated, fills `stats` (12 values), `precision`
+        [T, R, K, A, M] and `recall` [T, K, A, M] (numpy), builds the display string and clears the accumulated
+        detections.  keep_matches=True keeps the per-detection flags of stage 1 for `match_table()`."""
+        self.stats = self.precision = self.recall = None
+        self._last = None
+        if self._host_rows == 0 and self._resident_calls == 0:
+            self._eval_display_str = format_display(None)
+            self._clear()
+            return
+        d = self._state()
+        torch = d.torch
+        out = self._run()
+        with torch.cuda.device(d.dev):
+            tail = torch.cat([out['precision'].reshape(-1), out['recall'].reshape(-1), d.state.double()]).cpu().numpy()   # the one D2H
+        np_, nr = out['precision'].numel(), out['recall'].numel()
+        state = tail[np_ + nr:].astype(np.int64)
+        err = int(state[1])
+        n_det = int(state[0])
+        if keep_matches and not err:
+            n = int(state[2])
+            self._last = dict((k, out[k][:n].cpu().numpy()) for k in ('order', 'sorted_cat', 'sorted_rank', 'match_bits', 'ignore_bits'))
+            self._last['npig'] = out['npig'].cpu().numpy()
+            self._last['n_det'] = n_det
+        self._clear()
+        if err:
+            msgs = [m for bit, m in ((ERR_CAPACITY, 'the detection store overflowed'), (ERR_IMAGE, 'an image ordinal was out of range'),
+                                     (ERR_LABEL, 'a detection carried a label that label_indexes_to_category_ids does not map'))
+                    if err & bit]
+            raise RuntimeError('COCOEvaluator: ' + '; '.join(msgs) + ' (status bits %d); the accumulated detections were dropped' % err)
+        if n_det == 0:
+            self._eval_display_str = format_display(None)
+            return
+        self.precision = tail[:np_].reshape(out['precision'].shape)
+        self.recall = tail[np_:np_ + nr].reshape(out['recall'].shape)
+        self.stats = summarize(self.precision, self.recall)
+        self._eval_display_str = format_display(self.stats)
+
+    def match_table(self):
+        """After evaluate(keep_matches=True): dict of numpy arrays, one row per detection that took part --
+        `index` (insertion index), `category` (index), `rank` (inside its (image, category) pair), `matched` and `ignored`
+        [n, T, A] bool; plus `npig` [K, A]."""
+        if self._last is None:
+            raise RuntimeError('match_table: call evaluate(keep_matches=True) first')
+        T, A = len(self.iou_thrs), len(self.area_rng)
+        bits = np.arange(T * A, dtype=np.uint64)
+        unpack = lambda v: ((v.astype(np.uint64)[:, None] >> bits) & np.uint64(1)).astype(bool).reshape(-1, T, A)   # noqa: E731
+        return dict(index=self._last['order'], category=self._last['sorted_cat'], rank=self._last['sorted_rank'],
+                    matched=unpack(self._last['match_bits']), ignored=unpack(self._last['ignore_bits']), npig=self._last['npig'])
+
+    def _clear(self):
+        self._host_rows = self._resident_calls = self._upper = 0
+        if self._dev is not None:
+            self._dev.state.zero_()
+            self._dev.img_mask.zero_()
+
+    def get_eval_display_str(self):
+        return self._eval_display_str
