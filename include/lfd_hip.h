@@ -1210,6 +1210,74 @@ LFD_API size_t lfd_eval_accumulate_workspace_bytes(const lfd_eval_desc_t* desc);
 LFD_API int lfd_eval_accumulate(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t* bufs, void* workspace,
                                 size_t workspace_bytes, lfd_stream_t stream);
 
+/* ---- detection evaluation: the TT100K protocol, accuracy / recall (csrc/evaluate_tt100k.hip) -------------------------------
+ * The device side of lfd_amd/evaluation.py TT100KEvaluator: eval_annos of the reference's TT100K_train/official_eval.py
+ * (called from TT100K_train/evaluation.py:70-79), restated in DESIGN.md 9b.  Per evaluated image one global greedy matching
+ * in IoU-descending order (ties: ground-truth index, then detection index; strict IoU > iou), computed once per
+ * (iou, minscore) and read by every size band.  All arithmetic is float64, evaluated as the definition writes it.
+ *
+ * The detection store, `state` and `img_mask` work as in lfd_eval_bufs_t (same LFD_EVAL_ERR_* bits); boxes are
+ * {xmin, ymin, xmax, ymax} and scores are scaled to 0..100.  Every image named by an append is evaluated, with or without
+ * detections.  state[2]: detections grouped by the last lfd_eval_tt100k_match.  Cells are indexed [iou, minscore, size range]. */
+#define LFD_TT100K_DET_EXCLUDED 0   /* outside `types`, below minscore, outside the size band, or matched to such a ground truth */
+#define LFD_TT100K_DET_RIGHT 1
+#define LFD_TT100K_DET_WRONG 2      /* matched to a ground truth of another category (check_type) */
+#define LFD_TT100K_DET_UNMATCHED 3
+#define LFD_TT100K_GT_EXCLUDED 0
+#define LFD_TT100K_GT_MISSED 1
+#define LFD_TT100K_GT_MATCHED 2
+typedef struct lfd_eval_tt100k_desc {
+  int32_t num_images, num_categories, num_gt, det_capacity;
+  int32_t num_ious, num_minscores, num_size_ranges;   /* T, M, S >= 1; T * M <= 4096 */
+  int32_t check_type, match_same;
+} lfd_eval_tt100k_desc_t;
+typedef struct lfd_eval_tt100k_bufs {
+  /* the detection store, in insertion order */
+  double* det_box;             /* [det_capacity, 4] {xmin, ymin, xmax, ymax} */
+  double* det_score;           /* [det_capacity] 0..100 */
+  int32_t* det_img;            /* [det_capacity] image ordinal */
+  int32_t* det_cat;            /* [det_capacity] category index, -1: none */
+  int32_t* state;              /* [4] */
+  int32_t* img_mask;           /* [num_images] 1: the image is evaluated */
+  /* ground truth, sorted by image (stable: annotation order inside an image) */
+  const double* gt_box;        /* [num_gt, 4] {xmin, ymin, xmax, ymax} */
+  const int32_t* gt_cat;       /* [num_gt] category index */
+  const int32_t* gt_start;     /* [num_images + 1] */
+  const int32_t* cat_in_types; /* [num_categories] 1: the category takes part (all 1: no category filter) */
+  const double* ious;          /* [T] */
+  const double* minscores;     /* [M] */
+  const double* size_ranges;   /* [S, 2] {minboxsize, maxboxsize} */
+  /* results of lfd_eval_tt100k_match; "grouped" positions are image-major, insertion order inside an image */
+  int32_t* det_start;          /* [num_images + 1] first grouped position of each image */
+  int32_t* det_index;          /* [det_capacity] grouped position -> index into the store */
+  int32_t* det_match;          /* [T * M, det_capacity] per grouped position: matched ground truth (index inside its image), -1
+                                  unmatched, -2 taken out before the matching */
+  int32_t* gt_match;           /* [T * M, num_gt] matched detection (index inside its image), -1, -2 */
+  uint64_t* totals;            /* [T, M, S, 3] {right, counted detections, counted ground truth} */
+  uint64_t* per_category;      /* [T, M, S, num_categories, 3] the same by category, or NULL */
+  uint8_t* det_code;           /* [T, M, S, det_capacity] LFD_TT100K_DET_* per grouped position, or NULL */
+  uint8_t* gt_code;            /* [T, M, S, num_gt] LFD_TT100K_GT_*, or NULL */
+} lfd_eval_tt100k_bufs_t;
+
+/* Append the kept boxes of a detection step (as lfd_eval_append_dets_f32 reads them) the way the reference's
+ * TT100K_train/evaluation.py:42-55 builds its results: w = x2 - x1 + 1 and h in fp32, then xmax = (double)w + (double)x1,
+ * ymax likewise, score = (double)score * 100.  Every batch entry's image is marked for evaluation. */
+LFD_API int lfd_eval_tt100k_append_dets_f32(const lfd_eval_tt100k_desc_t* desc, const lfd_eval_tt100k_bufs_t* bufs,
+                                            const float* dets, const int32_t* labels, const int32_t* counts, int32_t n,
+                                            int32_t cap, const int32_t* label_map, int32_t num_labels, const int32_t* img_ord,
+                                            lfd_stream_t stream);
+/* Append m rows {image ordinal, category index, score, x, y, w, h} (float64, device): score * 100, xmax = w + x, ymax = h + y;
+ * `mark` [num_mark] (device, may be NULL with num_mark 0) lists image ordinals to evaluate whether or not they have a row. */
+LFD_API int lfd_eval_tt100k_append_rows_f64(const lfd_eval_tt100k_desc_t* desc, const lfd_eval_tt100k_bufs_t* bufs,
+                                            const double* rows, int64_t m, const int32_t* mark, int32_t num_mark,
+                                            lfd_stream_t stream);
+/* Groups the store by image in insertion order, runs the matching of every evaluated image for all T * M (iou, minscore)
+ * pairs (one workgroup each; IoU tile in LDS when it fits, recomputed round by round when not: any number of boxes per
+ * image), applies the S size bands and sums the counts (integer atomics: the result does not depend on the schedule). */
+LFD_API size_t lfd_eval_tt100k_workspace_bytes(const lfd_eval_tt100k_desc_t* desc);
+LFD_API int lfd_eval_tt100k_match(const lfd_eval_tt100k_desc_t* desc, const lfd_eval_tt100k_bufs_t* bufs, void* workspace,
+                                  size_t workspace_bytes, lfd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

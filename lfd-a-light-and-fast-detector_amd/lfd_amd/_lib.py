@@ -181,6 +181,19 @@ class EvalBufs(C.Structure):
                                           'precision', 'recall')]
 
 
+class TT100KEvalDesc(C.Structure):
+    """lfd_eval_tt100k_desc_t"""
+    _fields_ = [(k, C.c_int32) for k in ('num_images', 'num_categories', 'num_gt', 'det_capacity', 'num_ious', 'num_minscores',
+                                         'num_size_ranges', 'check_type', 'match_same')]
+
+
+class TT100KEvalBufs(C.Structure):
+    """lfd_eval_tt100k_bufs_t"""
+    _fields_ = [(k, C.c_void_p) for k in ('det_box', 'det_score', 'det_img', 'det_cat', 'state', 'img_mask', 'gt_box', 'gt_cat',
+                                          'gt_start', 'cat_in_types', 'ious', 'minscores', 'size_ranges', 'det_start', 'det_index',
+                                          'det_match', 'gt_match', 'totals', 'per_category', 'det_code', 'gt_code')]
+
+
 class RowsumJob(C.Structure):
     """lfd_rowsum_job_t"""
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('nrows', C.c_int32), ('row_stride', C.c_int32),
@@ -318,6 +331,11 @@ _SIGNATURES = {
     'lfd_eval_match': (C.c_int, [C.POINTER(EvalDesc), C.POINTER(EvalBufs), _P, _SZ, _P]),
     'lfd_eval_accumulate_workspace_bytes': (_SZ, [C.POINTER(EvalDesc)]),
     'lfd_eval_accumulate': (C.c_int, [C.POINTER(EvalDesc), C.POINTER(EvalBufs), _P, _SZ, _P]),
+    'lfd_eval_tt100k_append_dets_f32': (C.c_int, [C.POINTER(TT100KEvalDesc), C.POINTER(TT100KEvalBufs), _P, _P, _P, _I32, _I32, _P, _I32,
+                                                  _P, _P]),
+    'lfd_eval_tt100k_append_rows_f64': (C.c_int, [C.POINTER(TT100KEvalDesc), C.POINTER(TT100KEvalBufs), _P, _I64, _P, _I32, _P]),
+    'lfd_eval_tt100k_workspace_bytes': (_SZ, [C.POINTER(TT100KEvalDesc)]),
+    'lfd_eval_tt100k_match': (C.c_int, [C.POINTER(TT100KEvalDesc), C.POINTER(TT100KEvalBufs), _P, _SZ, _P]),
 }
 
 

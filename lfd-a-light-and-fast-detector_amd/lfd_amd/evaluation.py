@@ -6,6 +6,11 @@ maxDets [100, 300, 1000], restated from knowledge of pycocotools 2.0.x.  pycocot
 against this code: AGREEMENT WITH PYCOCOTOOLS ITSELF IS NOT VERIFIED.  tests/golden/coco_eval_oracle.py is the same
 definition as plain numpy loops; the kernels are tested against it.
 
+`TT100KEvaluator` is the other protocol the reference uses: the TT100K dataset's official accuracy / recall
+(TT100K_train/official_eval.py eval_annos, called from TT100K_train/evaluation.py:70-79) over csrc/evaluate_tt100k.hip.  Its
+definition is DESIGN.md 9b; tests/golden/ref_tt100k_eval.npz holds what the reference itself computes and the tests compare
+with it exactly.
+
 Importing this module and constructing an evaluator need no GPU (the ground truth is parsed on the host and uploaded when a
 device is first needed); update / update_resident / a non-empty evaluate run on the MI355X only.
 """
@@ -15,7 +20,7 @@ import os
 
 import numpy as np
 
-__all__ = ['Evaluator', 'COCOEvaluator']
+__all__ = ['Evaluator', 'COCOEvaluator', 'TT100KEvaluator', 'TYPE45', 'tt100k_results']
 
 METRIC_ITEMS = ['mAP', 'mAP_50', 'mAP_75', 'mAP_s', 'mAP_m', 'mAP_l']
 MAX_DETS = (100, 300, 1000)
@@ -342,6 +347,383 @@ class COCOEvaluator(Evaluator):
 
     def _clear(self):
         self._host_rows = self._resident_calls = self._upper = 0
+        if self._dev is not None:
+            self._dev.state.zero_()
+            self._dev.img_mask.zero_()
+
+    def get_eval_display_str(self):
+        return self._eval_display_str
+
+
+# ====================================================================== TT100K: the dataset's official accuracy / recall
+# the 45 categories the reference evaluates (official_eval.type45), in its order
+TYPE45 = ['i2', 'i4', 'i5', 'il100', 'il60', 'il80', 'io', 'ip', 'p10', 'p11', 'p12', 'p19', 'p23', 'p26', 'p27', 'p3', 'p5', 'p6',
+          'pg', 'ph4', 'ph4.5', 'ph5', 'pl100', 'pl120', 'pl20', 'pl30', 'pl40', 'pl5', 'pl50', 'pl60', 'pl70', 'pl80', 'pm20',
+          'pm30', 'pm55', 'pn', 'pne', 'po', 'pr40', 'w13', 'w32', 'w55', 'w57', 'w59', 'wo']
+DET_EXCLUDED, DET_RIGHT, DET_WRONG, DET_UNMATCHED = 0, 1, 2, 3      # LFD_TT100K_DET_*
+GT_EXCLUDED, GT_MISSED, GT_MATCHED = 0, 1, 2                        # LFD_TT100K_GT_*
+
+
+def _names_of(label_indexes_to_category_names):
+    """dict or list (dataset.meta_info['label_indexes_to_category_names']) -> dict label -> name"""
+    m = label_indexes_to_category_names
+    if isinstance(m, dict):
+        return dict((int(k), str(v)) for k, v in m.items())
+    if isinstance(m, (list, tuple)):
+        return dict((i, str(v)) for i, v in enumerate(m))
+    raise TypeError('label index to category name must be a dict or a list!!!')
+
+
+def tt100k_results(predict_results, meta_batch, label_indexes_to_category_names):
+    """The results dictionary of TT100K_train/evaluation.py:42-57 ({'imgs': {id: {'id', 'objects': [{'bbox', 'category',
+    'score'}]}}}) from LFD.get_results rows [label, score, x, y, w, h]: score * 100, xmax = w + x, ymax = h + y.  json.dump it
+    to get the file the dataset's official tool reads."""
+    names = _names_of(label_indexes_to_category_names)
+    if len(predict_results) != len(meta_batch):
+        raise ValueError('%d prediction lists for %d meta entries' % (len(predict_results), len(meta_batch)))
+    out = dict(imgs=dict())
+    for meta, results in zip(meta_batch, predict_results):
+        image_id = str(meta['image_id'])
+        temp = dict(id=image_id, objects=list())
+        for result in results:
+            temp['objects'].append(dict(bbox={'xmin': result[2], 'ymin': result[3], 'xmax': result[4] + result[2],
+                                              'ymax': result[5] + result[3]},
+                                        category=names[result[0]], score=result[1] * 100))
+        out['imgs'][image_id] = temp
+    return out
+
+
+def _ratio(right, n):
+    return 1 if n == 0 else right * 1.0 / n      # the reference's expression: the int 1 when nothing was counted
+
+
+def _as_list(v):
+    return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v]
+
+
+class TT100KEvaluator(Evaluator):
+    """The TT100K protocol as config_dict['evaluator']: `update`, `update_resident`, `evaluate`, `get_eval_display_str` as
+    COCOEvaluator.  The defaults reproduce the reference's call (iou 0.5, minscore 90, sizes [0, 400), the 45 types,
+    check_type and match_same on).
+
+    annotation_path: the dataset's annotations.json; annotations: the same structure as a dict (one of the two):
+    {'imgs': {id: {'objects': [{'bbox': {'xmin', 'ymin', 'xmax', 'ymax'}, 'category': name}]}}}.
+    iou, minscore: a value or a sequence; size_ranges: a sequence of (minboxsize, maxboxsize).  One evaluate() computes every
+    combination; the results are indexed [iou, minscore, size range].  types=None: no category filter.
+    Every image passed to update / update_resident is evaluated, with or without detections."""
+
+    def __init__(self, annotation_path=None, annotations=None, label_indexes_to_category_names=None, types=TYPE45, iou=0.5,
+                 minscore=90, size_ranges=((0, 400),), check_type=True, match_same=True, device=None):
+        if (annotation_path is None) == (annotations is None):
+            raise ValueError('give exactly one of annotation_path and annotations')
+        if annotation_path is not None:
+            if not os.path.isfile(annotation_path):
+                raise FileNotFoundError('annotation file does not exist!!! (%s)' % annotation_path)
+            with open(annotation_path) as f:
+                annotations = json.load(f)
+        if not isinstance(annotations, dict) or not isinstance(annotations.get('imgs'), dict) or not annotations['imgs']:
+            raise ValueError("annotations must be a TT100K dict with a non-empty 'imgs' dict")
+        self._names = _names_of(label_indexes_to_category_names)
+        self.types = None if types is None else [str(t) for t in types]
+        self.ious, self.minscores = _as_list(iou), _as_list(minscore)
+        self.size_ranges = [tuple(r) for r in size_ranges]
+        if not self.ious or not self.minscores or not self.size_ranges or any(len(r) != 2 for r in self.size_ranges):
+            raise ValueError('iou, minscore and size_ranges need at least one entry each; a size range is (min, max)')
+        self.check_type, self.match_same = bool(check_type), bool(match_same)
+        self._device = device
+        self._eval_display_str = ''
+        self._parse(annotations)
+        self.right = self.num_detections = self.num_ground_truth = self.accuracy = self.recall = None
+        self.right_per_category = self.num_detections_per_category = self.num_ground_truth_per_category = None
+        self._dev = None
+        self._seen = set()         # image ordinals since the last evaluate()
+        self._upper = 0            # upper bound of the detections stored on the device
+        self._last = None
+        import torch
+        if torch.cuda.is_available():
+            self._state()
+
+    # ------------------------------------------------------------------ ground truth (host)
+    def _parse(self, ann):
+        self.image_ids = [str(k) for k in ann['imgs']]
+        self._img_ord = dict((k, i) for i, k in enumerate(self.image_ids))
+        if len(self._img_ord) != len(self.image_ids):
+            raise ValueError('two image ids of the annotations are the same string')
+        cats, box, cat, start = dict(), [], [], [0]
+        idx = lambda name: cats.setdefault(str(name), len(cats))   # noqa: E731
+        for name in self._names.values():
+            idx(name)
+        for t in self.types or ():
+            idx(t)
+        for k in ann['imgs']:
+            for obj in ann['imgs'][k].get('objects', ()):
+                b = obj['bbox']
+                box.append([b['xmin'], b['ymin'], b['xmax'], b['ymax']])
+                cat.append(idx(obj['category']))
+            start.append(len(cat))
+        self.category_names = list(cats)
+        self._cat_idx = cats
+        self.gt_box = np.array(box, np.float64).reshape(len(cat), 4)
+        self.gt_cat = np.array(cat, np.int32).reshape(len(cat))
+        self.gt_start = np.array(start, np.int32)
+        K = len(cats)
+        self._in_types = np.ones(K, np.int32)
+        if self.types is not None:
+            self._in_types[:] = 0
+            self._in_types[[cats[t] for t in self.types]] = 1
+        lmax = max([l for l in self._names] + [0])
+        self._label_map = np.full(lmax + 1, -1, np.int32)
+        for lab, name in self._names.items():
+            if lab >= 0:
+                self._label_map[lab] = cats[name]
+
+    # ------------------------------------------------------------------ device state
+    def _state(self):
+        if self._dev is not None:
+            return self._dev
+        import torch
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError('TT100KEvaluator: the evaluation kernels run on the MI355X only; there is no CPU implementation')
+        dev = torch.device(self._device) if self._device is not None else torch.device('cuda', torch.cuda.current_device())
+        d = type('EvalDeviceState', (), {})()
+        d.torch, d.lib, d.dev = torch, _lib, dev
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+        G = len(self.gt_cat)
+        d.gt_box = up(self.gt_box if G else np.zeros((1, 4)))
+        d.gt_cat = up(self.gt_cat if G else np.zeros(1, np.int32))
+        d.gt_start = up(self.gt_start)
+        d.cat_in_types = up(self._in_types)
+        d.ious = up(np.array([float(v) for v in self.ious], np.float64))
+        d.minscores = up(np.array([float(v) for v in self.minscores], np.float64))
+        d.size_ranges = up(np.array([[float(lo), float(hi)] for lo, hi in self.size_ranges], np.float64))
+        d.label_map = up(self._label_map)
+        d.state = torch.zeros(4, dtype=torch.int32, device=dev)
+        d.img_mask = torch.zeros(len(self.image_ids), dtype=torch.int32, device=dev)
+        d.cap = 0
+        d.det_box = d.det_score = d.det_img = d.det_cat = None
+        self._dev = d
+        self._reserve(1 << 16)
+        return d
+
+    def _reserve(self, need):
+        """grow the detection store to hold `need` entries (device-to-device copies on the current stream, no sync)"""
+        d = self._dev
+        if need <= d.cap:
+            return
+        torch = d.torch
+        cap = max(int(need), 2 * d.cap)
+        new = [torch.empty((cap, 4), dtype=torch.float64, device=d.dev), torch.empty(cap, dtype=torch.float64, device=d.dev),
+               torch.empty(cap, dtype=torch.int32, device=d.dev), torch.empty(cap, dtype=torch.int32, device=d.dev)]
+        if d.cap:
+            for n, o in zip(new, (d.det_box, d.det_score, d.det_img, d.det_cat)):
+                n[:d.cap].copy_(o)
+        d.det_box, d.det_score, d.det_img, d.det_cat = new
+        d.cap = cap
+
+    def _desc(self):
+        d = self._dev
+        desc = d.lib.TT100KEvalDesc()
+        desc.num_images, desc.num_categories = len(self.image_ids), len(self.category_names)
+        desc.num_gt, desc.det_capacity = len(self.gt_cat), d.cap
+        desc.num_ious, desc.num_minscores, desc.num_size_ranges = len(self.ious), len(self.minscores), len(self.size_ranges)
+        desc.check_type, desc.match_same = int(self.check_type), int(self.match_same)
+        return desc
+
+    def _bufs(self, **extra):
+        d = self._dev
+        b = d.lib.TT100KEvalBufs()
+        for k in ('det_box', 'det_score', 'det_img', 'det_cat', 'state', 'img_mask', 'gt_box', 'gt_cat', 'gt_start', 'cat_in_types',
+                  'ious', 'minscores', 'size_ranges'):
+            setattr(b, k, getattr(d, k).data_ptr())
+        for k, t in extra.items():
+            setattr(b, k, t.data_ptr() if t is not None else None)
+        return b
+
+    def _ordinals(self, meta_batch):
+        """image ordinals of a batch; an unknown id, or one that already arrived since the last evaluate(), is a ValueError"""
+        ords = []
+        for m in meta_batch:
+            key = str(m['image_id'])
+            if key not in self._img_ord:
+                raise ValueError('image id %r is not in the annotations' % key)
+            o = self._img_ord[key]
+            if o in self._seen or o in ords:
+                raise ValueError('image id %r arrived twice before evaluate()' % key)
+            ords.append(o)
+        return ords
+
+    # ------------------------------------------------------------------ accumulation
+    def update(self, results):
+        """results: tuple(predict_results, meta_batch); predict_results[i] is a list of [label, score, x, y, w, h] rows for
+        image meta_batch[i]['image_id'] (what LFD.get_results / predict_for_single_image return)."""
+        if not (isinstance(results, tuple) and len(results) == 2):
+            raise TypeError('update info should contain two parts: predict bboxes and meta info.')
+        predict_results, meta_batch = results
+        if len(predict_results) != len(meta_batch):
+            raise ValueError('%d prediction lists for %d meta entries' % (len(predict_results), len(meta_batch)))
+        ords = self._ordinals(meta_batch)
+        rows = []
+        for o, boxes in zip(ords, predict_results):
+            for r in boxes:
+                if r[0] not in self._names:
+                    raise ValueError('label %r has no category name' % (r[0],))
+                rows.append((o, self._cat_idx[self._names[r[0]]], r[1], r[2], r[3], r[4], r[5]))
+        if not ords:
+            return
+        d = self._state()
+        torch = d.torch
+        self._upper += len(rows)
+        self._reserve(self._upper)
+        with torch.cuda.device(d.dev):
+            rows_t = torch.from_numpy(np.array(rows, np.float64).reshape(len(rows), 7)).to(d.dev) if rows else None
+            mark_t = torch.tensor(ords, dtype=torch.int32).to(d.dev)
+            desc, bufs = self._desc(), self._bufs()
+            d.lib.check(d.lib.lib().lfd_eval_tt100k_append_rows_f64(C.byref(desc), C.byref(bufs), d.lib.ptr(rows_t), len(rows),
+                                                                    d.lib.ptr(mark_t), len(ords), d.lib.stream_ptr()),
+                        'lfd_eval_tt100k_append_rows_f64')
+        self._seen.update(ords)
+
+    def update_resident(self, outputs, meta_batch):
+        """Appends the kept boxes of an ops.DetectOutputs (LFD.detect / detect_resident) on the device: no .item(),
+        .tolist(), .cpu() or synchronisation; the number of kept boxes is read from outputs.counts by the kernel, which also
+        does the reference's arithmetic (fp32 w = x2 - x1 + 1, float64 xmax = w + x1, score * 100).  The only host -> device
+        traffic is the batch's image ordinals (pinned, asynchronous)."""
+        n, cap = int(outputs.dets.size(0)), int(outputs.dets.size(1))
+        if len(meta_batch) != n:
+            raise ValueError('%d meta entries for a batch of %d' % (len(meta_batch), n))
+        ords = self._ordinals(meta_batch)
+        d = self._state()
+        torch = d.torch
+        if outputs.dets.device != d.dev:
+            raise RuntimeError('update_resident: the outputs live on %s, the evaluator on %s' % (outputs.dets.device, d.dev))
+        self._upper += n * cap
+        self._reserve(self._upper)
+        with torch.cuda.device(d.dev):
+            host = torch.empty(n, dtype=torch.int32, pin_memory=True)
+            host.numpy()[:] = ords
+            ord_t = host.to(d.dev, non_blocking=True)
+            desc, bufs = self._desc(), self._bufs()
+            d.lib.check(d.lib.lib().lfd_eval_tt100k_append_dets_f32(C.byref(desc), C.byref(bufs), d.lib.ptr(outputs.dets),
+                                                                    d.lib.ptr(outputs.labels), d.lib.ptr(outputs.counts), n, cap,
+                                                                    d.lib.ptr(d.label_map), int(d.label_map.numel()),
+                                                                    d.lib.ptr(ord_t), d.lib.stream_ptr()),
+                        'lfd_eval_tt100k_append_dets_f32')
+        self._seen.update(ords)
+
+    # ------------------------------------------------------------------ evaluation
+    def _run(self, keep_matches=False):
+        """enqueue the grouping, the matching and the counting; returns the device tensors (no synchronisation)"""
+        d = self._state()
+        torch, lib = d.torch, d.lib
+        T, M, S, K = len(self.ious), len(self.minscores), len(self.size_ranges), len(self.category_names)
+        G, I = max(len(self.gt_cat), 1), len(self.image_ids)
+        with torch.cuda.device(d.dev):
+            i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=d.dev)   # noqa: E731
+            u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=d.dev)   # noqa: E731
+            out = dict(det_start=i32(I + 1), det_index=i32(d.cap), det_match=i32(T * M, d.cap), gt_match=i32(T * M, G),
+                       totals=torch.empty((T, M, S, 3), dtype=torch.int64, device=d.dev),
+                       per_category=torch.empty((T, M, S, K, 3), dtype=torch.int64, device=d.dev) if self.match_same else None,
+                       det_code=u8(T, M, S, d.cap) if keep_matches else None, gt_code=u8(T, M, S, G) if keep_matches else None)
+            desc, bufs = self._desc(), self._bufs(**out)
+            wb = lib.lib().lfd_eval_tt100k_workspace_bytes(C.byref(desc))
+            if wb == 0:
+                raise RuntimeError('TT100KEvaluator: this problem size is not supported by the evaluation kernels')
+            ws = torch.empty(wb, dtype=torch.uint8, device=d.dev)
+            lib.check(lib.lib().lfd_eval_tt100k_match(C.byref(desc), C.byref(bufs), lib.ptr(ws), wb, lib.stream_ptr()),
+                      'lfd_eval_tt100k_match')
+        out['ws'] = ws
+        return out
+
+    def evaluate(self, keep_matches=False):
+        """Runs the kernels on what update / update_resident accumulated and fills `right`, `num_detections`,
+        `num_ground_truth` (int64 [T, M, S]), `accuracy`, `recall` (float64, from the integers with the reference's
+        expression) and, with match_same, `right_per_category`, `num_detections_per_category`,
+        `num_ground_truth_per_category` ([T, M, S, K], K over `category_names`); builds the display string and clears the
+        accumulated detections.  keep_matches=True keeps the per-object outcomes for `match_table()`."""
+        T, M, S, K = len(self.ious), len(self.minscores), len(self.size_ranges), len(self.category_names)
+        self._last = None
+        per = None
+        if not self._seen:
+            tot = np.zeros((T, M, S, 3), np.int64)
+            if self.match_same:
+                per = np.zeros((T, M, S, K, 3), np.int64)
+            self._clear()
+        else:
+            d = self._state()
+            torch = d.torch
+            out = self._run(keep_matches)
+            with torch.cuda.device(d.dev):
+                parts = [out['totals'].reshape(-1), d.state.long()]
+                if self.match_same:
+                    parts.append(out['per_category'].reshape(-1))
+                flat = torch.cat(parts).cpu().numpy()                    # the one D2H
+            nt = T * M * S * 3
+            tot = flat[:nt].reshape(T, M, S, 3)
+            state = flat[nt:nt + 4]
+            if self.match_same:
+                per = flat[nt + 4:].reshape(T, M, S, K, 3)
+            err = int(state[1])
+            if keep_matches and not err:
+                n = int(state[2])
+                self._last = dict(det_start=out['det_start'].cpu().numpy(), det_index=out['det_index'][:n].cpu().numpy(),
+                                  det_gt=out['det_match'][:, :n].cpu().numpy().reshape(T, M, n),
+                                  det_code=out['det_code'][..., :n].cpu().numpy(),
+                                  gt_code=out['gt_code'][..., :len(self.gt_cat)].cpu().numpy())
+            self._clear()
+            if err:
+                msgs = [m for bit, m in ((ERR_CAPACITY, 'the detection store overflowed'), (ERR_IMAGE, 'an image ordinal was out of range'),
+                                         (ERR_LABEL, 'a detection carried a label that label_indexes_to_category_names does not name'))
+                        if err & bit]
+                raise RuntimeError('TT100KEvaluator: ' + '; '.join(msgs) + ' (status bits %d); the accumulated detections were dropped' % err)
+        self.right, self.num_detections, self.num_ground_truth = tot[..., 0].copy(), tot[..., 1].copy(), tot[..., 2].copy()
+        ratios = lambda n: np.array([float(_ratio(int(r), int(v))) for r, v in zip(self.right.ravel(), n.ravel())],   # noqa: E731
+                                    np.float64).reshape(T, M, S)
+        self.accuracy, self.recall = ratios(self.num_detections), ratios(self.num_ground_truth)
+        if per is not None:
+            self.right_per_category, self.num_detections_per_category, self.num_ground_truth_per_category = (
+                per[..., 0].copy(), per[..., 1].copy(), per[..., 2].copy())
+        else:
+            self.right_per_category = self.num_detections_per_category = self.num_ground_truth_per_category = None
+        self._eval_display_str = '\n'.join(self.report(t, m, s) for t in range(T) for m in range(M) for s in range(S))
+
+    def report(self, t=0, m=0, s=0):
+        """the reference's report line for one combination, character for character (a `types` list with a single name
+        prints that name, where the reference raises)"""
+        if self.right is None:
+            raise RuntimeError('report: call evaluate() first')
+        if self.types is None:
+            styps = 'all'
+        else:
+            distinct = list(dict.fromkeys(self.types))
+            if len(distinct) == 1:
+                styps = distinct[0]
+            elif not self.check_type or len(distinct) == 0:
+                styps = 'none'
+            else:
+                styps = '[%s, ...total %s...]' % (distinct[0], len(distinct))
+        right = int(self.right[t, m, s])
+        return 'iou:%s, size:[%s,%s), types:%s, accuracy:%s, recall:%s' % (
+            self.ious[t], self.size_ranges[s][0], self.size_ranges[s][1], styps,
+            _ratio(right, int(self.num_detections[t, m, s])), _ratio(right, int(self.num_ground_truth[t, m, s])))
+
+    def match_table(self, t=0, m=0, s=0):
+        """After evaluate(keep_matches=True), for one combination: dict of numpy arrays.  Per detection that was stored, in
+        image order and insertion order inside an image: `image` (ordinal in `image_ids`), `index` (insertion index into the
+        accumulation), `det_code` (DET_EXCLUDED / DET_RIGHT / DET_WRONG / DET_UNMATCHED) and `det_gt` (index of the matched
+        ground truth inside its image's annotation list, -1 unmatched, -2 taken out before the matching); `det_start`
+        [images + 1]; per ground truth in annotation order `gt_code` (GT_EXCLUDED / GT_MISSED / GT_MATCHED) with `gt_start`.
+        The reference's `right` are the DET_RIGHT detections, `wrong` DET_WRONG and DET_UNMATCHED, `miss` GT_MISSED."""
+        if self._last is None:
+            raise RuntimeError('match_table: call evaluate(keep_matches=True) first')
+        L = self._last
+        start = L['det_start']
+        return dict(image=np.repeat(np.arange(len(start) - 1), np.diff(start)), index=L['det_index'], det_start=start,
+                    det_code=L['det_code'][t, m, s], det_gt=L['det_gt'][t, m], gt_code=L['gt_code'][t, m, s], gt_start=self.gt_start)
+
+    def _clear(self):
+        self._seen = set()
+        self._upper = 0
         if self._dev is not None:
             self._dev.state.zero_()
             self._dev.img_mask.zero_()

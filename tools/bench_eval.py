@@ -8,6 +8,12 @@
   (c) the numpy restatement of the definition (tests/golden/coco_eval_oracle.py) on a 500-image slice: the only host figure
       available.  It is plain Python loops, NOT pycocotools; pycocotools itself was not measured.
 
+--protocol tt100k times the TT100K protocol instead (lfd_amd.evaluation.TT100KEvaluator, csrc/evaluate_tt100k.hip) on a set of
+TT100K's test split's shape -- 3000 images, 45 classes, a few signs and --dets detections per image: update_resident per batch
+of 8, then evaluate() (device events around the enqueued kernels, and the host clock around the whole call, which ends in
+the one device-to-host copy) for the reference's default call and for a 3-band x 10-minscore sweep; beside it the numpy
+restatement tests/golden/tt100k_eval_oracle.py on a slice, on the host CPU.
+
 Prints one JSON line.  Needs the MI355X: there is no CPU path."""
 import argparse
 import json
@@ -58,15 +64,92 @@ def synthetic(images, cats, dets, seed):
     return coco, det_all, lab_all
 
 
+def main_tt100k(args):
+    import torch
+    from lfd_amd import evaluation, ops
+    import tt100k_eval_oracle as oracle
+    assert torch.cuda.is_available(), 'bench_eval needs the MI355X'
+    names = list(evaluation.TYPE45)[:args.categories] + ['class_%d' % i for i in range(len(evaluation.TYPE45), args.categories)]
+    coco, det_all, lab_all = synthetic(args.images, args.categories, args.dets, args.seed)
+    imgs = dict((str(i + 1), dict(objects=[])) for i in range(args.images))
+    for a in coco['annotations']:
+        x, y, w, h = a['bbox']
+        imgs[str(a['image_id'])]['objects'].append(dict(bbox=dict(xmin=x, ymin=y, xmax=x + w, ymax=y + h), category=names[a['category_id'] - 1]))
+    ann = dict(imgs=imgs)
+    B = 8
+    outs = []
+    for i in range(0, args.images, B):
+        o = ops.DetectOutputs()
+        o.dets = torch.from_numpy(det_all[i:i + B]).cuda()
+        o.labels = torch.from_numpy(lab_all[i:i + B]).cuda()
+        o.counts = torch.zeros((o.dets.size(0), 4), dtype=torch.int32, device='cuda')
+        o.counts[:, 1] = args.dets
+        o.cand = o.point = o.ws = None
+        outs.append((o, [dict(image_id=j + 1) for j in range(i, min(i + B, args.images))]))
+    sweep = dict(minscore=[5 + 10 * k for k in range(10)], size_ranges=((0, 32), (32, 96), (96, 400)))
+    n_or = min(args.oracle_images, args.images)
+    gt_by_img = [[] for _ in range(n_or)]
+    for a in coco['annotations']:
+        if a['image_id'] <= n_or:
+            x, y, w, h = a['bbox']
+            gt_by_img[a['image_id'] - 1].append(([x, y, x + w, y + h], a['category_id'] - 1))
+    or_images = []
+    for i in range(n_or):
+        box, score = oracle.detections_from_f32(det_all[i])
+        or_images.append((np.array([g[0] for g in gt_by_img[i]], np.float64).reshape(-1, 4), np.array([g[1] for g in gt_by_img[i]], np.int64),
+                          box, lab_all[i], score))
+    res = dict(protocol='tt100k', images=args.images, categories=args.categories, dets_per_image=args.dets,
+               ground_truth=len(coco['annotations']), runs=args.runs, numpy_oracle_images=n_or)
+    for tag, kw in (('default', dict()), ('sweep', sweep)):
+        ev = evaluation.TT100KEvaluator(annotations=ann, label_indexes_to_category_names=names, types=names, **kw)
+
+        def fill():
+            for o, meta in outs:
+                ev.update_resident(o, meta)
+        fill()
+        ev.evaluate()                         # warm-up of every kernel, sizes the store
+        torch.cuda.synchronize()
+        app, dev, wall = [], [], []
+        for _ in range(args.runs):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e[0].record()
+            fill()
+            e[1].record()
+            e[2].record()
+            ev._run()
+            e[3].record()
+            torch.cuda.synchronize()
+            app.append(e[0].elapsed_time(e[1]) / len(outs))
+            dev.append(e[2].elapsed_time(e[3]))
+            t0 = time.perf_counter()
+            ev.evaluate()
+            wall.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        ref = oracle.evaluate(or_images, [float(v) for v in ev.ious], [float(v) for v in ev.minscores],
+                              [[float(a), float(b)] for a, b in ev.size_ranges], None, True, True, num_categories=args.categories)
+        oracle_s = time.perf_counter() - t0
+        res[tag] = dict(combinations=int(ev.right.size), update_resident_ms_per_batch8=round(float(np.median(app)), 4),
+                        evaluate_device_ms=round(float(np.median(dev)), 3), evaluate_call_ms=round(float(np.median(wall)), 3),
+                        numpy_oracle_s=round(oracle_s, 2), accuracy=float(ev.accuracy.ravel()[0]), recall=float(ev.recall.ravel()[0]),
+                        oracle_slice_recall=float(ref['recall'].ravel()[0]))
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--images', type=int, default=5000)
-    ap.add_argument('--categories', type=int, default=80)
-    ap.add_argument('--dets', type=int, default=100)
+    ap.add_argument('--protocol', choices=['coco', 'tt100k'], default='coco')
+    ap.add_argument('--images', type=int, default=None, help='default: 5000 (coco), 3000 (tt100k)')
+    ap.add_argument('--categories', type=int, default=None, help='default: 80 (coco), 45 (tt100k)')
+    ap.add_argument('--dets', type=int, default=None, help='detections per image; default: 100 (coco), 20 (tt100k)')
     ap.add_argument('--runs', type=int, default=20)
     ap.add_argument('--oracle-images', type=int, default=500)
     ap.add_argument('--seed', type=int, default=0)
     args = ap.parse_args()
+    for k, coco_default, tt_default in (('images', 5000, 3000), ('categories', 80, 45), ('dets', 100, 20)):
+        if getattr(args, k) is None:
+            setattr(args, k, tt_default if args.protocol == 'tt100k' else coco_default)
+    if args.protocol == 'tt100k':
+        return main_tt100k(args)
     import torch
     from lfd_amd import evaluation, ops
     from lfd_amd.model.lfd import LFD
