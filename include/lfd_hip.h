@@ -1278,6 +1278,65 @@ LFD_API size_t lfd_eval_tt100k_workspace_bytes(const lfd_eval_tt100k_desc_t* des
 LFD_API int lfd_eval_tt100k_match(const lfd_eval_tt100k_desc_t* desc, const lfd_eval_tt100k_bufs_t* bufs, void* workspace,
                                   size_t workspace_bytes, lfd_stream_t stream);
 
+/* ---- detection evaluation: the WIDERFACE protocol, easy / medium / hard AP (csrc/evaluate_widerface.hip) --------------------
+ * The device side of lfd_amd/evaluation.py WIDERFACEEvaluator; the definition is DESIGN.md 9c, a restatement of the
+ * dataset's eval_tools from knowledge of them that is NOT verified against those tools.  Per image the detections are ranked
+ * by score (stable), every detection takes the first ground truth of maximal IoU (+1 convention), and per difficulty a
+ * sequential walk in rank order gives the running proposal and recall counts, which are sampled at num_thresholds thresholds
+ * of the normalised score and summed over the images into `curve`.  All arithmetic is float64, evaluated as the definition
+ * writes it; the results are integers.
+ *
+ * The detection store and `state` work as in lfd_eval_bufs_t (same LFD_EVAL_ERR_* bits; there is one class and no
+ * img_mask); boxes are {x, y, w, h}.  A stored row with det_img = -1 (a label the caller filters out) takes part in nothing.
+ * state[2]: detections grouped by the last lfd_eval_wf_match.  Difficulties are indexed 0 easy, 1 medium, 2 hard. */
+typedef struct lfd_eval_wf_desc {
+  int32_t num_images, num_gt, det_capacity;
+  int32_t num_thresholds;      /* T <= 1024 */
+  int32_t as_written;          /* lfd_eval_wf_append_dets_f32 quantises as the reference's text files do and adds their dummy row */
+  int32_t label_index;         /* lfd_eval_wf_append_dets_f32 keeps this label only; < 0: every label */
+  double iou_thresh;
+} lfd_eval_wf_desc_t;
+typedef struct lfd_eval_wf_bufs {
+  /* the detection store, in insertion order */
+  double* det_box;             /* [det_capacity, 4] {x, y, w, h} */
+  double* det_score;           /* [det_capacity] */
+  int32_t* det_img;            /* [det_capacity] image ordinal, -1: dropped */
+  int32_t* state;              /* [4] */
+  /* ground truth, sorted by image (annotation order inside an image) */
+  const double* gt_box;        /* [num_gt, 4] {x, y, w, h} */
+  const int32_t* gt_start;     /* [num_images + 1] */
+  const uint8_t* gt_kept;      /* [num_gt] bit d: the box is in difficulty d's keep list */
+  const int32_t* keep_len;     /* [num_images, 3] length of each keep list */
+  const double* thr;           /* [T] score thresholds, descending */
+  /* results of lfd_eval_wf_match; "grouped" positions are image-major, rank order inside an image */
+  int32_t* det_start;          /* [num_images + 1] first grouped position of each image */
+  int32_t* det_index;          /* [det_capacity] grouped position -> index into the store */
+  int32_t* det_gt;             /* [det_capacity] first ground truth of maximal IoU (index inside its image) */
+  uint8_t* det_over;           /* [det_capacity] 1: that IoU >= iou_thresh */
+  int32_t* det_prop;           /* [3, det_capacity] running proposal count inside the image, per difficulty */
+  int32_t* det_rec;            /* [3, det_capacity] running recalled-face count */
+  uint8_t* det_flags;          /* [det_capacity] bit 0: det_over, bit 1 + d: proposal of difficulty d; or NULL */
+  uint64_t* curve;             /* [3, T, 2] {proposals, recalled faces} at each threshold, summed over the images */
+  uint64_t* faces;             /* [3] keep-list lengths summed over every annotated image */
+  double* minmax;              /* [2] minimum and maximum stored score, or NULL */
+} lfd_eval_wf_bufs_t;
+/* grouped positions of images without ground truth are not ranked: their det_index .. det_flags entries are not written */
+
+/* Append the kept boxes of a detection step (as lfd_eval_append_dets_f32 reads them): w = x2 - x1 + 1 and h in fp32, then
+ * widened.  With desc->as_written every batch entry first gets the row {0, 0, 0, 0, 0.001} and every box is stored as
+ * {floor x, floor y, ceil w, ceil h} with the score min(s, 1) rounded to three decimals (half to even, decided exactly). */
+LFD_API int lfd_eval_wf_append_dets_f32(const lfd_eval_wf_desc_t* desc, const lfd_eval_wf_bufs_t* bufs, const float* dets,
+                                        const int32_t* labels, const int32_t* counts, int32_t n, int32_t cap,
+                                        const int32_t* img_ord, lfd_stream_t stream);
+/* Append m rows {image ordinal, score, x, y, w, h} (float64, device) as they are. */
+LFD_API int lfd_eval_wf_append_rows_f64(const lfd_eval_wf_desc_t* desc, const lfd_eval_wf_bufs_t* bufs, const double* rows,
+                                        int64_t m, lfd_stream_t stream);
+/* Score range, grouping by image, and one persistent grid over the images: rank, IoU argmax over 64-wide ground-truth
+ * tiles, the walk per difficulty, the threshold sweep (integer atomics: the result does not depend on the schedule). */
+LFD_API size_t lfd_eval_wf_workspace_bytes(const lfd_eval_wf_desc_t* desc);
+LFD_API int lfd_eval_wf_match(const lfd_eval_wf_desc_t* desc, const lfd_eval_wf_bufs_t* bufs, void* workspace,
+                              size_t workspace_bytes, lfd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,19 @@ class TT100KEvalBufs(C.Structure):
                                           'det_match', 'gt_match', 'totals', 'per_category', 'det_code', 'gt_code')]
 
 
+class WFEvalDesc(C.Structure):
+    """lfd_eval_wf_desc_t"""
+    _fields_ = [(k, C.c_int32) for k in ('num_images', 'num_gt', 'det_capacity', 'num_thresholds', 'as_written', 'label_index')] + [
+        ('iou_thresh', C.c_double)]
+
+
+class WFEvalBufs(C.Structure):
+    """lfd_eval_wf_bufs_t"""
+    _fields_ = [(k, C.c_void_p) for k in ('det_box', 'det_score', 'det_img', 'state', 'gt_box', 'gt_start', 'gt_kept', 'keep_len',
+                                          'thr', 'det_start', 'det_index', 'det_gt', 'det_over', 'det_prop', 'det_rec', 'det_flags',
+                                          'curve', 'faces', 'minmax')]
+
+
 class RowsumJob(C.Structure):
     """lfd_rowsum_job_t"""
     _fields_ = [('src', C.c_void_p), ('dst', C.c_void_p), ('nrows', C.c_int32), ('row_stride', C.c_int32),
@@ -336,6 +349,10 @@ _SIGNATURES = {
     'lfd_eval_tt100k_append_rows_f64': (C.c_int, [C.POINTER(TT100KEvalDesc), C.POINTER(TT100KEvalBufs), _P, _I64, _P, _I32, _P]),
     'lfd_eval_tt100k_workspace_bytes': (_SZ, [C.POINTER(TT100KEvalDesc)]),
     'lfd_eval_tt100k_match': (C.c_int, [C.POINTER(TT100KEvalDesc), C.POINTER(TT100KEvalBufs), _P, _SZ, _P]),
+    'lfd_eval_wf_append_dets_f32': (C.c_int, [C.POINTER(WFEvalDesc), C.POINTER(WFEvalBufs), _P, _P, _P, _I32, _I32, _P, _P]),
+    'lfd_eval_wf_append_rows_f64': (C.c_int, [C.POINTER(WFEvalDesc), C.POINTER(WFEvalBufs), _P, _I64, _P]),
+    'lfd_eval_wf_workspace_bytes': (_SZ, [C.POINTER(WFEvalDesc)]),
+    'lfd_eval_wf_match': (C.c_int, [C.POINTER(WFEvalDesc), C.POINTER(WFEvalBufs), _P, _SZ, _P]),
 }
 
 

@@ -11,6 +11,13 @@ definition as plain numpy loops; the kernels are tested against it.
 definition is DESIGN.md 9b; tests/golden/ref_tt100k_eval.npz holds what the reference itself computes and the tests compare
 with it exactly.
 
+`WIDERFACEEvaluator` is the WIDERFACE models' protocol: the dataset's easy / medium / hard AP over
+csrc/evaluate_widerface.hip.  The reference only writes text files for the dataset's Matlab tools
+(WIDERFACE_train/evaluation.py SIO_evaluation); the definition, DESIGN.md 9c, restates those tools from knowledge of them and
+AGREEMENT WITH THEM IS NOT VERIFIED.  tests/golden/widerface_eval_oracle.py is the same definition as plain numpy loops.
+`write_widerface_results` / `read_widerface_results` are the reference's text files, `load_widerface_mat` the dataset's
+ground truth (needs scipy).
+
 Importing this module and constructing an evaluator need no GPU (the ground truth is parsed on the host and uploaded when a
 device is first needed); update / update_resident / a non-empty evaluate run on the MI355X only.
 """
@@ -20,7 +27,8 @@ import os
 
 import numpy as np
 
-__all__ = ['Evaluator', 'COCOEvaluator', 'TT100KEvaluator', 'TYPE45', 'tt100k_results']
+__all__ = ['Evaluator', 'COCOEvaluator', 'TT100KEvaluator', 'TYPE45', 'tt100k_results', 'WIDERFACEEvaluator',
+           'write_widerface_results', 'read_widerface_results', 'load_widerface_mat']
 
 METRIC_ITEMS = ['mAP', 'mAP_50', 'mAP_75', 'mAP_s', 'mAP_m', 'mAP_l']
 MAX_DETS = (100, 300, 1000)
@@ -727,6 +735,415 @@ class TT100KEvaluator(Evaluator):
         if self._dev is not None:
             self._dev.state.zero_()
             self._dev.img_mask.zero_()
+
+    def get_eval_display_str(self):
+        return self._eval_display_str
+
+
+# ====================================================================== WIDERFACE: easy / medium / hard AP
+DIFFICULTIES = ('easy', 'medium', 'hard')
+NUM_THRESHOLDS = 1000
+
+
+def widerface_thresholds(T=NUM_THRESHOLDS):
+    """thr[t] = 1 - (t + 1) / T in float64, computed on the host and handed to the kernels as a table"""
+    return np.array([1 - (t + 1) / T for t in range(T)], np.float64)
+
+
+def _annotation_index(annotations):
+    index = dict()
+    for i, a in enumerate(annotations):
+        if a['id'] in index:
+            raise ValueError('image id %r appears twice in the annotations' % (a['id'],))
+        index[a['id']] = i
+    return index
+
+
+def voc_ap(rec, prec):
+    """VOC's VOCap: pad, running maximum of the precision from the right, and the sum of (mrec[i + 1] - mrec[i]) * mpre[i + 1]
+    over the i where mrec changes, added in ascending order one after the other (float64)."""
+    mrec = np.concatenate([[0.0], np.asarray(rec, np.float64), [1.0]])
+    mpre = np.concatenate([[0.0], np.asarray(prec, np.float64), [0.0]])
+    for i in range(len(mpre) - 2, -1, -1):
+        mpre[i] = max(mpre[i], mpre[i + 1])
+    ap = np.float64(0.0)
+    for i in np.nonzero(mrec[1:] != mrec[:-1])[0]:
+        ap = ap + (mrec[i + 1] - mrec[i]) * mpre[i + 1]
+    return float(ap)
+
+
+def widerface_ap(curve, faces):
+    """step 6 of DESIGN.md 9c: (precision [3, T], recall [3, T], ap [3]) in float64 from the integer curve [3, T, 2] and faces
+    [3].  Where no proposal was counted the precision is 0 (the dataset's tools have NaN there; the recall count is 0 there
+    as well, so the AP does not depend on the choice)."""
+    curve, faces = np.asarray(curve, np.int64), np.asarray(faces, np.int64)
+    prop, rec = curve[..., 0].astype(np.float64), curve[..., 1].astype(np.float64)
+    precision = np.zeros_like(rec)
+    np.divide(rec, prop, out=precision, where=prop != 0)
+    recall = np.zeros_like(rec)
+    den = np.broadcast_to(faces.astype(np.float64)[:, None], rec.shape)
+    np.divide(rec, den, out=recall, where=den != 0)
+    ap = np.array([voc_ap(recall[d], precision[d]) for d in range(curve.shape[0])], np.float64)
+    return precision, recall, ap
+
+
+def _quantise_as_written(r):
+    """SIO_evaluation line 41 on one row [label, score, x, y, w, h] -> (score, x, y, w, h) as the text file keeps them"""
+    import math
+    return (float('%.03f' % min(r[1], 1)), float(math.floor(r[2])), float(math.floor(r[3])), float(math.ceil(r[4])),
+            float(math.ceil(r[5])))
+
+
+def write_widerface_results(predict_results, meta_batch, annotations, results_save_root):
+    """The text files that the reference's WIDERFACE_train/evaluation.py SIO_evaluation leaves for the dataset's Matlab
+    tools: <results_save_root>/<event>/<stem>.txt holding the stem, the number of rows + 1, the dummy row '0 0 0 0 0.001' and
+    one 'x y w h score' row per detection (floor x, floor y, ceil w, ceil h as integers, min(score, 1) with three decimals).
+    predict_results[i]: rows [label, score, x, y, w, h] of image meta_batch[i]['image_id']; event and stem come from
+    `annotations`."""
+    if len(predict_results) != len(meta_batch):
+        raise ValueError('%d prediction lists for %d meta entries' % (len(predict_results), len(meta_batch)))
+    index = _annotation_index(annotations)
+    for meta, rows in zip(meta_batch, predict_results):
+        if meta['image_id'] not in index:
+            raise ValueError('image id %r is not in the annotations' % (meta['image_id'],))
+        a = annotations[index[meta['image_id']]]
+        lines = [a['stem'], '%d' % (len(rows) + 1), '0 0 0 0 0.001']
+        for r in rows:
+            score, x, y, w, h = _quantise_as_written(r)
+            lines.append('%d %d %d %d %.3f' % (x, y, w, h, score))
+        event_dir = os.path.join(results_save_root, a['event'])
+        os.makedirs(event_dir, exist_ok=True)
+        with open(os.path.join(event_dir, a['stem'] + '.txt'), 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+def read_widerface_results(root, annotations):
+    """Reads a directory that write_widerface_results (or the reference) wrote: -> (predict_results, meta_batch) for
+    WIDERFACEEvaluator.update, rows [0, score, x, y, w, h] with the dummy row included, one entry per annotated image that
+    has a file.  Fed to an evaluator with as_written=False they give what as_written=True gives on the original rows."""
+    predict_results, meta_batch = [], []
+    for a in annotations:
+        path = os.path.join(root, a['event'], a['stem'] + '.txt')
+        if not os.path.isfile(path):
+            continue
+        with open(path) as f:
+            lines = [l for l in f.read().splitlines() if l.strip()]
+        n = int(lines[1])
+        rows = []
+        for l in lines[2:2 + n]:
+            v = l.split()
+            rows.append([0, float(v[4]), float(v[0]), float(v[1]), float(v[2]), float(v[3])])
+        if len(rows) != n:
+            raise ValueError('%s announces %d rows and holds %d' % (path, n, len(rows)))
+        predict_results.append(rows)
+        meta_batch.append(dict(image_id=a['id']))
+    return predict_results, meta_batch
+
+
+def load_widerface_mat(gt_dir):
+    """The dataset's ground truth (wider_face_val.mat and wider_{easy,medium,hard}_val.mat in gt_dir) as the annotation list
+    of WIDERFACEEvaluator; an image's id is its file stem.  The keep lists of the .mat files are 1-based and become 0-based
+    here.  Needs scipy (ImportError without it); nothing else in the package does."""
+    try:
+        from scipy.io import loadmat
+    except ImportError:
+        raise ImportError('load_widerface_mat needs scipy to read the .mat files')
+    gt = loadmat(os.path.join(gt_dir, 'wider_face_val.mat'))
+    keep = dict((d, loadmat(os.path.join(gt_dir, 'wider_%s_val.mat' % d))['gt_list']) for d in DIFFICULTIES)
+    annotations = []
+    for e in range(len(gt['event_list'])):
+        event = str(np.asarray(gt['event_list'][e][0]).ravel()[0])
+        files = gt['file_list'][e][0]
+        for i in range(len(files)):
+            stem = str(np.asarray(files[i][0]).ravel()[0])
+            boxes = np.asarray(gt['face_bbx_list'][e][0][i][0], np.float64).reshape(-1, 4)
+            lists = dict((d, (np.asarray(keep[d][e][0][i][0], np.int64).reshape(-1) - 1).tolist()) for d in DIFFICULTIES)
+            annotations.append(dict(id=stem, event=event, stem=stem, boxes=boxes, keep=lists))
+    return annotations
+
+
+class WIDERFACEEvaluator(Evaluator):
+    """The WIDERFACE protocol as config_dict['evaluator']: `update`, `update_resident`, `evaluate`, `get_eval_display_str` as
+    the other two evaluators; evaluate() returns {'easy': ap, 'medium': ap, 'hard': ap}.  The definition is DESIGN.md 9c: a
+    restatement of the dataset's eval_tools (wider_eval.m, evaluation.m, read_pred.m, norm_score.m, boxoverlap.m) and VOC's
+    VOCap from knowledge of them and of the widely used Python port.  AGREEMENT WITH THOSE TOOLS IS NOT VERIFIED.
+
+    annotations: an ordered list of images, each a dict with 'id' (what meta['image_id'] carries), 'event' and 'stem' (used
+    by write_widerface_results only), 'boxes' ([G, 4] x, y, w, h) and 'keep' ({'easy' | 'medium' | 'hard': 0-based indices
+    into boxes}); load_widerface_mat builds it from the dataset's .mat files.
+    as_written=True evaluates what the reference's text files hold instead of the rows themselves: floor x, floor y, ceil w,
+    ceil h, min(score, 1) to three decimals, and the dummy row 0 0 0 0 0.001 first in every image passed to update /
+    update_resident.  label_index: detections with another label are dropped.
+    faces[d] counts the keep lists of EVERY annotated image, passed to update or not, with or without detections (unlike
+    COCOEvaluator's default, where an image without a detection does not count)."""
+
+    def __init__(self, annotations=None, iou_thresh=0.5, as_written=False, label_index=None, device=None):
+        if not isinstance(annotations, (list, tuple)) or not annotations:
+            raise ValueError('annotations must be a non-empty list of images (id, event, stem, boxes, keep)')
+        self.iou_thresh = float(iou_thresh)
+        self.as_written = bool(as_written)
+        self.label_index = None if label_index is None else int(label_index)
+        if self.label_index is not None and self.label_index < 0:
+            raise ValueError('label_index must not be negative')
+        self._device = device
+        self._eval_display_str = ''
+        self.thr = widerface_thresholds()
+        self._parse(annotations)
+        self.ap = self.curve = self.faces = self.precision = self.recall = None
+        self._dev = None
+        self._seen = set()         # image ordinals since the last evaluate()
+        self._upper = 0            # upper bound of the detections stored on the device
+        self._last = None
+        import torch
+        if torch.cuda.is_available():
+            self._state()
+
+    # ------------------------------------------------------------------ ground truth (host)
+    def _parse(self, annotations):
+        self.image_ids = [a['id'] for a in annotations]
+        self._img_ord = _annotation_index(annotations)
+        box, kept, start, keep_len = [], [], [0], []
+        for a in annotations:
+            b = np.asarray(a['boxes'], np.float64).reshape(-1, 4)
+            bits = np.zeros(len(b), np.uint8)
+            lens = []
+            for d, name in enumerate(DIFFICULTIES):
+                idx = np.asarray(a['keep'][name], np.int64).reshape(-1)
+                if len(idx) and (idx.min() < 0 or idx.max() >= len(b)):
+                    raise ValueError('image %r: a %s keep index is outside its %d boxes' % (a['id'], name, len(b)))
+                bits[idx] |= np.uint8(1 << d)
+                lens.append(len(idx))
+            box.append(b)
+            kept.append(bits)
+            keep_len.append(lens)
+            start.append(start[-1] + len(b))
+        self.gt_box = np.concatenate(box).reshape(-1, 4)
+        self.gt_kept = np.concatenate(kept).astype(np.uint8)
+        self.gt_start = np.array(start, np.int32)
+        self.keep_len = np.array(keep_len, np.int32).reshape(len(annotations), 3)
+
+    # ------------------------------------------------------------------ device state
+    def _state(self):
+        if self._dev is not None:
+            return self._dev
+        import torch
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError('WIDERFACEEvaluator: the evaluation kernels run on the MI355X only; there is no CPU implementation')
+        dev = torch.device(self._device) if self._device is not None else torch.device('cuda', torch.cuda.current_device())
+        d = type('EvalDeviceState', (), {})()
+        d.torch, d.lib, d.dev = torch, _lib, dev
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+        G = len(self.gt_kept)
+        d.gt_box = up(self.gt_box if G else np.zeros((1, 4)))
+        d.gt_kept = up(self.gt_kept if G else np.zeros(1, np.uint8))
+        d.gt_start, d.keep_len, d.thr = up(self.gt_start), up(self.keep_len), up(self.thr)
+        d.state = torch.zeros(4, dtype=torch.int32, device=dev)
+        d.cap = 0
+        d.det_box = d.det_score = d.det_img = None
+        self._dev = d
+        self._reserve(1 << 16)
+        return d
+
+    def _reserve(self, need):
+        """grow the detection store to hold `need` entries (device-to-device copies on the current stream, no sync)"""
+        d = self._dev
+        if need <= d.cap:
+            return
+        torch = d.torch
+        cap = max(int(need), 2 * d.cap)
+        new = [torch.empty((cap, 4), dtype=torch.float64, device=d.dev), torch.empty(cap, dtype=torch.float64, device=d.dev),
+               torch.empty(cap, dtype=torch.int32, device=d.dev)]
+        if d.cap:
+            for n, o in zip(new, (d.det_box, d.det_score, d.det_img)):
+                n[:d.cap].copy_(o)
+        d.det_box, d.det_score, d.det_img = new
+        d.cap = cap
+
+    def _desc(self):
+        d = self._dev
+        desc = d.lib.WFEvalDesc()
+        desc.num_images, desc.num_gt, desc.det_capacity = len(self.image_ids), len(self.gt_kept), d.cap
+        desc.num_thresholds = len(self.thr)
+        desc.as_written = int(self.as_written)
+        desc.label_index = -1 if self.label_index is None else self.label_index
+        desc.iou_thresh = self.iou_thresh
+        return desc
+
+    def _bufs(self, **extra):
+        d = self._dev
+        b = d.lib.WFEvalBufs()
+        for k in ('det_box', 'det_score', 'det_img', 'state', 'gt_box', 'gt_start', 'gt_kept', 'keep_len', 'thr'):
+            setattr(b, k, getattr(d, k).data_ptr())
+        for k, t in extra.items():
+            setattr(b, k, t.data_ptr() if t is not None else None)
+        return b
+
+    def _ordinals(self, meta_batch):
+        """image ordinals of a batch; an unknown id, or one that already arrived since the last evaluate(), is a ValueError"""
+        ords = []
+        for m in meta_batch:
+            key = m['image_id']
+            if key not in self._img_ord:
+                raise ValueError('image id %r is not in the annotations' % (key,))
+            o = self._img_ord[key]
+            if o in self._seen or o in ords:
+                raise ValueError('image id %r arrived twice before evaluate()' % (key,))
+            ords.append(o)
+        return ords
+
+    # ------------------------------------------------------------------ accumulation
+    def update(self, results):
+        """results: tuple(predict_bboxes, meta_batch); predict_bboxes[i] is a list of [label, score, x, y, w, h] rows for
+        image meta_batch[i]['image_id'] (what LFD.get_results / predict_for_single_image return).  With as_written the rows
+        are quantised here, on the host, with the reference's own Python expressions."""
+        if not (isinstance(results, tuple) and len(results) == 2):
+            raise TypeError('update info should contain two parts: predict bboxes and meta info.')
+        predict_bboxes, meta_batch = results
+        if len(predict_bboxes) != len(meta_batch):
+            raise ValueError('%d prediction lists for %d meta entries' % (len(predict_bboxes), len(meta_batch)))
+        ords = self._ordinals(meta_batch)
+        rows = []
+        for o, boxes in zip(ords, predict_bboxes):
+            if self.as_written:
+                rows.append((o, 0.001, 0.0, 0.0, 0.0, 0.0))
+            for r in boxes:
+                if self.label_index is not None and r[0] != self.label_index:
+                    continue
+                if self.as_written:
+                    rows.append((o,) + _quantise_as_written(r))
+                else:
+                    rows.append((o, r[1], r[2], r[3], r[4], r[5]))
+        if not ords:
+            return
+        self._seen.update(ords)
+        if not rows:
+            return
+        d = self._state()
+        torch = d.torch
+        self._upper += len(rows)
+        self._reserve(self._upper)
+        with torch.cuda.device(d.dev):
+            rows_t = torch.from_numpy(np.array(rows, np.float64).reshape(len(rows), 6)).to(d.dev)
+            desc, bufs = self._desc(), self._bufs()
+            d.lib.check(d.lib.lib().lfd_eval_wf_append_rows_f64(C.byref(desc), C.byref(bufs), d.lib.ptr(rows_t), len(rows),
+                                                                d.lib.stream_ptr()), 'lfd_eval_wf_append_rows_f64')
+
+    def update_resident(self, outputs, meta_batch):
+        """Appends the kept boxes of an ops.DetectOutputs (LFD.detect / detect_resident) on the device: no .item(),
+        .tolist(), .cpu() or synchronisation; the number of kept boxes is read from outputs.counts by the kernel, which also
+        forms w = x2 - x1 + 1 and h in fp32 (the two roundings of LFD._pack) and, with as_written, does the quantisation and
+        adds the dummy row.  The only host -> device traffic is the batch's image ordinals (pinned, asynchronous)."""
+        n, cap = int(outputs.dets.size(0)), int(outputs.dets.size(1))
+        if len(meta_batch) != n:
+            raise ValueError('%d meta entries for a batch of %d' % (len(meta_batch), n))
+        ords = self._ordinals(meta_batch)
+        d = self._state()
+        torch = d.torch
+        if outputs.dets.device != d.dev:
+            raise RuntimeError('update_resident: the outputs live on %s, the evaluator on %s' % (outputs.dets.device, d.dev))
+        self._upper += n * (cap + 1)
+        self._reserve(self._upper)
+        with torch.cuda.device(d.dev):
+            host = torch.empty(n, dtype=torch.int32, pin_memory=True)
+            host.numpy()[:] = ords
+            ord_t = host.to(d.dev, non_blocking=True)
+            desc, bufs = self._desc(), self._bufs()
+            d.lib.check(d.lib.lib().lfd_eval_wf_append_dets_f32(C.byref(desc), C.byref(bufs), d.lib.ptr(outputs.dets),
+                                                                d.lib.ptr(outputs.labels), d.lib.ptr(outputs.counts), n, cap,
+                                                                d.lib.ptr(ord_t), d.lib.stream_ptr()),
+                        'lfd_eval_wf_append_dets_f32')
+        self._seen.update(ords)
+
+    # ------------------------------------------------------------------ evaluation
+    def _run(self, keep_matches=False):
+        """enqueue the score range, the grouping and the matching; returns the device tensors (no synchronisation)"""
+        d = self._state()
+        torch, lib = d.torch, d.lib
+        I, T = len(self.image_ids), len(self.thr)
+        with torch.cuda.device(d.dev):
+            i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=d.dev)   # noqa: E731
+            u8 = lambda *s: torch.empty(s, dtype=torch.uint8, device=d.dev)   # noqa: E731
+            out = dict(det_start=i32(I + 1), det_index=i32(d.cap), det_gt=i32(d.cap), det_over=u8(d.cap), det_prop=i32(3, d.cap),
+                       det_rec=i32(3, d.cap), det_flags=u8(d.cap) if keep_matches else None,
+                       curve=torch.empty((3, T, 2), dtype=torch.int64, device=d.dev),
+                       faces=torch.empty(3, dtype=torch.int64, device=d.dev),
+                       minmax=torch.empty(2, dtype=torch.float64, device=d.dev))
+            desc, bufs = self._desc(), self._bufs(**out)
+            wb = lib.lib().lfd_eval_wf_workspace_bytes(C.byref(desc))
+            if wb == 0:
+                raise RuntimeError('WIDERFACEEvaluator: this problem size is not supported by the evaluation kernels')
+            ws = torch.empty(wb, dtype=torch.uint8, device=d.dev)
+            lib.check(lib.lib().lfd_eval_wf_match(C.byref(desc), C.byref(bufs), lib.ptr(ws), wb, lib.stream_ptr()),
+                      'lfd_eval_wf_match')
+        out['ws'] = ws
+        return out
+
+    def evaluate(self, keep_matches=False):
+        """Runs the kernels on what update / update_resident accumulated and fills `curve` (int64 [3, 1000, 2]: proposals and
+        recalled faces per difficulty and threshold), `faces` (int64 [3]), `precision`, `recall` (float64 [3, 1000]) and `ap`
+        (float64 [3]), builds the display string, clears the accumulated detections and returns {'easy': ap, 'medium': ap,
+        'hard': ap}.  keep_matches=True keeps the per-detection outcomes for `match_table()`."""
+        T = len(self.thr)
+        self._last = None
+        stored = self._upper > 0
+        if not stored:
+            curve = np.zeros((3, T, 2), np.int64)
+            faces = self.keep_len.astype(np.int64).sum(0)
+            self._clear()
+        else:
+            d = self._state()
+            torch = d.torch
+            out = self._run(keep_matches)
+            with torch.cuda.device(d.dev):
+                flat = torch.cat([out['curve'].reshape(-1), out['faces'], d.state.long()]).cpu().numpy()   # the one D2H
+            curve = flat[:6 * T].reshape(3, T, 2).copy()
+            faces = flat[6 * T:6 * T + 3].copy()
+            state = flat[6 * T + 3:]
+            err = int(state[1])
+            if keep_matches and not err:
+                n = int(state[2])
+                start = out['det_start'].cpu().numpy()
+                ranked = np.repeat(np.diff(self.gt_start) > 0, np.diff(start))      # images without ground truth are not ranked
+                self._last = dict(det_start=start, ranked=ranked)
+                for k in ('det_index', 'det_gt', 'det_flags'):
+                    self._last[k] = out[k][:n].cpu().numpy()
+                for k in ('det_prop', 'det_rec'):
+                    self._last[k] = out[k][:, :n].cpu().numpy()
+            self._clear()
+            if err:
+                msgs = [m for bit, m in ((ERR_CAPACITY, 'the detection store overflowed'), (ERR_IMAGE, 'an image ordinal was out of range'))
+                        if err & bit]
+                raise RuntimeError('WIDERFACEEvaluator: ' + '; '.join(msgs) + ' (status bits %d); the accumulated detections were dropped' % err)
+        self.curve, self.faces = curve, faces
+        self.precision, self.recall, self.ap = widerface_ap(curve, faces)
+        self._eval_display_str = '\n' + ''.join('{:<10}:{:.5f}\n'.format(name + ' AP', self.ap[i]) for i, name in enumerate(DIFFICULTIES))
+        return dict((name, float(self.ap[i])) for i, name in enumerate(DIFFICULTIES))
+
+    def match_table(self, d=0):
+        """After evaluate(keep_matches=True), for difficulty d (0 easy, 1 medium, 2 hard, or its name): dict of numpy arrays
+        with one row per stored detection of an image that has ground truth, image-major and in rank order inside an image --
+        `image` (ordinal in `image_ids`), `index` (index into the detection store: the insertion index, where update_resident
+        with label_index also counts the rows of other labels, which keep their slot, and update does not), `rank`, `m` (first ground truth of
+        maximal IoU, index inside the image's boxes), `over` (that IoU >= iou_thresh), `proposal` (bool) and `rec` (the
+        running count of recalled faces)."""
+        if self._last is None:
+            raise RuntimeError('match_table: call evaluate(keep_matches=True) first')
+        if d in DIFFICULTIES:
+            d = DIFFICULTIES.index(d)
+        L = self._last
+        start, sel = L['det_start'], L['ranked']
+        image = np.repeat(np.arange(len(start) - 1), np.diff(start))
+        rank = np.arange(len(image)) - start[image]
+        flags = L['det_flags'][sel]
+        return dict(image=image[sel], index=L['det_index'][sel], rank=rank[sel], m=L['det_gt'][sel], over=(flags & 1).astype(bool),
+                    proposal=((flags >> (1 + d)) & 1).astype(bool), rec=L['det_rec'][d][sel])
+
+    def _clear(self):
+        self._seen = set()
+        self._upper = 0
+        if self._dev is not None:
+            self._dev.state.zero_()
 
     def get_eval_display_str(self):
         return self._eval_display_str
