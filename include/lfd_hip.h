@@ -342,6 +342,75 @@ LFD_API int lfd_get_loss_bwd_f32(const lfd_loss_desc_t* d, const float* pred_cls
                          const float* grad_out, float* grad_cls, float* grad_reg, lfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sibling meta-architectures: target assignment and fused get_loss on the device (csrc/assign_sibling.hip,
+ * csrc/getloss_fcos.hip).  Conventions of lfd_assign_targets_f32: whole batch in one launch, one thread per (image,
+ * point), points generated on the fly, gt_boxes [num_boxes,4] (x, y, w, h), gt_labels [num_boxes], image i owns rows
+ * [gt_offsets[i], gt_offsets[i+1]) (device array of n + 1 values; rows outside [0, num_boxes) are never read).
+ * gt_offsets_host (nullable) is the caller's host copy of gt_offsets: when given it is checked before the launch
+ * (non-negative, non-decreasing, <= num_boxes) -- the device copy cannot be without a sync.  Any G per image (boxes are
+ * staged through LDS in fixed-size chunks), G = 0 included.  fp32, reference expression order, IEEE divide / sqrt.
+ *
+ * lfd_assign_targets_fcos_f32: FCOS.annotation_to_target (lfd/model/fcos.py:108-209).  Per (point, box)
+ *   dist = (px-x, py-y, (x+w-1)-px, (y+h-1)-py); the pair is valid iff min(dist) > 0 and range_lo <= max(dist) <=
+ *   range_hi of the point's level (both inclusive; floats: the last level's bound is 1e8).  The point takes the valid
+ *   box of smallest area w*h, ties -> lowest box index.  labels int64 [n,P] = that box's label or num_classes when no
+ *   box is valid; reg_targets [n,P,4] = dist of the chosen box (box 0 when none is valid, zeros when the image has no
+ *   box).  multi_label != 0 (FCOSv1, fcos.py:550-656): labels int64 [n,P,num_classes], 0 where a valid box of that
+ *   class covers the point, 1 elsewhere; reg_targets unchanged.
+ * lfd_assign_targets_v2_f32: LFDv2._generate_target_for_single_image (lfd/model/lfdv2.py:278-418) over
+ *   lfd_assign_desc_t (integer ranges, assign_mode 0..3, independent).  score = sqrt(min(l,r)/max(l,r) *
+ *   min(t,b)/max(t,b)) inside the box (hit test >= 0, denominators clamped at 0.01), 1 in the stride-sized core zone,
+ *   times the linear relaxation across the gray band; cls_targets [n,P,C] = per-class maximum of the positive scores,
+ *   reg_targets [n,P,4] = delta of the box with the largest score (/ reg_hi when independent), ties -- the all-zero row
+ *   included -- -> lowest box index. */
+typedef struct {
+  int32_t n, num_levels;
+  int32_t level_h[LFD_MAX_LEVELS], level_w[LFD_MAX_LEVELS], stride[LFD_MAX_LEVELS];
+  float range_lo[LFD_MAX_LEVELS], range_hi[LFD_MAX_LEVELS];   /* regress_ranges (fcos.py:19) */
+  int32_t total_points, num_classes;
+  int32_t multi_label, reserved_;
+} lfd_assign_fcos_desc_t;
+LFD_API int lfd_assign_targets_fcos_f32(const lfd_assign_fcos_desc_t* d, const float* gt_boxes, const int64_t* gt_labels,
+                                int64_t num_boxes, const int32_t* gt_offsets, const int32_t* gt_offsets_host,
+                                int64_t* labels, float* reg_targets, lfd_stream_t stream);
+LFD_API int lfd_assign_targets_v2_f32(const lfd_assign_desc_t* d, const float* gt_boxes, const int64_t* gt_labels,
+                              int64_t num_boxes, const int32_t* gt_offsets, const int32_t* gt_offsets_host,
+                              float* cls_targets, float* reg_targets, lfd_stream_t stream);
+
+/* Fused FCOS.get_loss / FCOSv1.get_loss (lfd/model/fcos.py:240-317, :687-768), same three stages as lfd_get_loss_*:
+ *   sums     : one pass over all N*P rows -> 8 doubles {cls_sum (sigmoid focal of every row; multi_label: the flattened
+ *              one-class focal), reg_sum (box loss of distance2bbox(prediction) vs distance2bbox(target), weighted by
+ *              the centerness target), ctr_sum (BCE-with-logits of the centerness logit), n_pos, sum of centerness
+ *              targets, 0, 0, 0} over the positive rows (label != num_classes; any class present when multi_label);
+ *              fp64 block partials + fixed-order second stage: deterministic;
+ *   finalize : out[8] floats {classification_loss, regression_loss, centerness_loss, loss, n_pos, avg_factor_cls
+ *              (= n_pos + N), avg_factor_reg (= sum of centerness targets), rank_scale}; global_sums = the sums
+ *              all-reduced over image-parallel ranks (== local_sums on one GPU), N = n * rank_scale (the global batch
+ *              of equally sized per-rank batches); no positive -> regression and centerness loss 0, zero gradient;
+ *   bwd      : dense d/d pred_cls [N,P,C], d/d pred_reg [N,P,4], d/d pred_ctr [N,P,1] for upstream gradients
+ *              grad_out[4] of {classification_loss, regression_loss, centerness_loss, loss}.
+ * The centerness targets are constants (computed from the regression targets).  labels as written by
+ * lfd_assign_targets_fcos_f32.  All float tensors fp32, contiguous. */
+typedef struct {
+  int32_t n, num_levels;
+  int32_t level_h[LFD_MAX_LEVELS], level_w[LFD_MAX_LEVELS], stride[LFD_MAX_LEVELS];
+  int32_t total_points, num_classes;
+  int32_t multi_label;
+  int32_t box_loss;                 /* 0 IoULoss, 1 GIoULoss, 2 DIoULoss, 3 CIoULoss (lfd/model/losses/iou_loss.py) */
+  float gamma, alpha, box_eps;
+  float cls_loss_weight, reg_loss_weight, ctr_loss_weight;   /* loss_weight of the three loss modules */
+} lfd_fcos_loss_desc_t;
+LFD_API size_t lfd_fcos_loss_workspace_bytes(void);
+LFD_API int lfd_fcos_loss_sums_f32(const lfd_fcos_loss_desc_t* d, const float* pred_cls, const float* pred_reg,
+                           const float* pred_ctr, const int64_t* labels, const float* reg_targets, void* workspace,
+                           size_t workspace_bytes, double* sums, lfd_stream_t stream);
+LFD_API int lfd_fcos_loss_finalize_f32(const lfd_fcos_loss_desc_t* d, const double* local_sums, const double* global_sums,
+                               float rank_scale, float* out, lfd_stream_t stream);
+LFD_API int lfd_fcos_loss_bwd_f32(const lfd_fcos_loss_desc_t* d, const float* pred_cls, const float* pred_reg,
+                          const float* pred_ctr, const int64_t* labels, const float* reg_targets, const float* finalized,
+                          const float* grad_out, float* grad_cls, float* grad_reg, float* grad_ctr, lfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Parameter update of a training iteration over one flat fp32 buffer (all tensors of a param group
  * contiguous, 16-byte aligned).  Replaces OptimizerHook.after_train_iter's
  *   clip_grad.clip_grad_norm_(params, max_norm, norm_type=2)   (lfd/execution/hooks/optimizer_hook.py:21-24,30-33)

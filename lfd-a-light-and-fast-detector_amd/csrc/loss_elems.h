@@ -2,6 +2,7 @@
 // targets.hip) and the fused get_loss kernels (getloss.hip), so both paths produce the same values.
 #pragma once
 #include <float.h>
+#include <math.h>
 #include "common.h"
 
 // one element of SigmoidFocalLossForward (sigmoid_focal_loss_cuda.cu:31-57), fp32 math
@@ -81,4 +82,84 @@ static __device__ __forceinline__ float4 iou_loss_grad_elem(float4 a, float4 b, 
     g.w += da1 * pw; g.y -= da1 * pw;
   }
   return g;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// GIoU / DIoU / CIoU (boxloss.hip's stand-alone kernel and the fused FCOS get_loss, getloss_fcos.hip): the loss
+// expression on dual numbers -- value + the four partial derivatives w.r.t. the predicted x1, y1, x2, y2.
+// ---------------------------------------------------------------------------------------------------------
+struct Dual {
+  float v;
+  float d[4];
+};
+
+static __device__ __forceinline__ Dual cst(float v) { return Dual{v, {0.f, 0.f, 0.f, 0.f}}; }
+static __device__ __forceinline__ Dual var(float v, int i) {
+  Dual r = cst(v);
+  r.d[i] = 1.f;
+  return r;
+}
+static __device__ __forceinline__ Dual operator+(const Dual& a, const Dual& b) {
+  return Dual{a.v + b.v, {a.d[0] + b.d[0], a.d[1] + b.d[1], a.d[2] + b.d[2], a.d[3] + b.d[3]}};
+}
+static __device__ __forceinline__ Dual operator-(const Dual& a, const Dual& b) {
+  return Dual{a.v - b.v, {a.d[0] - b.d[0], a.d[1] - b.d[1], a.d[2] - b.d[2], a.d[3] - b.d[3]}};
+}
+static __device__ __forceinline__ Dual operator*(const Dual& a, const Dual& b) {
+  Dual r;
+  r.v = a.v * b.v;
+  for (int i = 0; i < 4; ++i) r.d[i] = a.d[i] * b.v + a.v * b.d[i];
+  return r;
+}
+static __device__ __forceinline__ Dual operator/(const Dual& a, const Dual& b) {
+  Dual r;
+  r.v = a.v / b.v;
+  const float inv = 1.f / b.v;
+  for (int i = 0; i < 4; ++i) r.d[i] = (a.d[i] - r.v * b.d[i]) * inv;
+  return r;
+}
+static __device__ __forceinline__ Dual operator+(const Dual& a, float c) { Dual r = a; r.v += c; return r; }
+static __device__ __forceinline__ Dual operator*(const Dual& a, float c) {
+  return Dual{a.v * c, {a.d[0] * c, a.d[1] * c, a.d[2] * c, a.d[3] * c}};
+}
+static __device__ __forceinline__ Dual dmax(const Dual& a, const Dual& b) { return a.v >= b.v ? a : b; }
+static __device__ __forceinline__ Dual dmin(const Dual& a, const Dual& b) { return a.v <= b.v ? a : b; }
+static __device__ __forceinline__ Dual clamp0(const Dual& a) { return a.v > 0.f ? a : cst(0.f); }   // .clamp(min=0)
+static __device__ __forceinline__ Dual datan(const Dual& a) {
+  const float g = 1.f / (1.f + a.v * a.v);
+  return Dual{atanf(a.v), {a.d[0] * g, a.d[1] * g, a.d[2] * g, a.d[3] * g}};
+}
+
+// kind: 1 GIoU (iou_loss.py:127-169), 2 DIoU (:172-223), 3 CIoU (:226-283)
+static __device__ __forceinline__ Dual box_loss(float4 p, float4 t, int kind, float eps) {
+  const Dual x1 = var(p.x, 0), y1 = var(p.y, 1), x2 = var(p.z, 2), y2 = var(p.w, 3);
+  const Dual tx1 = cst(t.x), ty1 = cst(t.y), tx2 = cst(t.z), ty2 = cst(t.w);
+  const Dual w = clamp0(dmin(x2, tx2) - dmax(x1, tx1)), h = clamp0(dmin(y2, ty2) - dmax(y1, ty1));
+  const Dual overlap = w * h;
+  const Dual ap = (x2 - x1) * (y2 - y1);
+  const Dual ag = cst((t.z - t.x) * (t.w - t.y));
+  const Dual uni = ap + ag - overlap + eps;
+  const Dual iou = overlap / uni;
+  const Dual ew = clamp0(dmax(x2, tx2) - dmin(x1, tx1)), eh = clamp0(dmax(y2, ty2) - dmin(y1, ty1));
+  if (kind == 1) {
+    const Dual earea = ew * eh + eps;
+    const Dual giou = iou - (earea - uni) / earea;
+    return cst(1.f) - giou;
+  }
+  const Dual c2 = ew * ew + eh * eh + eps;
+  const Dual dx = (tx1 + tx2) - (x1 + x2), dy = (ty1 + ty2) - (y1 + y2);
+  const Dual rho2 = (dx * dx) * 0.25f + (dy * dy) * 0.25f;
+  if (kind == 2) return cst(1.f) - (iou - rho2 / c2);
+  const Dual w1 = x2 - x1, h1 = (y2 - y1) + eps;
+  const float w2 = t.z - t.x, h2 = (t.w - t.y) + eps;
+  const float factor = 4.f / (float)(M_PI * M_PI);
+  const Dual da = cst(atanf(w2 / h2)) - datan(w1 / h1);
+  const Dual v = (da * da) * factor;
+  const Dual ciou = iou - (rho2 / c2 + (v * v) / (cst(1.f) - iou + v));
+  return cst(1.f) - ciou;
+}
+
+// B(x, t) = max(x, 0) - x t + log(1 + exp(-|x|))  (F.binary_cross_entropy_with_logits), dB/dx = sigmoid(x) - t
+static __device__ __forceinline__ float bce_logits(float x, float t) {
+  return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
 }

@@ -146,6 +146,25 @@ class LossDesc(C.Structure):
                 ('cls_weighted', C.c_int32), ('reg_weighted', C.c_int32)]
 
 
+class AssignFcosDesc(C.Structure):
+    """lfd_assign_fcos_desc_t"""
+    _fields_ = [('n', C.c_int32), ('num_levels', C.c_int32),
+                ('level_h', C.c_int32 * MAX_LEVELS), ('level_w', C.c_int32 * MAX_LEVELS), ('stride', C.c_int32 * MAX_LEVELS),
+                ('range_lo', C.c_float * MAX_LEVELS), ('range_hi', C.c_float * MAX_LEVELS),
+                ('total_points', C.c_int32), ('num_classes', C.c_int32),
+                ('multi_label', C.c_int32), ('reserved_', C.c_int32)]
+
+
+class FcosLossDesc(C.Structure):
+    """lfd_fcos_loss_desc_t"""
+    _fields_ = [('n', C.c_int32), ('num_levels', C.c_int32),
+                ('level_h', C.c_int32 * MAX_LEVELS), ('level_w', C.c_int32 * MAX_LEVELS), ('stride', C.c_int32 * MAX_LEVELS),
+                ('total_points', C.c_int32), ('num_classes', C.c_int32),
+                ('multi_label', C.c_int32), ('box_loss', C.c_int32),
+                ('gamma', C.c_float), ('alpha', C.c_float), ('box_eps', C.c_float),
+                ('cls_loss_weight', C.c_float), ('reg_loss_weight', C.c_float), ('ctr_loss_weight', C.c_float)]
+
+
 class PackJob(C.Structure):
     """lfd_pack_job_t"""
     _fields_ = [('w', C.c_void_p), ('out', C.c_void_p), ('cout', C.c_int32), ('cin', C.c_int32), ('ks', C.c_int32),
@@ -259,6 +278,12 @@ _SIGNATURES = {
     'lfd_get_loss_sums_f32': (C.c_int, [C.POINTER(LossDesc), _P, _P, _P, _P, _P, _SZ, _P, _P]),
     'lfd_get_loss_finalize_f32': (C.c_int, [C.POINTER(LossDesc), _P, _P, _F, _P, _P]),
     'lfd_get_loss_bwd_f32': (C.c_int, [C.POINTER(LossDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'lfd_assign_targets_fcos_f32': (C.c_int, [C.POINTER(AssignFcosDesc), _P, _P, _I64, _P, _P, _P, _P, _P]),
+    'lfd_assign_targets_v2_f32': (C.c_int, [C.POINTER(AssignDesc), _P, _P, _I64, _P, _P, _P, _P, _P]),
+    'lfd_fcos_loss_workspace_bytes': (_SZ, []),
+    'lfd_fcos_loss_sums_f32': (C.c_int, [C.POINTER(FcosLossDesc), _P, _P, _P, _P, _P, _P, _SZ, _P, _P]),
+    'lfd_fcos_loss_finalize_f32': (C.c_int, [C.POINTER(FcosLossDesc), _P, _P, _F, _P, _P]),
+    'lfd_fcos_loss_bwd_f32': (C.c_int, [C.POINTER(FcosLossDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'lfd_grad_norm_workspace_bytes': (_SZ, []),
     'lfd_grad_norm_clip_coef_f32': (C.c_int, [_P, _I64, _F, _P, _P, _SZ, _P, _P, _P]),
     'lfd_scale_by_clip_coef_f32': (C.c_int, [_P, _I64, _P, _P]),

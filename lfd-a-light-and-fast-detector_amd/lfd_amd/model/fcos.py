@@ -10,14 +10,16 @@ Same constructor kwargs, `forward(x) -> (cls [N,P,C], reg [N,P,4] distances, cen
   get_results         ONE device pass for the whole batch, lfd_detect_batched_ex (csrc/postproc.hip): sigmoid scores x
                       sigmoid centerness, per-level pre-NMS top-k, decode, threshold, class-wise NMS, post-NMS cap --
                       instead of the reference's per-image, per-level Python loop (fcos.py:331-412)
-  get_loss            targets with the reference's [P,G] tensor algebra on the host (where the reference computes them
-                      too, :108-209), losses on the HIP loss kernels (focal / IoU-family / BCE, csrc/losses.hip, boxloss.hip)
+  get_loss            on a CUDA prediction: targets by lfd_assign_targets_fcos_f32 (csrc/assign_sibling.hip, one launch per
+                      batch) and the three-launch fused loss (csrc/getloss_fcos.hip), one host sync; with
+                      `device_targets = False`, or loss modules the fused kernels do not cover: targets with the
+                      reference's [P,G] tensor algebra on the host (:108-209), losses op by op on the HIP loss kernels
   train-mode forward  PyTorch-ROCm autograd over the same parameters (training-only route, as for LFD)
 """
 import torch
 import torch.nn as nn
 
-from .. import _lib, engine_sibling, ops, train_engine
+from .. import _lib, engine_sibling, ops, parallel, train_engine
 from .lfd import LFD
 from .utils import multiclass_nms  # noqa: F401  (importable like the reference module)
 
@@ -26,7 +28,29 @@ __all__ = ['FCOS', 'FCOSv1']
 INF = 1e8
 
 
+class _FusedFCOSLossFunction(torch.autograd.Function):
+    """get_loss as lfd_fcos_loss_{sums,finalize,bwd}_f32 (csrc/getloss_fcos.hip): -> [classification_loss, regression_loss,
+    centerness_loss, loss]; backward writes the three dense prediction gradients in one launch."""
+
+    @staticmethod
+    def forward(ctx, pred_cls, pred_reg, pred_ctr, labels, reg_t, desc, reduce_sums, rank_scale):
+        fin = ops.fcos_loss_forward(desc, pred_cls, pred_reg, pred_ctr, labels, reg_t, reduce_sums, rank_scale)
+        ctx.desc = desc
+        ctx.save_for_backward(pred_cls, pred_reg, pred_ctr, labels, reg_t, fin)
+        return fin[:4].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        pred_cls, pred_reg, pred_ctr, labels, reg_t, fin = ctx.saved_tensors
+        gc, gr, gt = ops.fcos_loss_backward(ctx.desc, pred_cls, pred_reg, pred_ctr, labels, reg_t, fin, g)
+        return (gc.view_as(pred_cls).to(pred_cls.dtype), gr.view_as(pred_reg).to(pred_reg.dtype),
+                gt.view_as(pred_ctr).to(pred_ctr.dtype), None, None, None, None, None)
+
+
 class FCOS(nn.Module):
+
+    _multi_label = False
+    device_targets = True        # False: targets on the host and op-by-op losses (the reference's route) on any device
 
     def __init__(self, backbone=None, neck=None, head=None, num_classes=80,
                  regress_ranges=((0, 64), (64, 128), (128, 256), (256, 512), (512, INF)),
@@ -163,10 +187,42 @@ class FCOS(nn.Module):
         return LFD.distance2bbox(self, points, distance, max_shape)
 
     # ------------------------------------------------------------------ loss
+    def _fused_loss_supported(self, pred_cls):
+        """the device path (csrc/assign_sibling.hip + getloss_fcos.hip) covers sigmoid FocalLoss + an IoU-family regression
+        loss + BCEWithLogitsLoss, all with 'mean' reduction; anything else takes the op-by-op path"""
+        if pred_cls.device.type != 'cuda' or not self.device_targets:
+            return False
+        cf, rf, tf = self._classification_loss_func, self._regression_loss_func, self._centerness_loss_func
+        return type(cf).__name__ == 'FocalLoss' and getattr(cf, 'use_sigmoid', True) \
+            and type(rf).__name__ in ops.FCOS_BOX_LOSSES and type(tf).__name__ == 'BCEWithLogitsLoss' \
+            and cf.reduction == 'mean' and rf.reduction == 'mean' and tf.reduction == 'mean'
+
+    def _get_loss_fused(self, pred_cls, pred_reg, pred_ctr, annotation_batch):
+        """device path end to end: annotations concatenated on the host and uploaded once, targets by
+        lfd_assign_targets_fcos_f32, loss by the fused kernels; no per-image tensors, one host sync"""
+        cf, rf, tf = self._classification_loss_func, self._regression_loss_func, self._centerness_loss_func
+        sizes = [self._head_indexes_to_feature_map_sizes[i] for i in range(self._num_levels)]
+        # annotation_to_target builds the ranges with points.new_tensor(...) on the int64 point grid (fcos.py:190)
+        ranges = [(int(lo), int(hi)) for lo, hi in self._regress_ranges]
+        labels, reg_t = ops.assign_targets_fcos_from_host(sizes, self._point_strides, ranges, self._num_classes,
+                                                          annotation_batch, pred_cls.device, multi_label=self._multi_label)
+        desc = ops.make_fcos_loss_desc(pred_cls.size(0), sizes, self._point_strides, self._num_classes, type(rf).__name__,
+                                       multi_label=self._multi_label, gamma=cf.gamma, alpha=cf.alpha, box_eps=rf.eps,
+                                       cls_loss_weight=cf.loss_weight, reg_loss_weight=rf.loss_weight,
+                                       ctr_loss_weight=tf.loss_weight)
+        dist_on = parallel.is_dist()
+        vals = _FusedFCOSLossFunction.apply(pred_cls, pred_reg, pred_ctr, labels, reg_t, desc,
+                                            parallel.global_count if dist_on else None,
+                                            float(parallel.world_size()) if dist_on else 1.0)
+        c, r, t, total = vals.tolist()      # the one host sync of the step (the reference does four .item())
+        return dict(loss=vals[3], loss_values=dict(loss=total, classification_loss=c, regression_loss=r, centerness_loss=t))
+
     def get_loss(self, predict_outputs, annotation_batch, *args):
         """fcos.py:240-317"""
         pred_cls, pred_reg, pred_ctr = predict_outputs
         dev = pred_cls.device
+        if self._fused_loss_supported(pred_cls):
+            return self._get_loss_fused(pred_cls, pred_reg, pred_ctr, annotation_batch)
         gt_b = [torch.from_numpy(b) for b, _ in annotation_batch]
         gt_l = [torch.from_numpy(l) for _, l in annotation_batch]
         pts_list = self.generate_point_coordinates(self._head_indexes_to_feature_map_sizes)
@@ -224,6 +280,8 @@ class FCOSv1(FCOS):
     row of C binary labels (0 = this class is present at the point, 1 = background; :611-616) instead of one label, the
     logits are flattened to [N*P*C, 1] for a one-class focal loss (:711), a point is positive when any of its classes is
     (:715-716).  The regression / centerness targets, the network and get_results are FCOS's."""
+
+    _multi_label = True
 
     def _empty_labels(self, gt_labels, P):
         # (the reference returns FCOS's [P] vector of C here, :570-572, which its own get_loss cannot reshape to [*, C]

@@ -9,8 +9,10 @@ modes, predict_for_single_image :704-815 == LFD's) is inherited from ..lfd.LFD.
 
 Where the arithmetic runs: forward on the fused LFD plan when neck / head are what that plan covers (SimpleNeck + 1x1
 LFDHead), otherwise layer by layer on the same kernels (engine_sibling: FPN / SimpleFPN necks, 3x3 head convs);
-get_results as one lfd_detect_batched_ex pass per batch; targets with the reference's tensor algebra on the host (where
-the reference computes them), losses on the HIP loss kernels.
+get_results as one lfd_detect_batched_ex pass per batch; get_loss on a CUDA prediction: targets by
+lfd_assign_targets_v2_f32 (csrc/assign_sibling.hip), then LFD's fused get_loss when the loss modules are what it covers,
+else the op-by-op HIP loss kernels; `device_targets = False` builds the targets with the reference's tensor algebra on the
+host (annotation_to_target, the public mirror) and takes the op-by-op losses.
 """
 import torch
 
@@ -26,6 +28,7 @@ from .losses.iou_loss import bbox_overlaps  # noqa: E402,F401  (lfdv2.py:15-131 
 class LFDv2(LFD):
 
     _ASSIGN_MODES = ('longer', 'shorter', 'sqrt', 'dist')      # lfdv2.py:158
+    device_targets = True        # False: targets on the host and op-by-op losses (the reference's route) on any device
 
     def __init__(self, backbone=None, neck=None, head=None, num_classes=80,
                  regression_ranges=((0, 64), (64, 128), (128, 256), (256, 512), (512, 1024)),
@@ -124,11 +127,23 @@ class LFDv2(LFD):
         return cls_t, reg_t
 
     def _fused_loss_supported(self, pred_cls):
-        return False        # the device target kernel implements LFD's assignment, not LFDv2's
+        """LFD's rule (Focal or CE + IoULoss, 'mean'): the fused get_loss reads targets, whoever assigned them"""
+        return self.device_targets and super()._fused_loss_supported(pred_cls)
 
     def get_loss(self, predict_outputs, annotation_batch, *args):
-        """lfdv2.py:443-554: same reduction as LFD.get_loss over LFDv2's targets (built on the host, as in the reference)"""
+        """lfdv2.py:443-554: same reduction as LFD.get_loss over LFDv2's targets"""
         pred_cls, pred_reg = predict_outputs
+        if pred_cls.device.type == 'cuda' and self.device_targets:
+            sizes = [self._head_indexes_to_feature_map_sizes[i] for i in range(self._num_heads)]
+            # annotation_to_target builds the ranges with points.new_tensor(...) on the int64 point grid (lfdv2.py:232-276)
+            cls_t, reg_t = ops.assign_targets_v2_from_host(sizes, self._point_strides, self._regression_ranges,
+                                                           self._gray_ranges, self._num_classes, self._range_assign_mode,
+                                                           self._regression_loss_type == 'independent', annotation_batch,
+                                                           pred_cls.device)
+            if self._fused_loss_supported(pred_cls):
+                return self._get_loss_fused(pred_cls, pred_reg, cls_t, reg_t)
+            pts_list = self.generate_point_coordinates(self._head_indexes_to_feature_map_sizes)
+            return self._loss_from_targets(pred_cls, pred_reg, cls_t, reg_t, pts_list)
         gt_b = [torch.as_tensor(b) for b, _ in annotation_batch]
         gt_l = [torch.as_tensor(l) for _, l in annotation_batch]
         pts_list = self.generate_point_coordinates(self._head_indexes_to_feature_map_sizes)

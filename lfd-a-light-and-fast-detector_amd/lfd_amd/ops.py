@@ -514,6 +514,180 @@ def get_loss_backward(desc, pred_cls, pred_reg, cls_t, reg_t, finalized, grad_ou
     return gc, gr
 
 
+# ------------------------------------------------------------------ sibling targets / fused FCOS get_loss
+def _concat_gt_lists(gt_bboxes_list, gt_labels_list):
+    """device-resident per-image annotations -> (boxes [K,4], labels [K], offs [n+1] device, offs host, K)"""
+    import numpy as np
+    dev = gt_bboxes_list[0].device
+    require_cuda(gt_bboxes_list[0], 'assign_targets')
+    counts = [int(b.reshape(-1, 4).size(0)) for b in gt_bboxes_list]
+    offs_h = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    k = int(offs_h[-1])
+    if k:
+        boxes = torch.cat([b.reshape(-1, 4) for b in gt_bboxes_list], 0).contiguous().float()
+        labels = torch.cat([l.reshape(-1) for l in gt_labels_list], 0).contiguous().long()
+    else:
+        boxes = torch.zeros((1, 4), dtype=torch.float32, device=dev)
+        labels = torch.zeros((1,), dtype=torch.int64, device=dev)
+    return boxes, labels, torch.from_numpy(offs_h).to(dev), offs_h, k
+
+
+def _concat_gt_host(annotation_batch, device):
+    """annotation_batch of get_loss (list of (bboxes numpy [G,4] xywh, labels numpy [G])): concatenated on the host and
+    uploaded with three copies -> (boxes, labels, offs device, offs host, K)"""
+    import numpy as np
+    bl = [np.asarray(b, dtype=np.float32).reshape(-1, 4) for b, _ in annotation_batch]
+    ll = [np.asarray(l, dtype=np.int64).reshape(-1) for _, l in annotation_batch]
+    offs_h = np.concatenate([[0], np.cumsum([b.shape[0] for b in bl])]).astype(np.int32)
+    k = int(offs_h[-1])
+    if k:
+        boxes = torch.from_numpy(np.ascontiguousarray(np.concatenate(bl, 0))).to(device)
+        labels = torch.from_numpy(np.ascontiguousarray(np.concatenate(ll, 0))).to(device)
+    else:
+        boxes = torch.zeros((1, 4), dtype=torch.float32, device=device)
+        labels = torch.zeros((1,), dtype=torch.int64, device=device)
+    return boxes, labels, torch.from_numpy(offs_h).to(device), offs_h, k
+
+
+def make_assign_fcos_desc(n, sizes, strides, regress_ranges, num_classes, multi_label=False):
+    """-> (lfd_assign_fcos_desc_t, total points per image)"""
+    d = _lib.AssignFcosDesc()
+    d.n, d.num_levels = int(n), len(sizes)
+    total = 0
+    for i, (h, w) in enumerate(sizes):
+        d.level_h[i], d.level_w[i], d.stride[i] = int(h), int(w), int(strides[i])
+        d.range_lo[i], d.range_hi[i] = float(regress_ranges[i][0]), float(regress_ranges[i][1])
+        total += int(h) * int(w)
+    d.total_points, d.num_classes, d.multi_label = total, int(num_classes), int(bool(multi_label))
+    return d, total
+
+
+def _assign_fcos_launch(d, total, gt, dev):
+    boxes, labels, offs, offs_h, k = gt
+    shape = (d.n, total, d.num_classes) if d.multi_label else (d.n, total)
+    lab_t = torch.empty(shape, dtype=torch.int64, device=dev)
+    reg_t = torch.empty((d.n, total, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().lfd_assign_targets_fcos_f32(C.byref(d), ptr(boxes), ptr(labels), k, ptr(offs),
+                                                offs_h.ctypes.data_as(C.c_void_p), ptr(lab_t), ptr(reg_t), stream_ptr()),
+              'lfd_assign_targets_fcos_f32')
+    return lab_t, reg_t
+
+
+def assign_targets_fcos(sizes, strides, regress_ranges, num_classes, gt_bboxes_list, gt_labels_list, multi_label=False):
+    """FCOS.annotation_to_target (fcos.py:108-209; FCOSv1's with multi_label) for a batch of device-resident annotations:
+    -> labels int64 [N,P] (background = num_classes) or [N,P,C] (0 = class present), distances [N,P,4]"""
+    d, total = make_assign_fcos_desc(len(gt_bboxes_list), sizes, strides, regress_ranges, num_classes, multi_label)
+    return _assign_fcos_launch(d, total, _concat_gt_lists(gt_bboxes_list, gt_labels_list), gt_bboxes_list[0].device)
+
+
+def assign_targets_fcos_from_host(sizes, strides, regress_ranges, num_classes, annotation_batch, device, multi_label=False):
+    """assign_targets_fcos for the annotation_batch get_loss receives (numpy pairs), uploaded once"""
+    d, total = make_assign_fcos_desc(len(annotation_batch), sizes, strides, regress_ranges, num_classes, multi_label)
+    return _assign_fcos_launch(d, total, _concat_gt_host(annotation_batch, device), torch.device(device))
+
+
+def _assign_v2_launch(d, total, gt, dev):
+    boxes, labels, offs, offs_h, k = gt
+    cls_t = torch.empty((d.n, total, d.num_classes), dtype=torch.float32, device=dev)
+    reg_t = torch.empty((d.n, total, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().lfd_assign_targets_v2_f32(C.byref(d), ptr(boxes), ptr(labels), k, ptr(offs),
+                                              offs_h.ctypes.data_as(C.c_void_p), ptr(cls_t), ptr(reg_t), stream_ptr()),
+              'lfd_assign_targets_v2_f32')
+    return cls_t, reg_t
+
+
+def assign_targets_v2(sizes, strides, reg_ranges, gray_ranges, num_classes, assign_mode, independent, gt_bboxes_list,
+                      gt_labels_list):
+    """LFDv2.annotation_to_target (lfdv2.py:232-418) for a batch of device-resident annotations: -> cls targets [N,P,C]
+    (relaxed centerness-like scores), reg targets [N,P,4]"""
+    d, total = make_assign_desc(len(gt_bboxes_list), sizes, strides, reg_ranges, gray_ranges, num_classes, assign_mode,
+                                independent)
+    return _assign_v2_launch(d, total, _concat_gt_lists(gt_bboxes_list, gt_labels_list), gt_bboxes_list[0].device)
+
+
+def assign_targets_v2_from_host(sizes, strides, reg_ranges, gray_ranges, num_classes, assign_mode, independent,
+                                annotation_batch, device):
+    """assign_targets_v2 for the annotation_batch get_loss receives (numpy pairs), uploaded once"""
+    d, total = make_assign_desc(len(annotation_batch), sizes, strides, reg_ranges, gray_ranges, num_classes, assign_mode,
+                                independent)
+    return _assign_v2_launch(d, total, _concat_gt_host(annotation_batch, device), torch.device(device))
+
+
+FCOS_BOX_LOSSES = {'IoULoss': 0, 'GIoULoss': 1, 'DIoULoss': 2, 'CIoULoss': 3}
+
+
+def make_fcos_loss_desc(n, sizes, strides, num_classes, box_loss, multi_label=False, gamma=2.0, alpha=0.25, box_eps=1e-6,
+                        cls_loss_weight=1.0, reg_loss_weight=1.0, ctr_loss_weight=1.0):
+    """lfd_fcos_loss_desc_t of the fused FCOS get_loss kernels (box_loss: a key of FCOS_BOX_LOSSES)"""
+    d = _lib.FcosLossDesc()
+    d.n, d.num_levels = int(n), len(sizes)
+    total = 0
+    for i, (h, w) in enumerate(sizes):
+        d.level_h[i], d.level_w[i], d.stride[i] = int(h), int(w), int(strides[i])
+        total += int(h) * int(w)
+    d.total_points, d.num_classes = total, int(num_classes)
+    d.multi_label, d.box_loss = int(bool(multi_label)), FCOS_BOX_LOSSES[box_loss]
+    d.gamma, d.alpha, d.box_eps = float(gamma), float(alpha), float(box_eps)
+    d.cls_loss_weight, d.reg_loss_weight, d.ctr_loss_weight = float(cls_loss_weight), float(reg_loss_weight), float(ctr_loss_weight)
+    return d
+
+
+def _fcos_loss_inputs(desc, pred_cls, pred_reg, pred_ctr, labels, reg_t):
+    require_cuda(pred_cls, 'fcos_loss')
+    rows = desc.n * desc.total_points
+    ts = [pred_cls.detach().contiguous().float(), pred_reg.detach().contiguous().float(),
+          pred_ctr.detach().contiguous().float(), labels.contiguous().long(), reg_t.contiguous().float()]
+    for t, c in zip(ts, (desc.num_classes, 4, 1, desc.num_classes if desc.multi_label else 1, 4)):
+        if t.numel() != rows * c or t.device != ts[0].device:
+            raise ValueError('fcos_loss: tensor with %d elements on %s, expected %d rows x %d on %s'
+                             % (t.numel(), t.device, rows, c, ts[0].device))
+    return ts
+
+
+def fcos_loss_sums(desc, pred_cls, pred_reg, pred_ctr, labels, reg_t):
+    """this rank's float64[8] sums {cls, weighted reg, ctr, n_pos, sum of centerness targets, 0, 0, 0}
+    (lfd_fcos_loss_sums_f32); all-reduced over image-parallel ranks before fcos_loss_finalize"""
+    pc, pr, pt, lab, rt = _fcos_loss_inputs(desc, pred_cls, pred_reg, pred_ctr, labels, reg_t)
+    dev = pc.device
+    nbytes = lib().lfd_fcos_loss_workspace_bytes()
+    ws = _workspace(nbytes, dev)
+    sums = torch.empty(8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().lfd_fcos_loss_sums_f32(C.byref(desc), ptr(pc), ptr(pr), ptr(pt), ptr(lab), ptr(rt), ptr(ws), nbytes,
+                                           ptr(sums), stream_ptr()), 'lfd_fcos_loss_sums_f32')
+    return sums
+
+
+def fcos_loss_finalize(desc, sums, gsums, rank_scale=1.0):
+    """local + global sums -> float32[8] {classification_loss, regression_loss, centerness_loss, loss, n_pos, avg_cls,
+    avg_reg, rank_scale} (lfd_fcos_loss_finalize_f32)"""
+    out = torch.empty(8, dtype=torch.float32, device=sums.device)
+    with torch.cuda.device(sums.device):
+        check(lib().lfd_fcos_loss_finalize_f32(C.byref(desc), ptr(sums), ptr(gsums), float(rank_scale), ptr(out),
+                                               stream_ptr()), 'lfd_fcos_loss_finalize_f32')
+    return out
+
+
+def fcos_loss_forward(desc, pred_cls, pred_reg, pred_ctr, labels, reg_t, reduce_sums=None, rank_scale=1.0):
+    """fused FCOS.get_loss forward -> the float32[8] tensor of fcos_loss_finalize (reduce_sums: the all-reduce over ranks)"""
+    sums = fcos_loss_sums(desc, pred_cls, pred_reg, pred_ctr, labels, reg_t)
+    gsums = reduce_sums(sums) if reduce_sums is not None else sums
+    return fcos_loss_finalize(desc, sums, gsums, rank_scale)
+
+
+def fcos_loss_backward(desc, pred_cls, pred_reg, pred_ctr, labels, reg_t, finalized, grad_out):
+    """-> (d pred_cls, d pred_reg, d pred_ctr), dense, for grad_out[4] = d/d{classification, regression, centerness, loss}"""
+    pc, pr, pt, lab, rt = _fcos_loss_inputs(desc, pred_cls, pred_reg, pred_ctr, labels, reg_t)
+    g = grad_out.contiguous().float()
+    gc, gr, gt = torch.empty_like(pc), torch.empty_like(pr), torch.empty_like(pt)
+    with torch.cuda.device(pc.device):
+        check(lib().lfd_fcos_loss_bwd_f32(C.byref(desc), ptr(pc), ptr(pr), ptr(pt), ptr(lab), ptr(rt), ptr(finalized), ptr(g),
+                                          ptr(gc), ptr(gr), ptr(gt), stream_ptr()), 'lfd_fcos_loss_bwd_f32')
+    return gc, gr, gt
+
+
 # ------------------------------------------------------------------ conv stack (NHWC fp16)
 def pack_conv_weight(w):
     """[Cout,Cin,k,k] float (BN already folded) -> MFMA fragment order [Cout/32][k*k*Cin/16][64][8] fp16.
