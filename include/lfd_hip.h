@@ -1198,6 +1198,67 @@ LFD_API int lfd_batch_assemble_f32(const uint8_t* src, const lfd_batch_desc_t* d
                                    const int32_t* coef, const float* lut, const int32_t* map, int32_t n, int32_t c_src,
                                    int32_t c_out, int32_t h_out, int32_t w_out, float* out, lfd_stream_t stream);
 
+/* ---- training batch planning (csrc/batch_plan.hip) ------------------------------------------------------------------------
+ * Everything the host did per batch in front of lfd_batch_assemble_f32, for RandomBBoxCropRegionSampler over a dataset whose
+ * decoded images and annotations are resident on the device (lfd_amd/data.py ResidentDataset): the sampler's draws, the scaled,
+ * cropped and flipped boxes, the descriptors and the resize tables.  Two launches on `stream`: one workgroup per sample plans
+ * it, then one workgroup scans the per-sample box counts and compacts the boxes.
+ *
+ * Draws ("the draw contract"): per sample two Philox4x32-10 blocks, key (seed & 0xffffffff, seed >> 32), counter
+ * (slot i, batch, epoch, j), j = 0, 1 -> words r0..r7.  U(a, b) = ((a >> 5) * 2^26 + (b >> 6)) * 2^-53; pick(r, n) = (r * n) >> 32.
+ *   resize iff U(r0, r1) < resize_prob; scale = U(r2, r3) * (resize_hi - resize_lo) + resize_lo (double, no fma), else 1.0
+ *   target box = pick(r4, G); crop_x = tx - (min(0, wr) + pick(r5, |wr| + 1)), wr = crop_size - tw; crop_y with r6;
+ *   flip iff U(r7, r7) < flip_prob.  G = 0: target = {0, 0, res_w, res_h}.
+ * The rest is the arithmetic of lfd_amd/data.py (RandomBBoxCropRegionSampler.__call__, flip_boxes, resized_size, plan_tables),
+ * value for value; every output image is crop_size x crop_size.
+ *
+ * status (int32 [4], written by every call): [0] LFD_PLAN_* bits; [1] boxes dropped because a sample kept more than
+ * max_boxes_per_image; [2] boxes dropped because the batch kept more than max_boxes (from the batch's tail); [3] samples
+ * rendered as all zero without boxes (LFD_PLAN_EMPTY_RESIZE or LFD_PLAN_BAD_SAMPLE).  Nothing is written beyond a capacity. */
+#define LFD_PLAN_EMPTY_RESIZE 1    /* rint(h * scale) or rint(w * scale) < 1 (cv2.resize asserts; resized_size raises) */
+#define LFD_PLAN_IMAGE_OVERFLOW 2
+#define LFD_PLAN_BATCH_OVERFLOW 4
+#define LFD_PLAN_BAD_SAMPLE 8      /* a dataset index or a table entry out of range, or coordinates beyond 2^30 */
+#define LFD_PLAN_MAX_BATCH 4096
+typedef struct lfd_plan_desc {
+  uint64_t seed;
+  double resize_lo, resize_hi, resize_prob, flip_prob;
+  int64_t arena_bytes;          /* bytes behind the image arena: an image that does not fit is LFD_PLAN_BAD_SAMPLE */
+  uint32_t epoch, batch;
+  int32_t n;                    /* samples in the batch, 1 .. LFD_PLAN_MAX_BATCH */
+  int32_t num_images;           /* M: rows of img_offset / img_h / img_w */
+  int32_t total_boxes;          /* rows of box / label */
+  int32_t crop_size, c_src;     /* c_src: channels of every stored image (1 | 3) */
+  int32_t max_boxes_per_image, max_boxes;
+  int32_t reserved_;
+} lfd_plan_desc_t;
+typedef struct lfd_plan_bufs {
+  /* the dataset (read only) */
+  const int64_t* img_offset;    /* [M] bytes from the arena's start to image m, HWC uint8 with c_src channels */
+  const int32_t* img_h;         /* [M] */
+  const int32_t* img_w;         /* [M] */
+  const double* box;            /* [total_boxes, 4] x, y, w, h */
+  const int64_t* label;         /* [total_boxes] */
+  const int32_t* box_offset;    /* [M + 1] image m owns boxes box_offset[m] .. box_offset[m + 1] */
+  const int32_t* indices;       /* [n] dataset index of every slot of this batch */
+  /* for lfd_batch_assemble_f32 (h_out = w_out = crop_size) */
+  lfd_batch_desc_t* desc;       /* [n], 8-byte aligned */
+  int32_t* coef;                /* [n, 2 * crop_size, 4], 16-byte aligned */
+  /* staging, per sample */
+  float* stage_box;             /* [n, max_boxes_per_image, 4], 16-byte aligned */
+  int64_t* stage_label;         /* [n, max_boxes_per_image] */
+  int32_t* stage_count;         /* [n, 4]: kept (clipped), dropped, LFD_PLAN_* bits of the sample, reserved */
+  /* the batch's annotations, GraphedTrainStep's layout */
+  float* boxes;                 /* [max_boxes, 4] x, y, w, h, 16-byte aligned */
+  int64_t* labels;              /* [max_boxes] */
+  int32_t* offsets;             /* [n + 1] */
+  int32_t* status;              /* [4] */
+} lfd_plan_bufs_t;
+/* LFD_ERR_INVALID_ARGUMENT: a null or misaligned pointer, n < 1, crop_size < 1, c_src outside {1, 3}, a capacity < 1,
+ * resize_lo / resize_hi not finite; LFD_ERR_UNSUPPORTED: n > LFD_PLAN_MAX_BATCH or an assembled output of 2^31
+ * elements or more. */
+LFD_API int lfd_plan_bbox_crop_batch(const lfd_plan_desc_t* d, const lfd_plan_bufs_t* b, lfd_stream_t stream);
+
 /* ---- detection evaluation: COCO-style bbox AP (csrc/evaluate.hip) -----------------------------------------------------------
  * The device side of lfd_amd/evaluation.py (the reference's COCOEvaluator, lfd/evaluation/coco_evaluator.py:13-82, which hands
  * its detections to pycocotools).  The definition implemented is written out in DESIGN.md ("Evaluation"); it restates

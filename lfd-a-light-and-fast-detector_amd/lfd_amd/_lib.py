@@ -185,6 +185,20 @@ class BatchDesc(C.Structure):
                 ('flip', C.c_int32), ('reserved_', C.c_int32)]
 
 
+class PlanDesc(C.Structure):
+    """lfd_plan_desc_t"""
+    _fields_ = [('seed', C.c_uint64), ('resize_lo', C.c_double), ('resize_hi', C.c_double), ('resize_prob', C.c_double),
+                ('flip_prob', C.c_double), ('arena_bytes', C.c_int64), ('epoch', C.c_uint32), ('batch', C.c_uint32),
+                ('n', C.c_int32), ('num_images', C.c_int32), ('total_boxes', C.c_int32), ('crop_size', C.c_int32),
+                ('c_src', C.c_int32), ('max_boxes_per_image', C.c_int32), ('max_boxes', C.c_int32), ('reserved_', C.c_int32)]
+
+
+class PlanBufs(C.Structure):
+    """lfd_plan_bufs_t"""
+    _fields_ = [(k, C.c_void_p) for k in ('img_offset', 'img_h', 'img_w', 'box', 'label', 'box_offset', 'indices', 'desc', 'coef',
+                                          'stage_box', 'stage_label', 'stage_count', 'boxes', 'labels', 'offsets', 'status')]
+
+
 class EvalDesc(C.Structure):
     """lfd_eval_desc_t"""
     _fields_ = [('num_images', C.c_int32), ('num_categories', C.c_int32), ('num_gt', C.c_int32), ('det_capacity', C.c_int32),
@@ -363,6 +377,7 @@ _SIGNATURES = {
     'lfd_p32_groupnorm_relu_f32': (C.c_int, [_P, _I32, _I64, _I32, _I32, _P, _P, _F, _I32, _P, _SZ, _P]),
     'lfd_conv2d_downsample_nhwc_f16': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'lfd_batch_assemble_f32': (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P]),
+    'lfd_plan_bbox_crop_batch': (C.c_int, [C.POINTER(PlanDesc), C.POINTER(PlanBufs), _P]),
     'lfd_eval_append_dets_f32': (C.c_int, [C.POINTER(EvalDesc), C.POINTER(EvalBufs), _P, _P, _P, _I32, _I32, _P, _I32, _P, _I32, _P]),
     'lfd_eval_append_rows_f64': (C.c_int, [C.POINTER(EvalDesc), C.POINTER(EvalBufs), _P, _I64, _P, _I32, _P]),
     'lfd_eval_match_workspace_bytes': (_SZ, [C.POINTER(EvalDesc)]),

@@ -10,6 +10,10 @@ threads copy the source window each crop reads into pinned memory, and one kerne
     for image_batch, annotation_batch, meta_batch in loader:     # image_batch: device fp32 [N, 3, 480, 480]
         step(image_batch, annotation_batch)
 
+ResidentDataset + ResidentDataLoader (below) go one step further: with the decoded images and the annotations resident in
+HBM the plan itself -- draws, boxes, descriptors, tables -- is made on the device (csrc/batch_plan.hip), under the loader's own
+draw contract, and the annotations arrive as DeviceAnnotations.
+
 The resize is cv2's INTER_LINEAR for 8-bit images, the fixed-point scalar path of OpenCV 4.x resize.cpp, as a formula
 (`column_coefs` / `row_coefs`); agreement with cv2 itself is not verified.
 """
@@ -25,7 +29,7 @@ from . import _lib
 __all__ = ['RandomBBoxCropRegionSampler', 'IdleRegionSampler', 'RegionPlan', 'DeviceAugmentation', 'DeviceDataLoader',
            'DeviceImageStore', 'SIMPLE_NORMALIZE', 'STANDARD_NORMALIZE', 'CAFFE_IMAGENET_NORMALIZE', 'resized_size',
            'column_coefs', 'row_coefs', 'plan_tables', 'compose_host', 'pil_decode', 'assemble', 'assemble_batch',
-           'stage_batch']
+           'stage_batch', 'ResidentDataset', 'ResidentDataLoader', 'DeviceAnnotations', 'plan_bbox_crop_batch']
 
 # lfd/data_pipeline/dataset/sample.py:5
 RESERVED_KEYS = ('image_bytes', 'image_type', 'image_path', 'image', 'bboxes', 'bbox_labels')
@@ -599,3 +603,231 @@ class DeviceDataLoader(object):
         images, plans, flips, annotations, metas = self.plan(index_batch, self._rng(epoch, batch_index))
         h, w = max(p.valid_h for p in plans), max(p.valid_w for p in plans)
         return compose_host(images, plans, flips, self._aug, h, w), annotations, metas
+
+
+# ---------------------------------------------------------------------------------------------------------- resident loader
+class ResidentDataset(object):
+    """A DeviceImageStore plus the dataset's annotations as device tables, so that a whole batch can be planned by
+    csrc/batch_plan.hip: img_offset int64 [M], img_h / img_w int32 [M], box float64 [sumB, 4] (the samples' 'bboxes' x, y, w, h,
+    exactly the Python floats), label int64 [sumB], box_offset int32 [M + 1].  Samples without 'bboxes' own no boxes.  The
+    non-reserved sample keys (the metas) stay on the host: `metas[index]` is a dict, or None."""
+
+    def __init__(self, dataset, device, max_bytes, decode=None):
+        import torch
+        self.store = DeviceImageStore(dataset, device, max_bytes, decode)
+        self.device = self.store.arena.device
+        boxes, labels, offs, self.metas = [], [], [0], []
+        for i in range(len(dataset)):
+            sample = dataset[i]
+            if 'bboxes' in sample:
+                b = [[float(v) for v in row[:4]] for row in sample['bboxes']]
+                l = [int(v) for v in sample['bbox_labels']]
+                if len(b) != len(l):
+                    raise ValueError('sample %d: %d bboxes, %d bbox_labels' % (i, len(b), len(l)))
+                boxes += b
+                labels += l
+            offs.append(len(boxes))
+            keys = set(sample.keys()) - set(RESERVED_KEYS)
+            self.metas.append({k: sample[k] for k in keys} if keys else None)
+        if offs[-1] >= 1 << 31:
+            raise RuntimeError('ResidentDataset: %d boxes do not fit int32 offsets' % offs[-1])
+        self.num_images, self.num_boxes = len(self.metas), offs[-1]
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)     # noqa: E731
+        self.img_offset = up(np.asarray(self.store.offsets, dtype=np.int64).reshape(-1))
+        self.img_h = up(np.array([s[0] for s in self.store.shapes], dtype=np.int32))
+        self.img_w = up(np.array([s[1] for s in self.store.shapes], dtype=np.int32))
+        self.box = up(np.array(boxes, dtype=np.float64).reshape(-1, 4) if boxes else np.zeros((1, 4), np.float64))
+        self.label = up(np.array(labels, dtype=np.int64) if labels else np.zeros((1,), np.int64))
+        self.box_offset = up(np.array(offs, dtype=np.int32))
+        torch.cuda.synchronize(self.device)
+
+    def __len__(self):
+        return self.num_images
+
+    @property
+    def channels(self):
+        return self.store.channels
+
+
+class DeviceAnnotations(object):
+    """One batch's annotations on the device, in GraphedTrainStep's single-buffer layout:
+    `buffer` uint8 = [boxes f32 [max_boxes, 4] | labels i64 [max_boxes] | offsets i32 [n + 1]], with the three views.  Image i
+    owns boxes offsets[i] .. offsets[i + 1] (x, y, w, h); rows beyond offsets[n] are unspecified.  len() is the batch size.
+    Lives as long as the image batch it was drawn with (the loader's ring)."""
+
+    def __init__(self, n, max_boxes, device):
+        import torch
+        self.n, self.max_boxes = int(n), int(max_boxes)
+        mb = self.max_boxes
+        self.buffer = torch.zeros(24 * mb + 4 * (self.n + 1), dtype=torch.uint8, device=device)
+        self.boxes = self.buffer[:16 * mb].view(torch.float32).view(mb, 4)
+        self.labels = self.buffer[16 * mb:24 * mb].view(torch.int64)
+        self.offsets = self.buffer[24 * mb:].view(torch.int32)
+        self.status_words = torch.zeros(4, dtype=torch.int32, device=device)
+
+    def __len__(self):
+        return self.n
+
+    def to_host(self):
+        """-> the reference's annotation_batch: a list of (float32 [g, 4], int64 [g]) per image (copies; synchronises)"""
+        offs = self.offsets.cpu().numpy()
+        k = int(offs[-1])
+        boxes, labels = self.boxes[:k].cpu().numpy(), self.labels[:k].cpu().numpy()
+        return [(boxes[offs[i]:offs[i + 1]].copy(), labels[offs[i]:offs[i + 1]].copy()) for i in range(self.n)]
+
+    def status(self):
+        """-> dict(bits, dropped_per_image, dropped_batch, blank_images): what the planning kernel could not keep (synchronises).
+        bits: 1 a resize to an empty image, 2 / 4 boxes beyond max_boxes_per_image / max_boxes, 8 a sample out of range."""
+        w = [int(v) for v in self.status_words.cpu().numpy()]
+        return dict(bits=w[0], dropped_per_image=w[1], dropped_batch=w[2], blank_images=w[3])
+
+
+class PlanBuffers(object):
+    """what lfd_plan_bbox_crop_batch writes for lfd_batch_assemble_f32 and its per-sample staging (one ring slot)"""
+
+    def __init__(self, n, crop_size, max_boxes_per_image, device):
+        import torch
+        self.n, self.crop_size, self.max_boxes_per_image = int(n), int(crop_size), int(max_boxes_per_image)
+        self.desc = torch.zeros(DESC_BYTES * self.n, dtype=torch.uint8, device=device)
+        self.coef = torch.zeros((self.n, 2 * self.crop_size, 4), dtype=torch.int32, device=device)
+        self.stage_box = torch.zeros((self.n, self.max_boxes_per_image, 4), dtype=torch.float32, device=device)
+        self.stage_label = torch.zeros((self.n, self.max_boxes_per_image), dtype=torch.int64, device=device)
+        self.stage_count = torch.zeros((self.n, 4), dtype=torch.int32, device=device)
+
+    def desc_host(self):
+        """-> the descriptors as a list of lfd_amd._lib.BatchDesc (copies; synchronises)"""
+        raw = self.desc.cpu().numpy().tobytes()
+        return [_lib.BatchDesc.from_buffer_copy(raw, i * DESC_BYTES) for i in range(self.n)]
+
+
+def plan_bbox_crop_batch(rds, indices, seed, epoch, batch, crop_size, resize_range, resize_prob, flip_prob, plan, ann,
+                         max_boxes_per_image=None):
+    """lfd_plan_bbox_crop_batch on torch.cuda.current_stream(): plans the batch whose dataset indices are the device int32 row
+    `indices` over the ResidentDataset `rds` into `plan` (PlanBuffers) and `ann` (DeviceAnnotations)."""
+    import ctypes as C
+    n = int(indices.numel())
+    mbpi = plan.max_boxes_per_image if max_boxes_per_image is None else int(max_boxes_per_image)
+    if n != plan.n or n != ann.n or crop_size != plan.crop_size or not 1 <= mbpi <= plan.max_boxes_per_image:
+        raise ValueError('plan_bbox_crop_batch: buffers for another batch size, crop size or capacity')
+    if indices.dtype != _torch().int32 or not indices.is_contiguous():
+        raise TypeError('plan_bbox_crop_batch: indices must be a contiguous int32 row')
+    if not 0 <= int(seed) < 1 << 64 or not 0 <= int(epoch) < 1 << 32 or not 0 <= int(batch) < 1 << 32:
+        raise ValueError('plan_bbox_crop_batch: seed in [0, 2^64), epoch and batch in [0, 2^32)')
+    for t in (indices, plan.desc, ann.buffer, rds.box):
+        _lib.require_cuda(t, 'batch planning')
+    d = _lib.PlanDesc()
+    d.seed, d.epoch, d.batch = int(seed), int(epoch), int(batch)
+    d.resize_lo, d.resize_hi = float(resize_range[0]), float(resize_range[1])
+    d.resize_prob, d.flip_prob = float(resize_prob), float(flip_prob)
+    d.arena_bytes = int(rds.store.nbytes)
+    d.n, d.num_images, d.total_boxes = n, rds.num_images, rds.num_boxes
+    d.crop_size, d.c_src = int(crop_size), rds.channels
+    d.max_boxes_per_image, d.max_boxes = mbpi, ann.max_boxes
+    b = _lib.PlanBufs()
+    for k, t in (('img_offset', rds.img_offset), ('img_h', rds.img_h), ('img_w', rds.img_w), ('box', rds.box),
+                 ('label', rds.label), ('box_offset', rds.box_offset), ('indices', indices), ('desc', plan.desc),
+                 ('coef', plan.coef), ('stage_box', plan.stage_box), ('stage_label', plan.stage_label),
+                 ('stage_count', plan.stage_count), ('boxes', ann.boxes), ('labels', ann.labels), ('offsets', ann.offsets),
+                 ('status', ann.status_words)):
+        setattr(b, k, t.data_ptr())
+    _lib.check(_lib.lib().lfd_plan_bbox_crop_batch(C.byref(d), C.byref(b), _lib.stream_ptr()), 'lfd_plan_bbox_crop_batch')
+
+
+def _torch():
+    import torch
+    return torch
+
+
+class ResidentDataLoader(object):
+    """DeviceDataLoader's contract over a ResidentDataset, with the whole per-batch plan made on the device
+    (csrc/batch_plan.hip): per batch the host launches lfd_plan_bbox_crop_batch and lfd_batch_assemble_f32 on the caller's
+    current stream, copies nothing (`last_h2d_bytes` is 0) and runs no worker threads.  Once per epoch `list(dataset_sampler)`
+    is uploaded as int32 [iterations, N].
+
+    Yields (image_batch, annotation_batch, meta_batch): image_batch fp32 [N, C_out, crop, crop] on the device,
+    annotation_batch a DeviceAnnotations (GraphedTrainStep, train_step and LFD.get_loss take it as it is; `.to_host()` gives
+    the reference's list), meta_batch the host list of the samples' metas.
+
+    region_sampler: this module's RandomBBoxCropRegionSampler, read for crop_size, resize_range and resize_prob only.  The
+    draws are NOT the reference's Mersenne Twister stream but the loader's own contract: Philox4x32-10 keyed by
+    `seed`, counter (slot, batch, epoch, j), words at fixed positions; batch (epoch, b) depends on nothing else.  Validation
+    batches (IdleRegionSampler) stay with DeviceDataLoader.
+
+    Lifetime: as DeviceDataLoader's -- image batches, annotations and `last_plan` come from rings of `out_buffers` slots taken in
+    draw order; a batch stays valid for work on the drawing stream until `out_buffers` more batches have been drawn."""
+
+    def __init__(self, resident_dataset, dataset_sampler, region_sampler, augmentation, seed, max_boxes=4096,
+                 max_boxes_per_image=None, out_buffers=2):
+        import torch
+        if not isinstance(region_sampler, RandomBBoxCropRegionSampler):
+            raise TypeError('ResidentDataLoader plans RandomBBoxCropRegionSampler (lfd_amd.data) on the device; '
+                            'other region samplers, IdleRegionSampler included, go through DeviceDataLoader')
+        if not isinstance(resident_dataset, ResidentDataset):
+            raise TypeError('ResidentDataLoader: a ResidentDataset (lfd_amd.data)')
+        if seed is None or not 0 <= int(seed) < 1 << 64:
+            raise ValueError('ResidentDataLoader: seed must be an int in [0, 2^64)')
+        if out_buffers < 1 or max_boxes < 1 or (max_boxes_per_image is not None and max_boxes_per_image < 1):
+            raise ValueError('out_buffers, max_boxes and max_boxes_per_image must be >= 1')
+        self._rds, self._dataset_sampler = resident_dataset, dataset_sampler
+        self._aug = augmentation or DeviceAugmentation()
+        self._crop = int(region_sampler._crop_size)
+        self._resize_range = (float(region_sampler._resize_range[0]), float(region_sampler._resize_range[1]))
+        self._resize_prob = float(region_sampler._resize_prob)
+        self._seed = int(seed)
+        self.max_boxes = int(max_boxes)
+        self.max_boxes_per_image = int(max_boxes if max_boxes_per_image is None else max_boxes_per_image)
+        self.device = resident_dataset.device
+        self._lut = torch.from_numpy(np.ascontiguousarray(self._aug.lut().reshape(-1))).to(self.device)
+        self._map = torch.tensor(self._aug.channel_map(resident_dataset.channels), dtype=torch.int32, device=self.device)
+        self._out = [None] * int(out_buffers)
+        self._ring = [None] * int(out_buffers)      # (PlanBuffers, DeviceAnnotations) per slot
+        self._drawn, self._epoch, self._active = 0, 0, None
+        self.last_h2d_bytes = 0
+        self.last_plan = None
+
+    def __len__(self):
+        return len(self._dataset_sampler)
+
+    @property
+    def batch_size(self):
+        return self._dataset_sampler.get_batch_size()
+
+    def draw(self, indices, epoch, batch_index):
+        """plans and assembles the batch (epoch, batch_index) over the device int32 row `indices` into the next ring slot:
+        -> (image_batch, DeviceAnnotations)"""
+        import torch
+        n, cs, c_out = int(indices.numel()), self._crop, self._aug.out_channels
+        k = self._drawn % len(self._out)
+        if self._ring[k] is None or self._ring[k][0].n != n:
+            self._ring[k] = (PlanBuffers(n, cs, self.max_boxes_per_image, self.device),
+                             DeviceAnnotations(n, self.max_boxes, self.device))
+            self._out[k] = torch.empty(n * c_out * cs * cs, dtype=torch.float32, device=self.device)
+        plan, ann = self._ring[k]
+        out = self._out[k].view(n, c_out, cs, cs)
+        with torch.cuda.device(self.device):
+            plan_bbox_crop_batch(self._rds, indices, self._seed, epoch, batch_index, cs, self._resize_range, self._resize_prob,
+                                 self._aug.flip_prob, plan, ann)
+            assemble(self._rds.store.arena, plan.desc, plan.coef, self._lut, self._map, n, self._rds.channels, c_out, cs, cs, out)
+        self._drawn += 1
+        self.last_plan, self.last_h2d_bytes = plan, 0
+        return out, ann
+
+    def __iter__(self):
+        if self._active is not None:
+            self._active.close()
+        self._active = self._epoch_batches(self._epoch)
+        self._epoch += 1
+        return self._active
+
+    def _epoch_batches(self, epoch):
+        import torch
+        rows = [list(map(int, r)) for r in self._dataset_sampler]
+        if not rows:
+            return
+        if any(len(r) != len(rows[0]) for r in rows):
+            raise ValueError('ResidentDataLoader: every batch of an epoch must have the same size')
+        table = torch.from_numpy(np.array(rows, dtype=np.int32)).to(self.device)      # the epoch's one upload
+        metas = self._rds.metas
+        for b, row in enumerate(rows):
+            out, ann = self.draw(table[b], epoch, b)
+            yield out, ann, [metas[i] for i in row]

@@ -25,6 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import engine, engine_p32, engine_sibling, ops, parallel, train_engine
+from ..data import DeviceAnnotations
 from .utils import multiclass_nms  # noqa: F401  (kept importable like the reference module)
 
 __all__ = ['LFD']
@@ -415,6 +416,18 @@ class LFD(nn.Module):
         """lfd.py:284-395.  Returns {'loss': Tensor, 'loss_values': {...floats}}."""
         pred_cls, pred_reg = predict_outputs
         dev = pred_cls.device
+        if isinstance(annotation_batch, DeviceAnnotations):
+            # annotations planned on the device (lfd_amd.data.ResidentDataLoader): the device-target route only
+            if not (dev.type == 'cuda' and self._fused_loss_supported(pred_cls)):
+                raise RuntimeError('LFD.get_loss: DeviceAnnotations need the device target route (a CUDA prediction and the '
+                                   'fused loss); pass annotation_batch.to_host() on the host route')
+            sizes = [self._head_indexes_to_feature_map_sizes[i] for i in range(self._num_heads)]
+            d, total = ops.make_assign_desc(len(annotation_batch), sizes, self._point_strides, self._regression_ranges,
+                                            self._gray_ranges, self._num_classes, self._range_assign_mode,
+                                            self._regression_loss_type == 'independent')
+            cls_t, reg_t = ops.assign_targets_device(d, total, self._num_classes, annotation_batch.boxes,
+                                                     annotation_batch.labels, annotation_batch.offsets)
+            return self._get_loss_fused(pred_cls, pred_reg, cls_t, reg_t)
         if dev.type == 'cuda' and self._fused_loss_supported(pred_cls):
             # device path end to end: annotations concatenated on the host and uploaded once, targets by
             # lfd_assign_targets_f32, loss by the fused get_loss kernels; no per-image tensors, one host sync

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from . import ops, optim, parallel, train_engine
+from .data import DeviceAnnotations
 
 
 class DynamicLossScale(object):
@@ -211,6 +212,19 @@ class GraphedTrainStep(object):
             self.x.copy_(image_batch)             # (fill `step.x` in place to save this copy)
         if len(annotation_batch) != self.x.size(0):
             raise RuntimeError('GraphedTrainStep: one annotation per image')
+        if isinstance(annotation_batch, DeviceAnnotations):
+            # already in this step's layout on the device (lfd_amd.data.ResidentDataLoader): no host work, no H2D copy
+            a = annotation_batch
+            if a.max_boxes == self.max_boxes:
+                self.ann.copy_(a.buffer)
+            elif a.max_boxes < self.max_boxes:
+                self.boxes[:a.max_boxes].copy_(a.boxes)
+                self.labels[:a.max_boxes].copy_(a.labels)
+                self.offs.copy_(a.offsets)
+            else:   # its offsets may point beyond this step's buffers
+                raise RuntimeError('GraphedTrainStep: DeviceAnnotations with max_boxes=%d, the step holds max_boxes=%d'
+                                   % (a.max_boxes, self.max_boxes))
+            return
         k = 0
         sg = self._stage[self._stage_i]
         self._stage_i = (self._stage_i + 1) % len(self._stage)

@@ -5,6 +5,8 @@ decoded images of WIDER FACE-like sizes (1024 wide, 400-1400 high, 1-20 boxes). 
   loader_store  : the loader alone over a DeviceImageStore (descriptors + tables only), batches/s
   fed           : GraphedTrainStep fed by the loader, ms per iteration
   fixed         : the same GraphedTrainStep on one fixed device batch (the ceiling), ms per iteration
+  resident      : ResidentDataLoader alone (the plan made on the device, csrc/batch_plan.hip; no per-batch copy), batches/s
+  fed_resident  : GraphedTrainStep fed by ResidentDataLoader (DeviceAnnotations), ms per iteration
 Each loader mode also reports the host-to-device bytes per batch.  Kernel time: run `--modes loader` under
 `rocprofv3 --kernel-trace --stats` in a run of its own.  Not the headline metric (bench.py is); recorded in DESIGN.md."""
 import argparse
@@ -56,6 +58,15 @@ def loader_for(ds, args, store=None):
                                  num_workers=args.workers, seed=1, store=store)
 
 
+def resident_loader_for(ds, args, holder):
+    if 'resident' not in holder:
+        holder['resident'] = data.ResidentDataset(ds, 'cuda', max_bytes=64 << 30)
+    return data.ResidentDataLoader(holder['resident'], Sampler(len(ds), args.batch, 0),
+                                   data.RandomBBoxCropRegionSampler(args.crop, (0.5, 1.5), 0.5),
+                                   data.DeviceAugmentation(flip_prob=0.5, normalize=data.SIMPLE_NORMALIZE), seed=1,
+                                   max_boxes=args.batch * 24)
+
+
 def batches(loader, count):
     """an endless stream of batches over repeated epochs"""
     while True:
@@ -92,12 +103,17 @@ def run(mode, args, ds, store_holder):
         dt, h2d = time_loader(loader_for(ds, args, store), args)
         out.update(batches_per_s=round(1.0 / dt, 2), ms_per_batch=round(dt * 1e3, 3), h2d_bytes_per_batch=int(h2d),
                    output_bytes_per_batch=args.batch * 3 * args.crop * args.crop * 4)
+    elif mode == 'resident':
+        dt, h2d = time_loader(resident_loader_for(ds, args, store_holder), args)
+        out.update(batches_per_s=round(1.0 / dt, 2), ms_per_batch=round(dt * 1e3, 3), h2d_bytes_per_batch=int(h2d),
+                   output_bytes_per_batch=args.batch * 3 * args.crop * args.crop * 4)
     else:
         torch.manual_seed(0)
         m = configs.build_model('WIDERFACE_LFD_S').cuda().train()
         opt = optim.SGD(m.parameters(), lr=0.01, momentum=0.9, weight_decay=1e-4)
         step = train.GraphedTrainStep(m, opt, dict(max_norm=10, norm_type=2), max_boxes=args.batch * 24)
-        it = batches(loader_for(ds, args), args.warmup + args.steps + 1)
+        feeder = resident_loader_for(ds, args, store_holder) if mode == 'fed_resident' else loader_for(ds, args)
+        it = batches(feeder, args.warmup + args.steps + 1)
         x0, ann0, _ = next(it)
         fixed_x = x0.clone()
         if mode == 'fixed':
@@ -113,6 +129,8 @@ def run(mode, args, ds, store_holder):
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
         out.update(ms_per_step=round(dt * 1e3, 3), images_per_s=round(args.batch / dt, 1), loss=lv['loss'])
+        if mode == 'fed_resident':
+            out.update(plan_status=feeder._ring[0][1].status())
     print(json.dumps(out), flush=True)
 
 
