@@ -1011,6 +1011,30 @@ LFD_API int lfd_head_out_grad_levels_f16(const void* y_concat, int32_t n, int64_
                                  int32_t nlevels, float loss_scale, void* dy_concat, void* workspace, size_t workspace_bytes,
                                  lfd_stream_t stream);
 
+/* The six entry points above for an output conv padded to `rows` output rows (csrc/head_out_wide.hip): `rows` is 64 or 128,
+ * anything else returns LFD_ERR_INVALID_ARGUMENT.  rows == 64 forwards to the entry point above of the same name; rows == 128
+ * serves heads whose level needs more than 64 rows (a merged head with 61..124 class channels + 4 regression rows, separate
+ * towers with up to 128 class channels): `y` / `dy` are [n, hw, 128] (`_concat` / `_levels`: [n, points_total, 128]) fp16, a
+ * segment must satisfy row0 + channels <= 128, and n * hw * 128 < 2^31.  Same values as the 64-row kernels compute for the
+ * same segments: out and dy are single roundings of the fp32 products, rows of dy outside every segment are zero, dbias / dscale
+ * accumulate through per-block partials and one fixed-order fp64 final launch.  `workspace` of the 128-row gradient entry
+ * points: >= 1 MB (1024 blocks x 2 x 128 floats), `_levels`: >= nlevels x 1 MB; lfd_train_workspace_bytes() covers both. */
+LFD_API int lfd_head_out_split_w_f16(const void* y, int32_t n, int32_t hw, int64_t points_total, int64_t point0,
+                             const lfd_head_out_seg_t* segs, int32_t nsegs, int32_t rows, lfd_stream_t stream);
+LFD_API int lfd_head_out_grad_w_f16(const void* y, int32_t n, int32_t hw, int64_t points_total, int64_t point0,
+                            const lfd_head_out_seg_t* segs, int32_t nsegs, int32_t rows, float loss_scale, void* dy,
+                            void* workspace, size_t workspace_bytes, lfd_stream_t stream);
+LFD_API int lfd_head_out_split_concat_w_f16(const void* y_concat, int32_t n, int32_t hw, int64_t points_total, int64_t point0,
+                                    const lfd_head_out_seg_t* segs, int32_t nsegs, int32_t rows, lfd_stream_t stream);
+LFD_API int lfd_head_out_grad_concat_w_f16(const void* y_concat, int32_t n, int32_t hw, int64_t points_total, int64_t point0,
+                                   const lfd_head_out_seg_t* segs, int32_t nsegs, int32_t rows, float loss_scale, void* dy_concat,
+                                   void* workspace, size_t workspace_bytes, lfd_stream_t stream);
+LFD_API int lfd_head_out_split_levels_w_f16(const void* y_concat, int32_t n, int64_t points_total, const lfd_head_out_level_t* levels,
+                                    int32_t nlevels, int32_t rows, lfd_stream_t stream);
+LFD_API int lfd_head_out_grad_levels_w_f16(const void* y_concat, int32_t n, int64_t points_total, const lfd_head_out_level_t* levels,
+                                   int32_t nlevels, int32_t rows, float loss_scale, void* dy_concat, void* workspace,
+                                   size_t workspace_bytes, lfd_stream_t stream);
+
 /* first stem conv (3 -> channels, 3x3 stride 2 pad 1, lfd_resnet.py:358,:378) on the NCHW fp32 image batch:
  * forward -> y NHWC fp16 (pre-norm), and its weight gradient (OIHW fp32); channels in {32, 64} */
 LFD_API int lfd_stem_conv0_train_fwd(const float* x_nchw, int32_t n, int32_t h, int32_t w, int32_t channels,

@@ -336,6 +336,13 @@ _SIGNATURES = {
     'lfd_stem_conv0_train_fwd': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),
     'lfd_head_out_split_f16': (C.c_int, [_P, _I32, _I32, _I64, _I64, C.POINTER(HeadOutSeg), _I32, _P]),
     'lfd_head_out_grad_f16': (C.c_int, [_P, _I32, _I32, _I64, _I64, C.POINTER(HeadOutSeg), _I32, _F, _P, _P, _SZ, _P]),
+    # ... for an output conv padded to `rows` in {64, 128} output rows (csrc/head_out_wide.hip; 64 forwards to the ones above)
+    'lfd_head_out_split_w_f16': (C.c_int, [_P, _I32, _I32, _I64, _I64, C.POINTER(HeadOutSeg), _I32, _I32, _P]),
+    'lfd_head_out_grad_w_f16': (C.c_int, [_P, _I32, _I32, _I64, _I64, C.POINTER(HeadOutSeg), _I32, _I32, _F, _P, _P, _SZ, _P]),
+    'lfd_head_out_split_concat_w_f16': (C.c_int, [_P, _I32, _I32, _I64, _I64, C.POINTER(HeadOutSeg), _I32, _I32, _P]),
+    'lfd_head_out_grad_concat_w_f16': (C.c_int, [_P, _I32, _I32, _I64, _I64, C.POINTER(HeadOutSeg), _I32, _I32, _F, _P, _P, _SZ, _P]),
+    'lfd_head_out_split_levels_w_f16': (C.c_int, [_P, _I32, _I64, C.POINTER(HeadOutLevel), _I32, _I32, _P]),
+    'lfd_head_out_grad_levels_w_f16': (C.c_int, [_P, _I32, _I64, C.POINTER(HeadOutLevel), _I32, _I32, _F, _P, _P, _SZ, _P]),
     'lfd_stem_conv0_train_fwd_bn_stats': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _F, _F, _P, _P, _P, _SZ, _P, _P]),
     'lfd_stem_conv0_wgrad': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _SZ, _P, _P]),
     'lfd_stem_conv0_bn_bwd_wgrad': (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _I32, _P, _SZ, _P, _P, _P, _P]),

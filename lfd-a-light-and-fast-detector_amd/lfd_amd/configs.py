@@ -90,15 +90,20 @@ def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, io
     return model
 
 
-def build_model(name_or_arch, seed=666, input_channels=3):
+def build_model(name_or_arch, seed=666, input_channels=3, num_classes=None):
     """This package's LFD for a named configuration; input_channels=1 builds its grayscale twin (same ARCHS entry, a
-    one-channel first stem conv)."""
+    one-channel first stem conv); num_classes=K the same configuration with a K-class head (the task scripts' `num_classes`,
+    WIDERFACE_LFD_S.py:79 -- 80 for a COCO parser)."""
     from .model.backbone import LFDResNet
     from .model.head import LFDHead
     from .model.lfd import LFD
     from .model.losses import CrossEntropyLoss, FocalLoss, IoULoss, QualityFocalLoss
     from .model.neck import SimpleNeck
     arch = ARCHS[name_or_arch] if isinstance(name_or_arch, str) else name_or_arch
+    if num_classes is not None:
+        if int(num_classes) < 1:
+            raise ValueError('num_classes must be >= 1')
+        arch = dict(arch, num_classes=int(num_classes))
     return build_modules(arch, LFDResNet, SimpleNeck, LFDHead, LFD, FocalLoss, IoULoss, CrossEntropyLoss, seed, QualityFocalLoss,
                          input_channels=input_channels)
 

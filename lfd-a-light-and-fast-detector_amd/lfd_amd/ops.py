@@ -1346,26 +1346,45 @@ def _head_out_segs(segs, field, tensors):
     return arr
 
 
+def _head_out_rows(y, what):
+    """output rows of the padded conv whose output `y` is: 64 (csrc/head_out.hip) or 128 (csrc/head_out_wide.hip)"""
+    rows = y.size(-1)
+    if rows not in (64, 128):
+        raise RuntimeError('%s: 64 or 128 output rows expected, got %d' % (what, rows))
+    return rows
+
+
 def head_out_split_concat(y_concat, hw, segs, outs, point0):
-    """head_out_split for a level whose conv output is rows [point0, point0 + hw) of every image of y_concat [n, P, 64]"""
+    """head_out_split for a level whose conv output is rows [point0, point0 + hw) of every image of y_concat [n, P, 64 | 128]"""
     require_cuda(y_concat, 'head_out_split_concat')
     n = y_concat.size(0)
+    rows = _head_out_rows(y_concat, 'head_out_split_concat')
     arr = _head_out_segs(segs, 'out', outs)
     with torch.cuda.device(y_concat.device):
-        check(lib().lfd_head_out_split_concat_f16(ptr(y_concat), n, int(hw), outs[0].size(1), int(point0), arr, len(segs),
-                                                  stream_ptr()), 'lfd_head_out_split_concat_f16')
+        if rows == 64:
+            check(lib().lfd_head_out_split_concat_f16(ptr(y_concat), n, int(hw), outs[0].size(1), int(point0), arr, len(segs),
+                                                      stream_ptr()), 'lfd_head_out_split_concat_f16')
+        else:
+            check(lib().lfd_head_out_split_concat_w_f16(ptr(y_concat), n, int(hw), outs[0].size(1), int(point0), arr, len(segs),
+                                                        rows, stream_ptr()), 'lfd_head_out_split_concat_w_f16')
 
 
 def head_out_grad_concat(y_concat, hw, segs, grads, point0, loss_scale, dy_concat):
-    """head_out_grad writing the level's rows of dy_concat [n, P, 64]; accumulates dbias / dscale of the segments"""
+    """head_out_grad writing the level's rows of dy_concat [n, P, 64 | 128]; accumulates dbias / dscale of the segments"""
     require_cuda(y_concat, 'head_out_grad_concat')
     n = y_concat.size(0)
+    rows = _head_out_rows(y_concat, 'head_out_grad_concat')
     arr = _head_out_segs(segs, 'grad', grads)
-    ws = train_workspace(y_concat.device)
+    ws = train_workspace(y_concat.device)       # (covers the 1 MB per level of the 128-row partials too)
     with torch.cuda.device(y_concat.device):
-        check(lib().lfd_head_out_grad_concat_f16(ptr(y_concat), n, int(hw), grads[0].size(1), int(point0), arr, len(segs),
-                                                 float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
-              'lfd_head_out_grad_concat_f16')
+        if rows == 64:
+            check(lib().lfd_head_out_grad_concat_f16(ptr(y_concat), n, int(hw), grads[0].size(1), int(point0), arr, len(segs),
+                                                     float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
+                  'lfd_head_out_grad_concat_f16')
+        else:
+            check(lib().lfd_head_out_grad_concat_w_f16(ptr(y_concat), n, int(hw), grads[0].size(1), int(point0), arr, len(segs),
+                                                       rows, float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
+                  'lfd_head_out_grad_concat_w_f16')
 
 
 def _head_out_levels(levels, field):
@@ -1381,50 +1400,65 @@ def _head_out_levels(levels, field):
 
 def head_out_split_levels(y_concat, levels):
     """head_out_split_concat for ALL pyramid levels of one output conv in one launch; levels: [(hw, point0, segs, outs)]
-    (lfd_head_out_split_levels_f16; bit-identical to the per-level calls)"""
+    (lfd_head_out_split_levels_f16, 128 rows: lfd_head_out_split_levels_w_f16; bit-identical to the per-level calls)"""
     require_cuda(y_concat, 'head_out_split_levels')
+    rows = _head_out_rows(y_concat, 'head_out_split_levels')
     arr = _head_out_levels(levels, 'out')
     with torch.cuda.device(y_concat.device):
-        check(lib().lfd_head_out_split_levels_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
-                                                  stream_ptr()), 'lfd_head_out_split_levels_f16')
+        if rows == 64:
+            check(lib().lfd_head_out_split_levels_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
+                                                      stream_ptr()), 'lfd_head_out_split_levels_f16')
+        else:
+            check(lib().lfd_head_out_split_levels_w_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
+                                                        rows, stream_ptr()), 'lfd_head_out_split_levels_w_f16')
 
 
 def head_out_grad_levels(y_concat, levels, loss_scale, dy_concat):
     """head_out_grad_concat for ALL pyramid levels in one launch (+ one final launch): levels: [(hw, point0, segs, grads)], segs
-    with their dbias / dscale targets (lfd_head_out_grad_levels_f16; bit-identical to the per-level calls)"""
+    with their dbias / dscale targets (lfd_head_out_grad_levels_f16, 128 rows: lfd_head_out_grad_levels_w_f16; bit-identical to
+    the per-level calls)"""
     require_cuda(y_concat, 'head_out_grad_levels')
+    rows = _head_out_rows(y_concat, 'head_out_grad_levels')
     arr = _head_out_levels(levels, 'grad')
     ws = train_workspace(y_concat.device)
     with torch.cuda.device(y_concat.device):
-        check(lib().lfd_head_out_grad_levels_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
-                                                 float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
-              'lfd_head_out_grad_levels_f16')
+        if rows == 64:
+            check(lib().lfd_head_out_grad_levels_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
+                                                     float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
+                  'lfd_head_out_grad_levels_f16')
+        else:
+            check(lib().lfd_head_out_grad_levels_w_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
+                                                       rows, float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
+                  'lfd_head_out_grad_levels_w_f16')
 
 
 def head_out_split(y, segs, outs, point0):
-    """y [n,h,w,64] fp16 (a level's padded output conv) -> outs[i][:, point0:point0+h*w, :] = float(y[..., rows of segment i])
-    (* scale); outs[i]: the level-concatenated [n, P, channels] fp32 tensors.  segs: dicts channels, row0, scale (tensor or
-    None).  (lfd_head_out_split_f16)"""
+    """y [n,h,w,64 | 128] fp16 (a level's padded output conv) -> outs[i][:, point0:point0+h*w, :] = float(y[..., rows of segment
+    i]) (* scale); outs[i]: the level-concatenated [n, P, channels] fp32 tensors.  segs: dicts channels, row0, scale (tensor or
+    None).  (lfd_head_out_split_f16; 128 rows: lfd_head_out_split_w_f16)"""
     _nhwc16(y, 'head_out_split')
     n, h, w_, rows = y.shape
-    if rows != 64:
-        raise RuntimeError('head_out_split: 64 output rows expected')
+    _head_out_rows(y, 'head_out_split')
     for sg, o in zip(segs, outs):
         if o.dtype != torch.float32 or not o.is_contiguous() or o.size(0) != n or o.size(2) != sg['channels']:
             raise RuntimeError('head_out_split: outs must be contiguous fp32 [n, P, channels]')
     arr = _head_out_segs(segs, 'out', outs)
     with torch.cuda.device(y.device):
-        check(lib().lfd_head_out_split_f16(ptr(y), n, h * w_, outs[0].size(1), int(point0), arr, len(segs), stream_ptr()),
-              'lfd_head_out_split_f16')
+        if rows == 64:
+            check(lib().lfd_head_out_split_f16(ptr(y), n, h * w_, outs[0].size(1), int(point0), arr, len(segs), stream_ptr()),
+                  'lfd_head_out_split_f16')
+        else:
+            check(lib().lfd_head_out_split_w_f16(ptr(y), n, h * w_, outs[0].size(1), int(point0), arr, len(segs), rows,
+                                                 stream_ptr()), 'lfd_head_out_split_w_f16')
 
 
 def head_out_grad(y, segs, grads, point0, loss_scale):
-    """-> dy [n,h,w,64] fp16 = grads[i][:, point0:point0+h*w, :] (* scale) * loss_scale in the rows of segment i, zero
-    elsewhere; accumulates segs[i]['dbias'] / ['dscale'] (fp32 tensors or None) in place.  (lfd_head_out_grad_f16)"""
+    """-> dy [n,h,w,64 | 128] fp16 = grads[i][:, point0:point0+h*w, :] (* scale) * loss_scale in the rows of segment i, zero
+    elsewhere; accumulates segs[i]['dbias'] / ['dscale'] (fp32 tensors or None) in place.  (lfd_head_out_grad_f16; 128 rows:
+    lfd_head_out_grad_w_f16)"""
     _nhwc16(y, 'head_out_grad')
     n, h, w_, rows = y.shape
-    if rows != 64:
-        raise RuntimeError('head_out_grad: 64 output rows expected')
+    _head_out_rows(y, 'head_out_grad')
     for sg, g in zip(segs, grads):
         if g.dtype != torch.float32 or not g.is_contiguous() or g.size(0) != n or g.size(2) != sg['channels']:
             raise RuntimeError('head_out_grad: grads must be contiguous fp32 [n, P, channels]')
@@ -1436,8 +1470,13 @@ def head_out_grad(y, segs, grads, point0, loss_scale):
     ws = train_workspace(y.device)
     with torch.cuda.device(y.device):
         dy = torch.empty_like(y)
-        check(lib().lfd_head_out_grad_f16(ptr(y), n, h * w_, grads[0].size(1), int(point0), arr, len(segs), float(loss_scale),
-                                          ptr(dy), ptr(ws), ws.numel(), stream_ptr()), 'lfd_head_out_grad_f16')
+        if rows == 64:
+            check(lib().lfd_head_out_grad_f16(ptr(y), n, h * w_, grads[0].size(1), int(point0), arr, len(segs), float(loss_scale),
+                                              ptr(dy), ptr(ws), ws.numel(), stream_ptr()), 'lfd_head_out_grad_f16')
+        else:
+            check(lib().lfd_head_out_grad_w_f16(ptr(y), n, h * w_, grads[0].size(1), int(point0), arr, len(segs), rows,
+                                                float(loss_scale), ptr(dy), ptr(ws), ws.numel(), stream_ptr()),
+                  'lfd_head_out_grad_w_f16')
     return dy
 
 

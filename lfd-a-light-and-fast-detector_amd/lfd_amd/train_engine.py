@@ -87,7 +87,13 @@ def check_train_input(backbone, x):
 
 
 def network_supported(model):
-    """+ SimpleNeck with BatchNorm2d, LFDHead with 1x1 convs and GroupNorm groups of 8 channels, <= 60 output channels."""
+    """+ SimpleNeck with BatchNorm2d, LFDHead with 1x1 convs and GroupNorm groups of 8 channels, and output convs that fit the
+    padded 1x1 conv of a level (_out_weight: 64 or 128 rows, csrc/head_out.hip / head_out_wide.hip):
+      - cls and reg conv reading the same activation (merge_path_flag, or no tower layers) run as ONE conv:
+        num_cls_channels + 4 <= 128  (<= 60: the 64-row kernels; 61..124: the 128-row ones)
+      - separate towers, one conv each: num_cls_channels <= 128
+    The convs on both sides exist for every admitted shape: forward {64, 128} -> {64, 128} rows and data gradient
+    {64, 128} rows -> {64, 128} channels are instances of csrc/conv.hip, the weight gradient tiles any multiple of 64."""
     bb, neck, head = model._backbone, model._neck, model._head
     if type(neck).__name__ != 'SimpleNeck' or type(head).__name__ != 'LFDHead':
         return False          # FPN / SimpleFPN necks, LFDHeadV1, FCOSHead: PyTorch-ROCm autograd behind the HIP backbone
@@ -112,7 +118,8 @@ def network_supported(model):
             return False
         if isinstance(m, nn.Conv2d) and not _conv_ok(m):
             return False
-    return head.num_cls_channels + 4 <= 64
+    one_conv = head._merge_path_flag or head._num_conv_layers == 0
+    return head.num_cls_channels + (4 if one_conv else 0) <= 128
 
 
 class _Builder(object):
@@ -401,7 +408,7 @@ def backward(units, saved, grads, scale=None, store=None, trace=None):
 # ---------------------------------------------------------------------------------------------- output convs
 def _out_weight(o):
     """rows of the level's output convs concatenated and zero-padded to 64 (the narrowest 1x1 conv shape instantiated
-    for 128 input channels, forward and data gradient): [64, C, 1, 1], bias [64]"""
+    for 128 input channels, forward and data gradient) or, above 64 rows, to 128: [rows, C, 1, 1], bias [rows]"""
     w = torch.cat([c.weight.detach() for _, c in o.convs], 0)
     bias = torch.cat([c.bias.detach() for _, c in o.convs], 0)
     rows = -(-w.size(0) // 64) * 64
@@ -606,7 +613,8 @@ def _sched(plan_owner, dev):
 
 
 def _out_packs(sc, outs):
-    """{ids of a level's output convs: (padded weight [64, C, 1, 1], padded bias [64], forward pack, data-gradient pack)}: the
+    """{ids of a level's output convs: (padded weight [rows, C, 1, 1], padded bias [rows], forward pack, data-gradient pack), rows
+    64 or 128}: the
     rows of the convs are gathered into persistent zero-padded buffers by ONE launch (lfd_rows_sum_batched_f32 with one source
     row = a batched copy), then packed; shared heads: once for all levels"""
     cache, jobs = {}, []

@@ -1,5 +1,7 @@
 """Training-step timing (BASELINE.json configs[4]: WIDERFACE_LFD_S, synthetic 640x640, bs 32 per GPU): forward, fused
-get_loss, backward, gradient clipping + SGD.  --input-channels 1 times the model's grayscale twin on [N,1,H,W] batches.
+get_loss, backward, gradient clipping + SGD.  --input-channels 1 times the model's grayscale twin on [N,1,H,W] batches;
+--num-classes K the configuration with a K-class head (80: a COCO-sized head, the 128-row output convs) and box labels of
+all K classes.
 Prints one JSON line per mode:
   hip   : the whole network on the hand-written kernels (train_engine) + fused loss + flat SGD
   graph : the same iteration replayed as one HIP graph (lfd_amd.train.GraphedTrainStep)
@@ -18,12 +20,13 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'
 from lfd_amd import configs, optim, train  # noqa: E402
 
 
-def annotations(rng, n, hw, k=6):
+def annotations(rng, n, hw, k=6, num_classes=1):
     ann = []
     for _ in range(n):
         wh = np.exp(rng.uniform(np.log(8), np.log(200), (k, 2)))
         xy = rng.uniform(0, 1, (k, 2)) * (np.array([hw[1], hw[0]]) - wh).clip(1)
-        ann.append((np.concatenate([xy, wh], 1).astype(np.float32), np.zeros(k, np.int64)))
+        labels = rng.integers(0, num_classes, k).astype(np.int64) if num_classes > 1 else np.zeros(k, np.int64)
+        ann.append((np.concatenate([xy, wh], 1).astype(np.float32), labels))
     return ann
 
 
@@ -32,12 +35,12 @@ def run(mode, args):
     os.environ['LFD_HIP_TRAIN'] = '1' if hip else '0'
     os.environ['LFD_FUSED_LOSS'] = '1' if hip else '0'
     torch.manual_seed(0)
-    m = configs.build_model(args.model, input_channels=args.input_channels).cuda().train()
+    m = configs.build_model(args.model, input_channels=args.input_channels, num_classes=args.num_classes).cuda().train()
     kw = dict(lr=0.01, momentum=0.9, weight_decay=1e-4)
     opt = optim.SGD(m.parameters(), **kw) if hip else torch.optim.SGD(m.parameters(), **kw)
     rng = np.random.default_rng(0)
     x = torch.randn(args.batch, args.input_channels, args.size, args.size, device='cuda')
-    ann = annotations(rng, args.batch, (args.size, args.size))
+    ann = annotations(rng, args.batch, (args.size, args.size), num_classes=m._num_classes)
     clip = dict(max_norm=10, norm_type=2)
     if mode == 'graph':
         gstep = train.GraphedTrainStep(m, opt, clip, max_boxes=args.batch * 8)
@@ -52,9 +55,9 @@ def run(mode, args):
         lv, _ = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
-    print(json.dumps(dict(mode=mode, model=args.model, input_channels=args.input_channels, batch=args.batch, size=args.size, ms_per_step=round(dt * 1e3, 3),
-                          images_per_s=round(args.batch / dt, 1), loss=lv['loss'],
-                          peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))))
+    print(json.dumps(dict(mode=mode, model=args.model, num_classes=m._num_classes, input_channels=args.input_channels,
+                          batch=args.batch, size=args.size, ms_per_step=round(dt * 1e3, 3), images_per_s=round(args.batch / dt, 1),
+                          loss=lv['loss'], peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))))
 
 
 if __name__ == '__main__':
@@ -66,6 +69,7 @@ if __name__ == '__main__':
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--modes', default='hip,torch')
     ap.add_argument('--input-channels', type=int, default=3, choices=(1, 3), help='3: RGB, 1: the grayscale twin')
+    ap.add_argument('--num-classes', type=int, default=None, help='classes of the head (default: the configuration\'s own)')
     ap.add_argument('--concat', type=int, default=-1, help='train_engine.CONCAT_HEAD: 1 = shared head towers once over all pyramid '
                     'levels, 0 = level by level (default: the module\'s setting)')
     a = ap.parse_args()
