@@ -15,19 +15,17 @@
 // runs one workgroup per (category, area range, max_dets entry, threshold) backwards over its category: suffix sums give
 // tp / fp at every position, a suffix maximum the precision envelope, and each position that raises recall writes the
 // recall points it is the first to reach.
-#include "common.h"
+#include "eval_store.h"
 
 namespace {
 
-constexpr int EV_THREADS = 256;
-constexpr int EV_SCAN_THREADS = 1024;
+constexpr int EV_THREADS = ES_THREADS;
+constexpr int EV_SCAN_THREADS = ES_SCAN_THREADS;
 constexpr int EV_GT_TILE = 64;
 constexpr int EV_DPS = EV_THREADS / EV_GT_TILE;   // detections per IoU tile
 constexpr int EV_RX_ITEMS = 8;
 constexpr int EV_RX_TILE = EV_THREADS * EV_RX_ITEMS;
 constexpr int EV_MATCH_GRID = 4096;
-
-typedef unsigned long long u64;
 
 struct EvArgs {
   lfd_eval_bufs_t b;
@@ -46,28 +44,11 @@ struct EvArgs {
   int rx_blocks;
 };
 
-struct OpAdd { __device__ u64 operator()(u64 x, u64 y) const { return x + y; } };
-struct OpMax { __device__ double operator()(double x, double y) const { return fmax(x, y); } };
-
-// inclusive Hillis-Steele scan over the workgroup, s: [2 * NT]
-template <typename T, int NT, typename Op>
-__device__ __forceinline__ T ev_block_scan(T v, T* s, Op op) {
-  const int t = threadIdx.x;
-  int cur = 0;
-  s[t] = v;
-  __syncthreads();
-#pragma unroll 1
-  for (int off = 1; off < NT; off <<= 1) {
-    T x = s[cur * NT + t];
-    if (t >= off) x = op(s[cur * NT + t - off], x);
-    s[(cur ^ 1) * NT + t] = x;
-    cur ^= 1;
-    __syncthreads();
-  }
-  const T r = s[cur * NT + t];
-  __syncthreads();
-  return r;
+__host__ __device__ __forceinline__ EsStore ev_store(const EvArgs& a) {
+  return EsStore{a.b.det_box, a.b.det_score, a.b.det_img, a.b.det_cat, a.b.state, a.b.img_mask, a.I, a.K, a.cap};
 }
+
+struct OpMax { __device__ double operator()(double x, double y) const { return fmax(x, y); } };
 
 // scores: -0.0 counts as 0.0, NaN as -inf (a total order, whatever the input)
 __device__ __forceinline__ double ev_score(double s) {
@@ -81,101 +62,40 @@ __device__ __forceinline__ u64 ev_desc_key(double s) {
   return ~ord;
 }
 
-// ------------------------------------------------------------------ appends
-__global__ __launch_bounds__(EV_THREADS) void k_append_dets(EvArgs a, const float* dets, const int32_t* labels, const int32_t* counts,
-                                                            int n, int cap, const int32_t* label_map, int num_labels,
-                                                            const int32_t* img_ord, int mark_all) {
-  __shared__ long long s_base;
-  const int i = blockIdx.x;
-  if (threadIdx.x == 0) {
-    long long base = a.b.state[0];
-    for (int j = 0; j < i; ++j) base += min(max(counts[j * 4 + 1], 0), cap);
-    s_base = base;
+// ------------------------------------------------------------------ appends (the frame is eval_store.h)
+struct EvDets : EsDetsDefaults {   // a bad ordinal: LFD_EVAL_ERR_IMAGE whether or not the entry fits, and nothing is written
+  const int32_t* label_map;
+  int num_labels, mark_all;
+  __device__ bool marks(int c, bool fits) const { return fits && (mark_all || c > 0); }   // after the capacity test
+  __device__ void row(const EsStore& s, long long o, int ord, float x1, float y1, float w, float h, float score, int lab) const {
+    es_put(s, o, (double)x1, (double)y1, (double)w, (double)h, (double)score, ord);   // {x, y, w, h}, the score as is
+    s.det_cat[o] = es_label_category(s, label_map, num_labels, lab);
   }
-  __syncthreads();
-  const long long base = s_base;
-  const int c = min(max(counts[i * 4 + 1], 0), cap);
-  const int ord = img_ord[i];
-  if (ord < 0 || ord >= a.I) {
-    if (threadIdx.x == 0) atomicOr(&a.b.state[1], LFD_EVAL_ERR_IMAGE);
-    return;
-  }
-  if (base + c > a.cap) return;   // k_append_commit raises LFD_EVAL_ERR_CAPACITY
-  if (threadIdx.x == 0 && (mark_all || c > 0)) a.b.img_mask[ord] = 1;
-  for (int j = threadIdx.x; j < c; j += EV_THREADS) {
-    const float* d = dets + ((long long)i * cap + j) * 5;
-    const float x1 = d[0], y1 = d[1];
-    const float w = d[2] - x1 + 1.0f, h = d[3] - y1 + 1.0f;
-    const long long o = base + j;
-    a.b.det_box[o * 4 + 0] = (double)x1;
-    a.b.det_box[o * 4 + 1] = (double)y1;
-    a.b.det_box[o * 4 + 2] = (double)w;
-    a.b.det_box[o * 4 + 3] = (double)h;
-    a.b.det_score[o] = (double)d[4];
-    a.b.det_img[o] = ord;
-    const int lab = labels[(long long)i * cap + j];
-    const int cat = (lab >= 0 && lab < num_labels) ? label_map[lab] : -1;
-    if (cat < 0 || cat >= a.K) atomicOr(&a.b.state[1], LFD_EVAL_ERR_LABEL);
-    a.b.det_cat[o] = (cat >= 0 && cat < a.K) ? cat : -1;
-  }
-}
+};
 
-__global__ void k_append_commit_dets(EvArgs a, const int32_t* counts, int n, int cap) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  long long total = 0;
-  for (int j = 0; j < n; ++j) total += min(max(counts[j * 4 + 1], 0), cap);
-  if ((long long)a.b.state[0] + total > a.cap) atomicOr(&a.b.state[1], LFD_EVAL_ERR_CAPACITY);
-  else a.b.state[0] += (int)total;
-}
-
-__global__ __launch_bounds__(EV_THREADS) void k_append_rows(EvArgs a, const double* rows, long long m, const int32_t* mark, int num_mark) {
-  const long long base = a.b.state[0];
-  const long long stride = (long long)gridDim.x * EV_THREADS;
-  const long long t0 = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
-  for (long long j = t0; j < num_mark; j += stride) {
-    const int ord = mark[j];
-    if (ord >= 0 && ord < a.I) a.b.img_mask[ord] = 1;
-    else atomicOr(&a.b.state[1], LFD_EVAL_ERR_IMAGE);
+struct EvRows {
+  static constexpr int kCols = 7;   // ordinal, category, score, x, y, w, h
+  __device__ void row(const EsStore& s, long long o, const double* r, int ord, bool bad) const {
+    const int cat = (int)r[1];
+    es_put(s, o, r[3], r[4], r[5], r[6], r[2], bad ? 0 : ord);   // a bad ordinal: image 0 with no category
+    s.det_cat[o] = (!bad && cat >= 0 && cat < s.K) ? cat : -1;   // a category out of range: -1, silently
   }
-  if (base + m > a.cap) return;   // k_append_commit_rows raises LFD_EVAL_ERR_CAPACITY
-  for (long long j = t0; j < m; j += stride) {
-    const double* r = rows + j * 7;
-    const long long o = base + j;
-    int ord = (int)r[0], cat = (int)r[1];
-    if (ord < 0 || ord >= a.I) {
-      atomicOr(&a.b.state[1], LFD_EVAL_ERR_IMAGE);
-      ord = 0;
-      cat = -1;
-    } else {
-      a.b.img_mask[ord] = 1;
-    }
-    a.b.det_img[o] = ord;
-    a.b.det_cat[o] = (cat >= 0 && cat < a.K) ? cat : -1;
-    a.b.det_score[o] = r[2];
-    a.b.det_box[o * 4 + 0] = r[3];
-    a.b.det_box[o * 4 + 1] = r[4];
-    a.b.det_box[o * 4 + 2] = r[5];
-    a.b.det_box[o * 4 + 3] = r[6];
-  }
-}
-
-__global__ void k_append_commit_rows(EvArgs a, long long m) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  if ((long long)a.b.state[0] + m > a.cap) atomicOr(&a.b.state[1], LFD_EVAL_ERR_CAPACITY);
-  else a.b.state[0] += (int)m;
-}
+};
 
 // ------------------------------------------------------------------ stage 1: grouping
-__device__ __forceinline__ int ev_pair_of(const EvArgs& a, int d) {
-  const int img = a.b.det_img[d], cat = a.b.det_cat[d];
-  if (img < 0 || img >= a.I || cat < 0 || cat >= a.K || !a.b.img_mask[img]) return -1;
-  return img * a.K + cat;
-}
+struct EvPairKey {
+  __device__ int operator()(const EsStore& s, int d) const {
+    const int img = s.det_img[d], cat = s.det_cat[d];
+    if (img < 0 || img >= s.I || cat < 0 || cat >= s.K || !s.img_mask[img]) return -1;
+    return img * s.K + cat;
+  }
+};
 
 __global__ __launch_bounds__(EV_THREADS) void k_count(EvArgs a) {
+  const EsStore s = ev_store(a);
   const int n = min(a.b.state[0], a.cap);
   for (int d = blockIdx.x * EV_THREADS + threadIdx.x; d < n; d += gridDim.x * EV_THREADS) {
-    const int p = ev_pair_of(a, d);
+    const int p = EvPairKey()(s, d);
     if (p < 0) continue;
     atomicAdd(&a.cnt[p], 1);
     atomicAdd(&a.cat_cnt[p % a.K], 1);
@@ -222,16 +142,6 @@ __global__ __launch_bounds__(EV_SCAN_THREADS) void k_pair_scan(EvArgs a) {
     krun += (u64)a.cat_cnt[k];
   }
   if (t == EV_SCAN_THREADS - 1) a.b.cat_start[a.K] = (int)kinc;
-}
-
-__global__ __launch_bounds__(EV_THREADS) void k_scatter(EvArgs a) {
-  const int n = min(a.b.state[0], a.cap);
-  for (int d = blockIdx.x * EV_THREADS + threadIdx.x; d < n; d += gridDim.x * EV_THREADS) {
-    const int p = ev_pair_of(a, d);
-    if (p < 0) continue;
-    const int slot = a.start[p] + atomicAdd(&a.fill[p], 1);
-    if (slot < a.start[p + 1] && slot < a.cap) a.members[slot] = d;
-  }
 }
 
 // ------------------------------------------------------------------ stage 1: rank + match
@@ -616,8 +526,6 @@ size_t ev_carve_acc(EvArgs& a, void* ws) {
   return c.used();
 }
 
-int ev_grid(long long items) { return (int)max(1LL, min((items + EV_THREADS - 1) / EV_THREADS, 2048LL)); }
-
 bool ev_store_ok(const lfd_eval_bufs_t* b) {
   return b && b->det_box && b->det_score && b->det_img && b->det_cat && b->state && b->img_mask;
 }
@@ -632,14 +540,11 @@ int lfd_eval_append_dets_f32(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t*
   if (!ev_desc_ok(desc) || !ev_store_ok(bufs) || !dets || !labels || !counts || !label_map || !img_ord) return LFD_ERR_INVALID_ARGUMENT;
   if (n < 1 || cap < 1 || num_labels < 1) return LFD_ERR_INVALID_ARGUMENT;
   if (!ev_desc_supported(desc) || n > 65535) return LFD_ERR_UNSUPPORTED;
-  const EvArgs a = ev_args(desc, bufs);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_append_dets, dim3(n), dim3(EV_THREADS), 0, st, a, dets, labels, counts, n, cap, label_map, num_labels, img_ord,
-                     mark_all);
-  LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_append_commit_dets, dim3(1), dim3(64), 0, st, a, counts, n, cap);
-  LFD_CHECK_LAUNCH();
-  return LFD_OK;
+  EvDets p;
+  p.label_map = label_map;
+  p.num_labels = num_labels;
+  p.mark_all = mark_all;
+  return es_append_dets(ev_store(ev_args(desc, bufs)), p, dets, labels, counts, n, cap, img_ord, 0, stream);
 }
 
 int lfd_eval_append_rows_f64(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t* bufs, const double* rows, int64_t m,
@@ -648,14 +553,7 @@ int lfd_eval_append_rows_f64(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t*
   if ((m > 0 && !rows) || (num_mark > 0 && !mark)) return LFD_ERR_INVALID_ARGUMENT;
   if (!ev_desc_supported(desc)) return LFD_ERR_UNSUPPORTED;
   if (m == 0 && num_mark == 0) return LFD_OK;
-  const EvArgs a = ev_args(desc, bufs);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_append_rows, dim3(ev_grid(max((long long)m, (long long)num_mark))), dim3(EV_THREADS), 0, st, a, rows,
-                     (long long)m, mark, num_mark);
-  LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_append_commit_rows, dim3(1), dim3(64), 0, st, a, (long long)m);
-  LFD_CHECK_LAUNCH();
-  return LFD_OK;
+  return es_append_rows(ev_store(ev_args(desc, bufs)), EvRows(), rows, (long long)m, mark, num_mark, stream);
 }
 
 size_t lfd_eval_match_workspace_bytes(const lfd_eval_desc_t* desc) {
@@ -679,11 +577,11 @@ int lfd_eval_match(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t* bufs, voi
   const size_t P = (size_t)a.I * a.K;
   if (hipMemsetAsync(a.cnt, 0, (2 * P + a.K) * sizeof(int), st) != hipSuccess) return LFD_ERR_LAUNCH_FAILED;
   if (hipMemsetAsync(a.b.npig, 0, (size_t)a.K * a.A * sizeof(int), st) != hipSuccess) return LFD_ERR_LAUNCH_FAILED;
-  hipLaunchKernelGGL(k_count, dim3(ev_grid(a.cap)), dim3(EV_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_count, dim3(es_grid(a.cap)), dim3(EV_THREADS), 0, st, a);
   LFD_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(EV_SCAN_THREADS), 0, st, a);
   LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_scatter, dim3(ev_grid(a.cap)), dim3(EV_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_es_scatter<EvPairKey>, dim3(es_grid(a.cap)), dim3(EV_THREADS), 0, st, ev_store(a), a.start, a.fill, a.members);
   LFD_CHECK_LAUNCH();
   const long long pairs_max = min((long long)P, (long long)a.cap + a.G);
   hipLaunchKernelGGL(k_match, dim3((unsigned)max(1LL, min(pairs_max, (long long)EV_MATCH_GRID))), dim3(EV_THREADS), 0, st, a);
@@ -708,7 +606,7 @@ int lfd_eval_accumulate(const lfd_eval_desc_t* desc, const lfd_eval_bufs_t* bufs
   EvArgs a = ev_args(desc, bufs);
   if (ev_carve_acc(a, workspace) > workspace_bytes) return LFD_ERR_WORKSPACE_TOO_SMALL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_rx_init, dim3(ev_grid(a.cap)), dim3(EV_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_rx_init, dim3(es_grid(a.cap)), dim3(EV_THREADS), 0, st, a);
   LFD_CHECK_LAUNCH();
   // 8 passes over the score key, then the category index (nothing to sort by with one category)
   const int cat_passes = a.K <= 1 ? 0 : (a.K <= 256 ? 1 : 2);

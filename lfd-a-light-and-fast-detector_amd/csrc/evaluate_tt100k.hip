@@ -3,9 +3,10 @@
 // reference's TT100K_train/official_eval.py: everything is float64 and evaluated as the definition writes it (the library
 // is built with -ffp-contract=off and fp64 division is correctly rounded, so an IoU that is computed twice has the same bits).
 //
-// The detection store has evaluate.hip's layout (boxes are {xmin, ymin, xmax, ymax} here, scores are scaled to 0..100) and
-// its status words.  lfd_eval_tt100k_match:
-//   k_tt_count / k_tt_scan / k_tt_scatter  group the stored detections by image (histogram, one-workgroup scan, atomic scatter);
+// The detection store, its status words, the append kernels and the grouping are eval_store.h (boxes are {xmin, ymin, xmax,
+// ymax} here, scores are scaled to 0..100); TtDets / TtRows below are what this protocol makes of one row.
+// lfd_eval_tt100k_match:
+//   k_es_count / k_es_scan / k_es_scatter  group the stored detections by image (histogram, one-workgroup scan, atomic scatter);
 //   k_tt_order   puts each image's detections back into insertion order (rank by counting) and gathers box, score and
 //                category next to each other, so the matching reads contiguous memory;
 //   k_tt_match   one workgroup per (image, iou, minscore).  The reference sorts all candidate pairs by IoU descending (a stable
@@ -16,17 +17,14 @@
 //                in every round, walking ground truth after ground truth, 256 detections at a time.  The match state lives in
 //                caller-owned global memory, so no per-image capacity exists.  The size bands and the counting follow in the
 //                same workgroup: every band re-reads the one matching.
-#include "common.h"
+#include "eval_store.h"
 
 namespace {
 
-constexpr int TT_THREADS = 256;
+constexpr int TT_THREADS = ES_THREADS;
 constexpr int TT_WAVES = TT_THREADS / 64;
-constexpr int TT_SCAN_THREADS = 1024;
 constexpr int TT_TILE = 4096;           // IoU values kept in LDS: 32 KiB
 constexpr long long TT_MATCH_GRID = 1 << 20;
-
-typedef unsigned long long u64;
 
 struct TtArgs {
   lfd_eval_tt100k_bufs_t b;
@@ -42,148 +40,42 @@ struct TtArgs {
   u64* percat;
 };
 
-// ------------------------------------------------------------------ appends
-__global__ __launch_bounds__(TT_THREADS) void k_tt_append_dets(TtArgs a, const float* dets, const int32_t* labels, const int32_t* counts,
-                                                               int n, int cap, const int32_t* label_map, int num_labels,
-                                                               const int32_t* img_ord) {
-  __shared__ long long s_base;
-  const int i = blockIdx.x;
-  if (threadIdx.x == 0) {
-    long long base = a.b.state[0];
-    for (int j = 0; j < i; ++j) base += min(max(counts[j * 4 + 1], 0), cap);
-    s_base = base;
-  }
-  __syncthreads();
-  const long long base = s_base;
-  const int c = min(max(counts[i * 4 + 1], 0), cap);
-  const int ord = img_ord[i];
-  if (ord < 0 || ord >= a.I) {
-    if (threadIdx.x == 0) atomicOr(&a.b.state[1], LFD_EVAL_ERR_IMAGE);
-    return;
-  }
-  if (threadIdx.x == 0) a.b.img_mask[ord] = 1;   // an image without a detection is evaluated too
-  if (base + c > a.cap) return;                  // k_tt_commit_dets raises LFD_EVAL_ERR_CAPACITY
-  for (int j = threadIdx.x; j < c; j += TT_THREADS) {
-    const float* d = dets + ((long long)i * cap + j) * 5;
-    const float x1 = d[0], y1 = d[1];
-    const float w = d[2] - x1 + 1.0f, h = d[3] - y1 + 1.0f;   // fp32, as LFD._pack
-    const long long o = base + j;
-    a.b.det_box[o * 4 + 0] = (double)x1;
-    a.b.det_box[o * 4 + 1] = (double)y1;
-    a.b.det_box[o * 4 + 2] = (double)w + (double)x1;
-    a.b.det_box[o * 4 + 3] = (double)h + (double)y1;
-    a.b.det_score[o] = (double)d[4] * 100.0;
-    a.b.det_img[o] = ord;
-    const int lab = labels[(long long)i * cap + j];
-    const int cat = (lab >= 0 && lab < num_labels) ? label_map[lab] : -1;
-    if (cat < 0 || cat >= a.K) atomicOr(&a.b.state[1], LFD_EVAL_ERR_LABEL);
-    a.b.det_cat[o] = (cat >= 0 && cat < a.K) ? cat : -1;
-  }
+__host__ __device__ __forceinline__ EsStore tt_store(const TtArgs& a) {
+  return EsStore{a.b.det_box, a.b.det_score, a.b.det_img, a.b.det_cat, a.b.state, a.b.img_mask, a.I, a.K, a.cap};
 }
 
-__global__ void k_tt_commit_dets(TtArgs a, const int32_t* counts, int n, int cap) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  long long total = 0;
-  for (int j = 0; j < n; ++j) total += min(max(counts[j * 4 + 1], 0), cap);
-  if ((long long)a.b.state[0] + total > a.cap) atomicOr(&a.b.state[1], LFD_EVAL_ERR_CAPACITY);
-  else a.b.state[0] += (int)total;
-}
-
-__global__ __launch_bounds__(TT_THREADS) void k_tt_append_rows(TtArgs a, const double* rows, long long m, const int32_t* mark, int num_mark) {
-  const long long base = a.b.state[0];
-  const long long stride = (long long)gridDim.x * TT_THREADS;
-  const long long t0 = (long long)blockIdx.x * TT_THREADS + threadIdx.x;
-  for (long long j = t0; j < num_mark; j += stride) {
-    const int ord = mark[j];
-    if (ord >= 0 && ord < a.I) a.b.img_mask[ord] = 1;
-    else atomicOr(&a.b.state[1], LFD_EVAL_ERR_IMAGE);
+// ------------------------------------------------------------------ appends (the frame is eval_store.h)
+struct TtDets : EsDetsDefaults {   // a bad ordinal: LFD_EVAL_ERR_IMAGE whether or not the entry fits, and nothing is written
+  const int32_t* label_map;
+  int num_labels;
+  __device__ bool marks(int, bool) const { return true; }   // before the capacity test: an image without a detection is evaluated too
+  __device__ void row(const EsStore& s, long long o, int ord, float x1, float y1, float w, float h, float score, int lab) const {
+    // {xmin, ymin, xmax, ymax}: xmax = w + x in float64 from the fp32 w; the score in 0..100
+    es_put(s, o, (double)x1, (double)y1, (double)w + (double)x1, (double)h + (double)y1, (double)score * 100.0, ord);
+    s.det_cat[o] = es_label_category(s, label_map, num_labels, lab);
   }
-  if (base + m > a.cap) return;   // k_tt_commit_rows raises LFD_EVAL_ERR_CAPACITY
-  for (long long j = t0; j < m; j += stride) {
-    const double* r = rows + j * 7;
-    const long long o = base + j;
-    int ord = (int)r[0], cat = (int)r[1];
-    if (ord < 0 || ord >= a.I) {
-      atomicOr(&a.b.state[1], LFD_EVAL_ERR_IMAGE);
-      ord = -1;
-      cat = -1;
-    } else {
-      a.b.img_mask[ord] = 1;
-    }
-    if (cat < 0 || cat >= a.K) {
-      atomicOr(&a.b.state[1], LFD_EVAL_ERR_LABEL);
+};
+
+struct TtRows {
+  static constexpr int kCols = 7;   // ordinal, category, score, x, y, w, h
+  __device__ void row(const EsStore& s, long long o, const double* r, int ord, bool bad) const {
+    int cat = bad ? -1 : (int)r[1];   // a bad ordinal: image -1 with no category, which raises LFD_EVAL_ERR_LABEL as well
+    if (cat < 0 || cat >= s.K) {
+      atomicOr(&s.state[1], LFD_EVAL_ERR_LABEL);
       cat = -1;
     }
-    a.b.det_img[o] = ord;
-    a.b.det_cat[o] = cat;
-    a.b.det_score[o] = r[2] * 100.0;
-    a.b.det_box[o * 4 + 0] = r[3];
-    a.b.det_box[o * 4 + 1] = r[4];
-    a.b.det_box[o * 4 + 2] = r[5] + r[3];
-    a.b.det_box[o * 4 + 3] = r[6] + r[4];
+    es_put(s, o, r[3], r[4], r[5] + r[3], r[6] + r[4], r[2] * 100.0, bad ? -1 : ord);
+    s.det_cat[o] = cat;
   }
-}
+};
 
-__global__ void k_tt_commit_rows(TtArgs a, long long m) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  if ((long long)a.b.state[0] + m > a.cap) atomicOr(&a.b.state[1], LFD_EVAL_ERR_CAPACITY);
-  else a.b.state[0] += (int)m;
-}
-
-// ------------------------------------------------------------------ grouping by image
-__device__ __forceinline__ int tt_image_of(const TtArgs& a, int d) {
-  const int img = a.b.det_img[d];
-  return (img >= 0 && img < a.I && a.b.img_mask[img]) ? img : -1;
-}
-
-__global__ __launch_bounds__(TT_THREADS) void k_tt_count(TtArgs a) {
-  const int n = min(max(a.b.state[0], 0), a.cap);
-  for (int d = blockIdx.x * TT_THREADS + threadIdx.x; d < n; d += gridDim.x * TT_THREADS) {
-    const int img = tt_image_of(a, d);
-    if (img >= 0) atomicAdd(&a.cnt[img], 1);
+// ------------------------------------------------------------------ grouping by image (the kernels are eval_store.h)
+struct TtImageKey {
+  __device__ int operator()(const EsStore& s, int d) const {
+    const int img = s.det_img[d];
+    return (img >= 0 && img < s.I && s.img_mask[img]) ? img : -1;
   }
-}
-
-// one workgroup: det_start[] = exclusive scan of cnt[]
-__global__ __launch_bounds__(TT_SCAN_THREADS) void k_tt_scan(TtArgs a) {
-  __shared__ long long s[2 * TT_SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int chunk = (a.I + TT_SCAN_THREADS - 1) / TT_SCAN_THREADS;
-  const int p0 = min(a.I, t * chunk), p1 = min(a.I, p0 + chunk);
-  long long loc = 0;
-  for (int p = p0; p < p1; ++p) loc += a.cnt[p];
-  int cur = 0;
-  s[t] = loc;
-  __syncthreads();
-#pragma unroll 1
-  for (int off = 1; off < TT_SCAN_THREADS; off <<= 1) {
-    long long x = s[cur * TT_SCAN_THREADS + t];
-    if (t >= off) x += s[cur * TT_SCAN_THREADS + t - off];
-    s[(cur ^ 1) * TT_SCAN_THREADS + t] = x;
-    cur ^= 1;
-    __syncthreads();
-  }
-  const long long inc = s[cur * TT_SCAN_THREADS + t];
-  long long run = inc - loc;
-  for (int p = p0; p < p1; ++p) {
-    a.b.det_start[p] = (int)run;
-    run += a.cnt[p];
-  }
-  if (t == TT_SCAN_THREADS - 1) {
-    a.b.det_start[a.I] = (int)inc;
-    a.b.state[2] = (int)inc;
-  }
-}
-
-__global__ __launch_bounds__(TT_THREADS) void k_tt_scatter(TtArgs a) {
-  const int n = min(max(a.b.state[0], 0), a.cap);
-  for (int d = blockIdx.x * TT_THREADS + threadIdx.x; d < n; d += gridDim.x * TT_THREADS) {
-    const int img = tt_image_of(a, d);
-    if (img < 0) continue;
-    const int slot = a.b.det_start[img] + atomicAdd(&a.fill[img], 1);
-    if (slot < a.b.det_start[img + 1] && slot < a.cap) a.members[slot] = d;
-  }
-}
+};
 
 // insertion order inside every image: position = number of the image's detections with a smaller store index
 __global__ __launch_bounds__(TT_THREADS) void k_tt_order(TtArgs a) {
@@ -430,8 +322,6 @@ size_t tt_carve(TtArgs& a, void* ws) {
   return c.used();
 }
 
-int tt_grid(long long items) { return (int)max(1LL, min((items + TT_THREADS - 1) / TT_THREADS, 2048LL)); }
-
 bool tt_store_ok(const lfd_eval_tt100k_bufs_t* b) {
   return b && b->det_box && b->det_score && b->det_img && b->det_cat && b->state && b->img_mask;
 }
@@ -446,13 +336,10 @@ int lfd_eval_tt100k_append_dets_f32(const lfd_eval_tt100k_desc_t* desc, const lf
   if (!tt_desc_ok(desc) || !tt_store_ok(bufs) || !dets || !labels || !counts || !label_map || !img_ord) return LFD_ERR_INVALID_ARGUMENT;
   if (n < 1 || cap < 1 || num_labels < 1) return LFD_ERR_INVALID_ARGUMENT;
   if (!tt_desc_supported(desc) || n > 65535) return LFD_ERR_UNSUPPORTED;
-  const TtArgs a = tt_args(desc, bufs);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_tt_append_dets, dim3(n), dim3(TT_THREADS), 0, st, a, dets, labels, counts, n, cap, label_map, num_labels, img_ord);
-  LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_tt_commit_dets, dim3(1), dim3(64), 0, st, a, counts, n, cap);
-  LFD_CHECK_LAUNCH();
-  return LFD_OK;
+  TtDets p;
+  p.label_map = label_map;
+  p.num_labels = num_labels;
+  return es_append_dets(tt_store(tt_args(desc, bufs)), p, dets, labels, counts, n, cap, img_ord, 0, stream);
 }
 
 int lfd_eval_tt100k_append_rows_f64(const lfd_eval_tt100k_desc_t* desc, const lfd_eval_tt100k_bufs_t* bufs, const double* rows,
@@ -461,14 +348,7 @@ int lfd_eval_tt100k_append_rows_f64(const lfd_eval_tt100k_desc_t* desc, const lf
   if ((m > 0 && !rows) || (num_mark > 0 && !mark)) return LFD_ERR_INVALID_ARGUMENT;
   if (!tt_desc_supported(desc)) return LFD_ERR_UNSUPPORTED;
   if (m == 0 && num_mark == 0) return LFD_OK;
-  const TtArgs a = tt_args(desc, bufs);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_tt_append_rows, dim3(tt_grid(max((long long)m, (long long)num_mark))), dim3(TT_THREADS), 0, st, a, rows,
-                     (long long)m, mark, num_mark);
-  LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_tt_commit_rows, dim3(1), dim3(64), 0, st, a, (long long)m);
-  LFD_CHECK_LAUNCH();
-  return LFD_OK;
+  return es_append_rows(tt_store(tt_args(desc, bufs)), TtRows(), rows, (long long)m, mark, num_mark, stream);
 }
 
 size_t lfd_eval_tt100k_workspace_bytes(const lfd_eval_tt100k_desc_t* desc) {
@@ -494,11 +374,12 @@ int lfd_eval_tt100k_match(const lfd_eval_tt100k_desc_t* desc, const lfd_eval_tt1
   if (hipMemsetAsync(a.totals, 0, cells * 3 * sizeof(u64), st) != hipSuccess) return LFD_ERR_LAUNCH_FAILED;
   if (a.percat && hipMemsetAsync(a.percat, 0, cells * a.K * 3 * sizeof(u64), st) != hipSuccess)
     return LFD_ERR_LAUNCH_FAILED;
-  hipLaunchKernelGGL(k_tt_count, dim3(tt_grid(a.cap)), dim3(TT_THREADS), 0, st, a);
+  const EsStore s = tt_store(a);
+  hipLaunchKernelGGL(k_es_count<TtImageKey>, dim3(es_grid(a.cap)), dim3(ES_THREADS), 0, st, s, a.cnt);
   LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_tt_scan, dim3(1), dim3(TT_SCAN_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_es_scan, dim3(1), dim3(ES_SCAN_THREADS), 0, st, a.cnt, a.I, a.b.det_start, a.b.state);
   LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_tt_scatter, dim3(tt_grid(a.cap)), dim3(TT_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_es_scatter<TtImageKey>, dim3(es_grid(a.cap)), dim3(ES_THREADS), 0, st, s, a.b.det_start, a.fill, a.members);
   LFD_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_tt_order, dim3((unsigned)min(a.I, 65536)), dim3(TT_THREADS), 0, st, a);
   LFD_CHECK_LAUNCH();

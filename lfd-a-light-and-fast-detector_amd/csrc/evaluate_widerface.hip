@@ -4,11 +4,12 @@
 // and evaluated as the definition writes it (-ffp-contract=off, fp64 division is correctly rounded); what leaves the device
 // are integer counts, summed with integer atomics, so the result does not depend on the schedule.
 //
-// The detection store has evaluate.hip's layout (boxes are {x, y, w, h}, one class) and its status words; a row whose label
-// the caller filters out keeps its slot with det_img = -1 and takes part in nothing.  lfd_eval_wf_match:
+// The detection store, its status words, the append kernels and the grouping are eval_store.h (boxes are {x, y, w, h}, one
+// class, no img_mask); WfDets / WfRows below are what this protocol makes of one row.  A row whose label the caller filters
+// out keeps its slot with det_img = -1 and takes part in nothing.  lfd_eval_wf_match:
 //   k_wf_minmax   minimum and maximum score over the store (an order-preserving 64-bit key, integer atomicMin / atomicMax);
 //   k_wf_faces    faces[d] = sum of the keep-list lengths over every annotated image;
-//   k_wf_count / k_wf_scan / k_wf_scatter  group the stored detections by image (histogram, one-workgroup scan, atomic scatter);
+//   k_es_count / k_es_scan / k_es_scatter  group the stored detections by image (histogram, one-workgroup scan, atomic scatter);
 //   k_wf_match    a persistent grid draws images from a ticket.  For an image with detections and ground truth a workgroup
 //                 ranks the detections by counting (score descending, then store index: the stable sort), computes for every
 //                 ranked detection the first ground truth of maximal IoU over 64-wide ground-truth tiles in LDS, lets three
@@ -16,18 +17,16 @@
 //                 most WF_HIT_LDS boxes, caller-owned global memory otherwise: no per-image capacity), and lets all lanes
 //                 share the thresholds: a binary search in the ranked normalised scores per threshold, the running counts
 //                 added into a per-workgroup LDS copy of the curve that is flushed with 64-bit atomics at the end.
-#include "common.h"
+#include "eval_store.h"
 
 namespace {
 
-constexpr int WF_THREADS = 256;
-constexpr int WF_SCAN_THREADS = 1024;
+constexpr int WF_THREADS = ES_THREADS;
+constexpr int WF_SCAN_THREADS = ES_SCAN_THREADS;
 constexpr int WF_TILE = 64;             // ground-truth boxes per LDS tile
 constexpr int WF_HIT_LDS = 256;         // images with at most this many boxes keep the hit state in LDS
 constexpr int WF_MAX_T = 1024;          // thresholds: the per-workgroup curve is 3 * T * 2 uint32 in LDS
 constexpr int WF_GRID = 512;
-
-typedef unsigned long long u64;
 
 struct WfArgs {
   lfd_eval_wf_bufs_t b;
@@ -44,6 +43,10 @@ struct WfArgs {
   u64* curve;      // the caller's uint64_t outputs, as the type atomicAdd takes
   u64* faces;
 };
+
+__host__ __device__ __forceinline__ EsStore wf_store(const WfArgs& a) {   // one class, no img_mask
+  return EsStore{a.b.det_box, a.b.det_score, a.b.det_img, nullptr, a.b.state, nullptr, a.I, 1, a.cap};
+}
 
 // order-preserving map double -> u64 (and back): the reduction then is an integer minimum / maximum
 __device__ __forceinline__ u64 wf_key(double v) {
@@ -69,106 +72,46 @@ __device__ __forceinline__ double wf_quantise_score(float s32) {
   return k / 1000.0;
 }
 
-__device__ __forceinline__ int wf_count_of(const int32_t* counts, int j, int cap) { return min(max(counts[j * 4 + 1], 0), cap); }
-
-// ------------------------------------------------------------------ appends
-__global__ __launch_bounds__(WF_THREADS) void k_wf_append_dets(WfArgs a, const float* dets, const int32_t* labels, const int32_t* counts,
-                                                               int n, int cap, const int32_t* img_ord) {
-  __shared__ long long s_base;
-  const int i = blockIdx.x;
-  const int extra = a.as_written ? 1 : 0;
-  if (threadIdx.x == 0) {
-    long long base = a.b.state[0];
-    for (int j = 0; j < i; ++j) base += wf_count_of(counts, j, cap) + extra;
-    s_base = base;
+// ------------------------------------------------------------------ appends (the frame is eval_store.h)
+struct WfDets : EsDetsDefaults {
+  int as_written, label_index;
+  static constexpr bool kImageFirst = false;   // an entry that does not fit reports nothing, whatever its ordinal
+  __device__ bool marks(int, bool) const { return false; }
+  __device__ void drop(const EsStore& s, long long o) const {   // a bad ordinal keeps its slots (the commit counts them), dropped
+    s.det_img[o] = -1;
+    s.det_score[o] = 0.0;
   }
-  __syncthreads();
-  long long base = s_base;
-  const int c = wf_count_of(counts, i, cap);
-  const int ord = img_ord[i];
-  if (base + c + extra > a.cap) return;          // k_wf_commit_dets raises LFD_EVAL_ERR_CAPACITY
-  if (ord < 0 || ord >= a.I) {                   // the entry keeps its slots (the commit counts them): mark them dropped
-    if (threadIdx.x == 0) atomicOr(&a.b.state[1], LFD_EVAL_ERR_IMAGE);
-    for (int j = threadIdx.x; j < c + extra; j += WF_THREADS) {
-      a.b.det_img[base + j] = -1;
-      a.b.det_score[base + j] = 0.0;
-    }
-    return;
+  __device__ void first(const EsStore& s, long long o, int ord) const {   // as_written: the writer's first line of every file
+    es_put(s, o, 0.0, 0.0, 0.0, 0.0, 0.001, ord);
   }
-  if (extra) {
-    if (threadIdx.x == 0) {                      // the writer's first line of every file: 0 0 0 0 0.001
-      a.b.det_box[base * 4 + 0] = 0.0;
-      a.b.det_box[base * 4 + 1] = 0.0;
-      a.b.det_box[base * 4 + 2] = 0.0;
-      a.b.det_box[base * 4 + 3] = 0.0;
-      a.b.det_score[base] = 0.001;
-      a.b.det_img[base] = ord;
-    }
-    base += 1;
-  }
-  for (int j = threadIdx.x; j < c; j += WF_THREADS) {
-    const float* d = dets + ((long long)i * cap + j) * 5;
-    const float x1 = d[0], y1 = d[1];
-    const float w = d[2] - x1 + 1.0f, h = d[3] - y1 + 1.0f;   // fp32, as LFD._pack
-    const long long o = base + j;
-    double x = (double)x1, y = (double)y1, ww = (double)w, hh = (double)h, s = (double)d[4];
-    if (a.as_written) {
+  __device__ void row(const EsStore& s, long long o, int ord, float x1, float y1, float w, float h, float score, int lab) const {
+    double x = (double)x1, y = (double)y1, ww = (double)w, hh = (double)h, sc = (double)score;   // {x, y, w, h}
+    if (as_written) {
       x = floor(x);
       y = floor(y);
       ww = ceil(ww);
       hh = ceil(hh);
-      s = wf_quantise_score(d[4]);
+      sc = wf_quantise_score(score);
     }
-    a.b.det_box[o * 4 + 0] = x;
-    a.b.det_box[o * 4 + 1] = y;
-    a.b.det_box[o * 4 + 2] = ww;
-    a.b.det_box[o * 4 + 3] = hh;
-    a.b.det_score[o] = s;
-    const bool take = a.label_index < 0 || labels[(long long)i * cap + j] == a.label_index;
-    a.b.det_img[o] = take ? ord : -1;
+    es_put(s, o, x, y, ww, hh, sc, (label_index < 0 || lab == label_index) ? ord : -1);   // a filtered label keeps its slot
   }
-}
+};
 
-__global__ void k_wf_commit_dets(WfArgs a, const int32_t* counts, int n, int cap) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  long long total = 0;
-  for (int j = 0; j < n; ++j) total += wf_count_of(counts, j, cap) + (a.as_written ? 1 : 0);
-  if ((long long)a.b.state[0] + total > a.cap) atomicOr(&a.b.state[1], LFD_EVAL_ERR_CAPACITY);
-  else a.b.state[0] += (int)total;
-}
-
-__global__ __launch_bounds__(WF_THREADS) void k_wf_append_rows(WfArgs a, const double* rows, long long m) {
-  const long long base = a.b.state[0];
-  if (base + m > a.cap) return;   // k_wf_commit_rows raises LFD_EVAL_ERR_CAPACITY
-  const long long stride = (long long)gridDim.x * WF_THREADS;
-  for (long long j = (long long)blockIdx.x * WF_THREADS + threadIdx.x; j < m; j += stride) {
-    const double* r = rows + j * 6;
-    const long long o = base + j;
-    int ord = (int)r[0];
-    if (ord < 0 || ord >= a.I) {
-      atomicOr(&a.b.state[1], LFD_EVAL_ERR_IMAGE);
-      ord = -1;
-    }
-    a.b.det_img[o] = ord;
-    a.b.det_score[o] = r[1];
-    a.b.det_box[o * 4 + 0] = r[2];
-    a.b.det_box[o * 4 + 1] = r[3];
-    a.b.det_box[o * 4 + 2] = r[4];
-    a.b.det_box[o * 4 + 3] = r[5];
+struct WfRows {
+  static constexpr int kCols = 6;   // ordinal, score, x, y, w, h
+  __device__ void row(const EsStore& s, long long o, const double* r, int ord, bool bad) const {
+    es_put(s, o, r[2], r[3], r[4], r[5], r[1], bad ? -1 : ord);
   }
-}
-
-__global__ void k_wf_commit_rows(WfArgs a, long long m) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  if ((long long)a.b.state[0] + m > a.cap) atomicOr(&a.b.state[1], LFD_EVAL_ERR_CAPACITY);
-  else a.b.state[0] += (int)m;
-}
+};
 
 // ------------------------------------------------------------------ score range, faces
-__device__ __forceinline__ int wf_image_of(const WfArgs& a, int d) {
-  const int img = a.b.det_img[d];
-  return (img >= 0 && img < a.I) ? img : -1;
-}
+struct WfImageKey {
+  __device__ int operator()(const EsStore& s, int d) const {
+    const int img = s.det_img[d];
+    return (img >= 0 && img < s.I) ? img : -1;
+  }
+};
+__device__ __forceinline__ int wf_image_of(const WfArgs& a, int d) { return WfImageKey()(wf_store(a), d); }
 
 __global__ __launch_bounds__(WF_THREADS) void k_wf_minmax(WfArgs a) {
   const int n = min(max(a.b.state[0], 0), a.cap);
@@ -204,56 +147,6 @@ __global__ __launch_bounds__(WF_SCAN_THREADS) void k_wf_faces(WfArgs a) {
     if (loc[d]) atomicAdd(&s[d], loc[d]);
   __syncthreads();
   if (threadIdx.x < 3) a.faces[threadIdx.x] = s[threadIdx.x];
-}
-
-// ------------------------------------------------------------------ grouping by image
-__global__ __launch_bounds__(WF_THREADS) void k_wf_count(WfArgs a) {
-  const int n = min(max(a.b.state[0], 0), a.cap);
-  for (int d = blockIdx.x * WF_THREADS + threadIdx.x; d < n; d += gridDim.x * WF_THREADS) {
-    const int img = wf_image_of(a, d);
-    if (img >= 0) atomicAdd(&a.cnt[img], 1);
-  }
-}
-
-// one workgroup: det_start[] = exclusive scan of cnt[]
-__global__ __launch_bounds__(WF_SCAN_THREADS) void k_wf_scan(WfArgs a) {
-  __shared__ long long s[2 * WF_SCAN_THREADS];
-  const int t = threadIdx.x;
-  const int chunk = (a.I + WF_SCAN_THREADS - 1) / WF_SCAN_THREADS;
-  const int p0 = min(a.I, t * chunk), p1 = min(a.I, p0 + chunk);
-  long long loc = 0;
-  for (int p = p0; p < p1; ++p) loc += a.cnt[p];
-  int cur = 0;
-  s[t] = loc;
-  __syncthreads();
-#pragma unroll 1
-  for (int off = 1; off < WF_SCAN_THREADS; off <<= 1) {
-    long long x = s[cur * WF_SCAN_THREADS + t];
-    if (t >= off) x += s[cur * WF_SCAN_THREADS + t - off];
-    s[(cur ^ 1) * WF_SCAN_THREADS + t] = x;
-    cur ^= 1;
-    __syncthreads();
-  }
-  const long long inc = s[cur * WF_SCAN_THREADS + t];
-  long long run = inc - loc;
-  for (int p = p0; p < p1; ++p) {
-    a.b.det_start[p] = (int)run;
-    run += a.cnt[p];
-  }
-  if (t == WF_SCAN_THREADS - 1) {
-    a.b.det_start[a.I] = (int)inc;
-    a.b.state[2] = (int)inc;
-  }
-}
-
-__global__ __launch_bounds__(WF_THREADS) void k_wf_scatter(WfArgs a) {
-  const int n = min(max(a.b.state[0], 0), a.cap);
-  for (int d = blockIdx.x * WF_THREADS + threadIdx.x; d < n; d += gridDim.x * WF_THREADS) {
-    const int img = wf_image_of(a, d);
-    if (img < 0) continue;
-    const int slot = a.b.det_start[img] + atomicAdd(&a.fill[img], 1);
-    if (slot < a.b.det_start[img + 1] && slot < a.cap) a.members[slot] = d;
-  }
 }
 
 // ------------------------------------------------------------------ matching
@@ -483,8 +376,6 @@ size_t wf_carve(WfArgs& a, void* ws) {
   return c.used();
 }
 
-int wf_grid(long long items) { return (int)max(1LL, min((items + WF_THREADS - 1) / WF_THREADS, 2048LL)); }
-
 bool wf_store_ok(const lfd_eval_wf_bufs_t* b) { return b && b->det_box && b->det_score && b->det_img && b->state; }
 
 }  // namespace
@@ -498,12 +389,10 @@ int lfd_eval_wf_append_dets_f32(const lfd_eval_wf_desc_t* desc, const lfd_eval_w
   if (n < 1 || cap < 1) return LFD_ERR_INVALID_ARGUMENT;
   if (!wf_desc_supported(desc) || n > 65535) return LFD_ERR_UNSUPPORTED;
   const WfArgs a = wf_args(desc, bufs);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_wf_append_dets, dim3(n), dim3(WF_THREADS), 0, st, a, dets, labels, counts, n, cap, img_ord);
-  LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_wf_commit_dets, dim3(1), dim3(64), 0, st, a, counts, n, cap);
-  LFD_CHECK_LAUNCH();
-  return LFD_OK;
+  WfDets p;
+  p.as_written = a.as_written;
+  p.label_index = a.label_index;
+  return es_append_dets(wf_store(a), p, dets, labels, counts, n, cap, img_ord, a.as_written, stream);   // as_written: one dummy row per entry
 }
 
 int lfd_eval_wf_append_rows_f64(const lfd_eval_wf_desc_t* desc, const lfd_eval_wf_bufs_t* bufs, const double* rows, int64_t m,
@@ -512,13 +401,7 @@ int lfd_eval_wf_append_rows_f64(const lfd_eval_wf_desc_t* desc, const lfd_eval_w
   if (m > 0 && !rows) return LFD_ERR_INVALID_ARGUMENT;
   if (!wf_desc_supported(desc)) return LFD_ERR_UNSUPPORTED;
   if (m == 0) return LFD_OK;
-  const WfArgs a = wf_args(desc, bufs);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_wf_append_rows, dim3(wf_grid((long long)m)), dim3(WF_THREADS), 0, st, a, rows, (long long)m);
-  LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_wf_commit_rows, dim3(1), dim3(64), 0, st, a, (long long)m);
-  LFD_CHECK_LAUNCH();
-  return LFD_OK;
+  return es_append_rows(wf_store(wf_args(desc, bufs)), WfRows(), rows, (long long)m, nullptr, 0, stream);
 }
 
 size_t lfd_eval_wf_workspace_bytes(const lfd_eval_wf_desc_t* desc) {
@@ -543,15 +426,16 @@ int lfd_eval_wf_match(const lfd_eval_wf_desc_t* desc, const lfd_eval_wf_bufs_t* 
   if (hipMemsetAsync(a.mm, 0xff, sizeof(u64), st) != hipSuccess) return LFD_ERR_LAUNCH_FAILED;
   if (hipMemsetAsync(a.mm + 1, 0, sizeof(u64), st) != hipSuccess) return LFD_ERR_LAUNCH_FAILED;
   if (hipMemsetAsync(a.curve, 0, (size_t)3 * a.T * 2 * sizeof(u64), st) != hipSuccess) return LFD_ERR_LAUNCH_FAILED;
-  hipLaunchKernelGGL(k_wf_minmax, dim3(wf_grid(a.cap)), dim3(WF_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_wf_minmax, dim3(es_grid(a.cap)), dim3(WF_THREADS), 0, st, a);
   LFD_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_wf_faces, dim3(1), dim3(WF_SCAN_THREADS), 0, st, a);
   LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_wf_count, dim3(wf_grid(a.cap)), dim3(WF_THREADS), 0, st, a);
+  const EsStore s = wf_store(a);
+  hipLaunchKernelGGL(k_es_count<WfImageKey>, dim3(es_grid(a.cap)), dim3(ES_THREADS), 0, st, s, a.cnt);
   LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_wf_scan, dim3(1), dim3(WF_SCAN_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_es_scan, dim3(1), dim3(ES_SCAN_THREADS), 0, st, a.cnt, a.I, a.b.det_start, a.b.state);
   LFD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_wf_scatter, dim3(wf_grid(a.cap)), dim3(WF_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_es_scatter<WfImageKey>, dim3(es_grid(a.cap)), dim3(ES_THREADS), 0, st, s, a.b.det_start, a.fill, a.members);
   LFD_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_wf_match, dim3((unsigned)min(a.I, WF_GRID)), dim3(WF_THREADS), 0, st, a);
   LFD_CHECK_LAUNCH();

@@ -76,7 +76,159 @@ def format_display(stats):
     return s
 
 
-class COCOEvaluator(Evaluator):
+class _DeviceEvaluator(Evaluator):
+    """What the three evaluators share: the lazily built device state, the detection store of csrc/eval_store.h (grown on
+    demand), the bufs struct, the frames of the two append paths, the status word and the display string.  A subclass names
+    its store columns, the device tensors its bufs struct points to and its _lib struct, uploads its ground truth in
+    `_upload` and describes the problem in `_desc`."""
+    _COLUMNS = dict(det_box=((4,), 'float64'), det_score=((), 'float64'), det_img=((), 'int32'), det_cat=((), 'int32'))
+    _STORE = ('det_box', 'det_score', 'det_img', 'det_cat')      # the columns this protocol's store has
+    _BUFS = ()                 # further device-state tensors of the bufs struct ('img_mask' among them: the protocol has one)
+    _BUFS_STRUCT = None        # the struct's ctypes mirror in _lib
+    _ERR_LABEL = None          # what LFD_EVAL_ERR_LABEL means to the caller; None: the protocol never raises it
+    _image_key = None          # meta['image_id'] -> key of _img_ord, where the two differ
+
+    def _start(self, device):
+        """the accumulation state; with a GPU the ground truth is uploaded once, here"""
+        self._device = device
+        self._eval_display_str = ''
+        self._dev = None           # device state, built on first use
+        self._seen = set()         # image ordinals since the last evaluate() (_ordinals)
+        self._upper = 0            # upper bound of the detections stored on the device
+        self._last = None
+        import torch
+        if torch.cuda.is_available():
+            self._state()
+
+    # ------------------------------------------------------------------ device state
+    def _state(self):
+        if self._dev is not None:
+            return self._dev
+        import torch
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError('%s: the evaluation kernels run on the MI355X only; there is no CPU implementation' % type(self).__name__)
+        dev = torch.device(self._device) if self._device is not None else torch.device('cuda', torch.cuda.current_device())
+        d = type('EvalDeviceState', (), {})()
+        d.torch, d.lib, d.dev = torch, _lib, dev
+        d.fields = self._STORE + ('state',) + self._BUFS           # what _bufs points the struct to
+        self._upload(d, lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev))
+        d.state = torch.zeros(4, dtype=torch.int32, device=dev)
+        if 'img_mask' in self._BUFS:
+            d.img_mask = torch.zeros(len(self.image_ids), dtype=torch.int32, device=dev)
+        d.cap = 0
+        for k in self._STORE:
+            setattr(d, k, None)
+        self._dev = d
+        self._reserve(1 << 16)
+        return d
+
+    def _reserve(self, need):
+        """grow the detection store to hold `need` entries (device-to-device copies on the current stream, no sync)"""
+        d = self._dev
+        if need <= d.cap:
+            return
+        torch = d.torch
+        cap = max(int(need), 2 * d.cap)
+        for k in self._STORE:
+            shape, dtype = self._COLUMNS[k]
+            new = torch.empty((cap,) + shape, dtype=getattr(torch, dtype), device=d.dev)
+            if d.cap:
+                new[:d.cap].copy_(getattr(d, k))
+            setattr(d, k, new)
+        d.cap = cap
+
+    def _bufs(self, **extra):
+        d = self._dev
+        b = getattr(d.lib, self._BUFS_STRUCT)()
+        for k in d.fields:
+            setattr(b, k, getattr(d, k).data_ptr())
+        for k, t in extra.items():
+            setattr(b, k, t.data_ptr() if t is not None else None)
+        return b
+
+    def _ordinals(self, meta_batch):
+        """image ordinals of a batch; an unknown id, or one that already arrived since the last evaluate(), is a ValueError"""
+        ords = []
+        for m in meta_batch:
+            key = m['image_id'] if self._image_key is None else self._image_key(m['image_id'])
+            if key not in self._img_ord:
+                raise ValueError('image id %r is not in the annotations' % (key,))
+            o = self._img_ord[key]
+            if o in self._seen or o in ords:
+                raise ValueError('image id %r arrived twice before evaluate()' % (key,))
+            ords.append(o)
+        return ords
+
+    # ------------------------------------------------------------------ accumulation
+    @staticmethod
+    def _split(results):
+        if not (isinstance(results, tuple) and len(results) == 2):
+            raise TypeError('update info should contain two parts: predict bboxes and meta info.')
+        predict, meta_batch = results
+        if len(predict) != len(meta_batch):
+            raise ValueError('%d prediction lists for %d meta entries' % (len(predict), len(meta_batch)))
+        return predict, meta_batch
+
+    def _append_rows(self, name, rows, cols, mark=None):
+        """_lib `name`(desc, bufs, rows [len(rows), cols] float64, len(rows)[, mark, len(mark)], stream); mark: a list of image
+        ordinals where the entry point takes one"""
+        d = self._state()
+        torch = d.torch
+        self._upper += len(rows)
+        self._reserve(self._upper)
+        with torch.cuda.device(d.dev):
+            rows_t = torch.from_numpy(np.array(rows, np.float64).reshape(len(rows), cols)).to(d.dev) if rows else None
+            tail = ()
+            if mark is not None:
+                mark_t = torch.tensor(mark, dtype=torch.int32).to(d.dev) if mark else None
+                tail = (d.lib.ptr(mark_t), len(mark))
+            desc, bufs = self._desc(), self._bufs()
+            d.lib.check(getattr(d.lib.lib(), name)(C.byref(desc), C.byref(bufs), d.lib.ptr(rows_t), len(rows), *tail, d.lib.stream_ptr()), name)
+
+    def _append_resident(self, name, outputs, meta_batch, tail, dummy_rows=0):
+        """The frame of update_resident: _lib `name`(desc, bufs, dets, labels, counts, n, cap, *tail(d, ordinals), stream); an
+        image takes at most cap + dummy_rows store entries.  -> the batch's image ordinals"""
+        n, cap = int(outputs.dets.size(0)), int(outputs.dets.size(1))
+        if len(meta_batch) != n:
+            raise ValueError('%d meta entries for a batch of %d' % (len(meta_batch), n))
+        ords = self._ordinals(meta_batch)
+        d = self._state()
+        torch = d.torch
+        if outputs.dets.device != d.dev:
+            raise RuntimeError('update_resident: the outputs live on %s, the evaluator on %s' % (outputs.dets.device, d.dev))
+        self._upper += n * (cap + dummy_rows)
+        self._reserve(self._upper)
+        with torch.cuda.device(d.dev):
+            host = torch.empty(n, dtype=torch.int32, pin_memory=True)
+            host.numpy()[:] = ords
+            ord_t = host.to(d.dev, non_blocking=True)
+            desc, bufs = self._desc(), self._bufs()
+            d.lib.check(getattr(d.lib.lib(), name)(C.byref(desc), C.byref(bufs), d.lib.ptr(outputs.dets), d.lib.ptr(outputs.labels),
+                                                   d.lib.ptr(outputs.counts), n, cap, *tail(d, d.lib.ptr(ord_t)), d.lib.stream_ptr()), name)
+        return ords
+
+    # ------------------------------------------------------------------ evaluation
+    def _status_error(self, err):
+        """the RuntimeError for the status bits `err` (LFD_EVAL_ERR_*) that an evaluate() found"""
+        msgs = [m for bit, m in ((ERR_CAPACITY, 'the detection store overflowed'), (ERR_IMAGE, 'an image ordinal was out of range'),
+                                 (ERR_LABEL, self._ERR_LABEL)) if err & bit and m]
+        return RuntimeError('%s: ' % type(self).__name__ + '; '.join(msgs) +
+                            ' (status bits %d); the accumulated detections were dropped' % err)
+
+    def _clear(self):
+        self._seen = set()
+        self._upper = 0
+        if self._dev is not None:
+            self._dev.state.zero_()
+            if 'img_mask' in self._BUFS:
+                self._dev.img_mask.zero_()
+
+    def get_eval_display_str(self):
+        return self._eval_display_str
+
+
+class COCOEvaluator(_DeviceEvaluator):
     """Drop-in for the reference's COCOEvaluator (config_dict['evaluator']): same constructor arguments, `update`,
     `evaluate`, `get_eval_display_str`; plus `update_resident` for ops.DetectOutputs that never leave the device.
 
@@ -99,20 +251,13 @@ class COCOEvaluator(Evaluator):
             raise ValueError("annotations must be a COCO dict with an 'annotations' list")
         self._label_indexes_to_category_ids = dict(label_indexes_to_category_ids)
         self._all_images = bool(all_images)
-        self._device = device
-        self._eval_display_str = ''
         self._parse(annotations)
         self.iou_thrs, self.rec_thrs, self.area_rng = coco_params()
         self.max_dets = MAX_DETS
         self.stats = self.precision = self.recall = None
-        self._dev = None           # device state, built on first use
         self._host_rows = 0        # rows appended through update()
         self._resident_calls = 0
-        self._upper = 0            # upper bound of the detections stored on the device
-        self._last = None
-        import torch
-        if torch.cuda.is_available():
-            self._state()          # the ground truth is uploaded once, here
+        self._start(device)
 
     # ------------------------------------------------------------------ ground truth (host)
     def _parse(self, ann):
@@ -144,17 +289,11 @@ class COCOEvaluator(Evaluator):
                 self._label_map[int(lab)] = self._cat_idx[cid]
 
     # ------------------------------------------------------------------ device state
-    def _state(self):
-        if self._dev is not None:
-            return self._dev
-        import torch
-        from . import _lib
-        if not torch.cuda.is_available():
-            raise RuntimeError('COCOEvaluator: the evaluation kernels run on the MI355X only; there is no CPU implementation')
-        dev = torch.device(self._device) if self._device is not None else torch.device('cuda', torch.cuda.current_device())
-        d = type('EvalDeviceState', (), {})()
-        d.torch, d.lib, d.dev = torch, _lib, dev
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    _BUFS = ('img_mask', 'gt_box', 'gt_area', 'gt_crowd', 'gt_pair_start', 'iou_thrs', 'area_rng', 'rec_thrs')
+    _BUFS_STRUCT = 'EvalBufs'
+    _ERR_LABEL = 'a detection carried a label that label_indexes_to_category_ids does not map'
+
+    def _upload(self, d, up):
         G = len(self.gt_area)
         d.gt_box = up(self.gt_box if G else np.zeros((1, 4)))
         d.gt_area = up(self.gt_area if G else np.zeros(1))
@@ -162,28 +301,6 @@ class COCOEvaluator(Evaluator):
         d.gt_pair_start = up(self.gt_pair_start)
         d.iou_thrs, d.rec_thrs, d.area_rng = up(self.iou_thrs), up(self.rec_thrs), up(self.area_rng)
         d.label_map = up(self._label_map)
-        d.state = torch.zeros(4, dtype=torch.int32, device=dev)
-        d.img_mask = torch.zeros(len(self.image_ids), dtype=torch.int32, device=dev)
-        d.cap = 0
-        d.det_box = d.det_score = d.det_img = d.det_cat = None
-        self._dev = d
-        self._reserve(1 << 16)
-        return d
-
-    def _reserve(self, need):
-        """grow the detection store to hold `need` entries (device-to-device copies on the current stream, no sync)"""
-        d = self._dev
-        if need <= d.cap:
-            return
-        torch = d.torch
-        cap = max(int(need), 2 * d.cap)
-        new = [torch.empty((cap, 4), dtype=torch.float64, device=d.dev), torch.empty(cap, dtype=torch.float64, device=d.dev),
-               torch.empty(cap, dtype=torch.int32, device=d.dev), torch.empty(cap, dtype=torch.int32, device=d.dev)]
-        if d.cap:
-            for n, o in zip(new, (d.det_box, d.det_score, d.det_img, d.det_cat)):
-                n[:d.cap].copy_(o)
-        d.det_box, d.det_score, d.det_img, d.det_cat = new
-        d.cap = cap
 
     def _desc(self):
         d = self._dev
@@ -196,16 +313,6 @@ class COCOEvaluator(Evaluator):
             desc.max_dets[i] = int(m)
         return desc
 
-    def _bufs(self, **extra):
-        d = self._dev
-        b = d.lib.EvalBufs()
-        for k in ('det_box', 'det_score', 'det_img', 'det_cat', 'state', 'img_mask', 'gt_box', 'gt_area', 'gt_crowd',
-                  'gt_pair_start', 'iou_thrs', 'area_rng', 'rec_thrs'):
-            setattr(b, k, getattr(d, k).data_ptr())
-        for k, t in extra.items():
-            setattr(b, k, t.data_ptr())
-        return b
-
     def _ordinals(self, meta_batch):
         try:
             return [self._img_ord[m['image_id']] for m in meta_batch]
@@ -216,11 +323,7 @@ class COCOEvaluator(Evaluator):
     def update(self, results):
         """results: tuple(predict_bboxes, meta_batch); predict_bboxes[i] is a list of [label, score, x, y, w, h] rows for
         image meta_batch[i]['image_id'] (what LFD.get_results returns)."""
-        if not (isinstance(results, tuple) and len(results) == 2):
-            raise TypeError('update info should contain two parts: predict bboxes and meta info.')
-        predict_bboxes, meta_batch = results
-        if len(predict_bboxes) != len(meta_batch):
-            raise ValueError('%d prediction lists for %d meta entries' % (len(predict_bboxes), len(meta_batch)))
+        predict_bboxes, meta_batch = self._split(results)
         ords = self._ordinals(meta_batch)
         rows = []
         for o, boxes in zip(ords, predict_bboxes):
@@ -230,43 +333,15 @@ class COCOEvaluator(Evaluator):
         mark = ords if self._all_images else []
         if not rows and not mark:
             return
-        d = self._state()
-        torch = d.torch
-        self._upper += len(rows)
-        self._reserve(self._upper)
-        with torch.cuda.device(d.dev):
-            rows_t = torch.from_numpy(np.array(rows, np.float64).reshape(len(rows), 7)).to(d.dev) if rows else None
-            mark_t = torch.tensor(mark, dtype=torch.int32).to(d.dev) if mark else None
-            desc, bufs = self._desc(), self._bufs()
-            d.lib.check(d.lib.lib().lfd_eval_append_rows_f64(C.byref(desc), C.byref(bufs), d.lib.ptr(rows_t), len(rows),
-                                                             d.lib.ptr(mark_t), len(mark), d.lib.stream_ptr()),
-                        'lfd_eval_append_rows_f64')
+        self._append_rows('lfd_eval_append_rows_f64', rows, 7, mark)
         self._host_rows += len(rows)
 
     def update_resident(self, outputs, meta_batch):
         """Appends the kept boxes of an ops.DetectOutputs (LFD.detect / detect_resident) on the device: no .item(),
         .tolist(), .cpu() or synchronisation; the number of kept boxes is read from outputs.counts by the kernel.  The only
         host -> device traffic is the batch's image ordinals (pinned, asynchronous)."""
-        n, cap = int(outputs.dets.size(0)), int(outputs.dets.size(1))
-        if len(meta_batch) != n:
-            raise ValueError('%d meta entries for a batch of %d' % (len(meta_batch), n))
-        ords = self._ordinals(meta_batch)
-        d = self._state()
-        torch = d.torch
-        if outputs.dets.device != d.dev:
-            raise RuntimeError('update_resident: the outputs live on %s, the evaluator on %s' % (outputs.dets.device, d.dev))
-        self._upper += n * cap
-        self._reserve(self._upper)
-        with torch.cuda.device(d.dev):
-            host = torch.empty(n, dtype=torch.int32, pin_memory=True)
-            host.numpy()[:] = ords
-            ord_t = host.to(d.dev, non_blocking=True)
-            desc, bufs = self._desc(), self._bufs()
-            d.lib.check(d.lib.lib().lfd_eval_append_dets_f32(C.byref(desc), C.byref(bufs), d.lib.ptr(outputs.dets),
-                                                             d.lib.ptr(outputs.labels), d.lib.ptr(outputs.counts), n, cap,
-                                                             d.lib.ptr(d.label_map), int(d.label_map.numel()), d.lib.ptr(ord_t),
-                                                             int(self._all_images), d.lib.stream_ptr()),
-                        'lfd_eval_append_dets_f32')
+        self._append_resident('lfd_eval_append_dets_f32', outputs, meta_batch,
+                              lambda d, ords: (d.lib.ptr(d.label_map), int(d.label_map.numel()), ords, int(self._all_images)))
         self._resident_calls += 1
 
     # ------------------------------------------------------------------ evaluation
@@ -329,10 +404,7 @@ class COCOEvaluator(Evaluator):
             self._last['n_det'] = n_det
         self._clear()
         if err:
-            msgs = [m for bit, m in ((ERR_CAPACITY, 'the detection store overflowed'), (ERR_IMAGE, 'an image ordinal was out of range'),
-                                     (ERR_LABEL, 'a detection carried a label that label_indexes_to_category_ids does not map'))
-                    if err & bit]
-            raise RuntimeError('COCOEvaluator: ' + '; '.join(msgs) + ' (status bits %d); the accumulated detections were dropped' % err)
+            raise self._status_error(err)
         if n_det == 0:
             self._eval_display_str = format_display(None)
             return
@@ -354,13 +426,8 @@ class COCOEvaluator(Evaluator):
                     matched=unpack(self._last['match_bits']), ignored=unpack(self._last['ignore_bits']), npig=self._last['npig'])
 
     def _clear(self):
-        self._host_rows = self._resident_calls = self._upper = 0
-        if self._dev is not None:
-            self._dev.state.zero_()
-            self._dev.img_mask.zero_()
-
-    def get_eval_display_str(self):
-        return self._eval_display_str
+        self._host_rows = self._resident_calls = 0
+        super(COCOEvaluator, self)._clear()
 
 
 # ====================================================================== TT100K: the dataset's official accuracy / recall
@@ -409,7 +476,7 @@ def _as_list(v):
     return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v]
 
 
-class TT100KEvaluator(Evaluator):
+class TT100KEvaluator(_DeviceEvaluator):
     """The TT100K protocol as config_dict['evaluator']: `update`, `update_resident`, `evaluate`, `get_eval_display_str` as
     COCOEvaluator.  The defaults reproduce the reference's call (iou 0.5, minscore 90, sizes [0, 400), the 45 types,
     check_type and match_same on).
@@ -438,18 +505,10 @@ class TT100KEvaluator(Evaluator):
         if not self.ious or not self.minscores or not self.size_ranges or any(len(r) != 2 for r in self.size_ranges):
             raise ValueError('iou, minscore and size_ranges need at least one entry each; a size range is (min, max)')
         self.check_type, self.match_same = bool(check_type), bool(match_same)
-        self._device = device
-        self._eval_display_str = ''
         self._parse(annotations)
         self.right = self.num_detections = self.num_ground_truth = self.accuracy = self.recall = None
         self.right_per_category = self.num_detections_per_category = self.num_ground_truth_per_category = None
-        self._dev = None
-        self._seen = set()         # image ordinals since the last evaluate()
-        self._upper = 0            # upper bound of the detections stored on the device
-        self._last = None
-        import torch
-        if torch.cuda.is_available():
-            self._state()
+        self._start(device)
 
     # ------------------------------------------------------------------ ground truth (host)
     def _parse(self, ann):
@@ -486,17 +545,12 @@ class TT100KEvaluator(Evaluator):
                 self._label_map[lab] = cats[name]
 
     # ------------------------------------------------------------------ device state
-    def _state(self):
-        if self._dev is not None:
-            return self._dev
-        import torch
-        from . import _lib
-        if not torch.cuda.is_available():
-            raise RuntimeError('TT100KEvaluator: the evaluation kernels run on the MI355X only; there is no CPU implementation')
-        dev = torch.device(self._device) if self._device is not None else torch.device('cuda', torch.cuda.current_device())
-        d = type('EvalDeviceState', (), {})()
-        d.torch, d.lib, d.dev = torch, _lib, dev
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    _BUFS = ('img_mask', 'gt_box', 'gt_cat', 'gt_start', 'cat_in_types', 'ious', 'minscores', 'size_ranges')
+    _BUFS_STRUCT = 'TT100KEvalBufs'
+    _ERR_LABEL = 'a detection carried a label that label_indexes_to_category_names does not name'
+    _image_key = staticmethod(str)
+
+    def _upload(self, d, up):
         G = len(self.gt_cat)
         d.gt_box = up(self.gt_box if G else np.zeros((1, 4)))
         d.gt_cat = up(self.gt_cat if G else np.zeros(1, np.int32))
@@ -506,28 +560,6 @@ class TT100KEvaluator(Evaluator):
         d.minscores = up(np.array([float(v) for v in self.minscores], np.float64))
         d.size_ranges = up(np.array([[float(lo), float(hi)] for lo, hi in self.size_ranges], np.float64))
         d.label_map = up(self._label_map)
-        d.state = torch.zeros(4, dtype=torch.int32, device=dev)
-        d.img_mask = torch.zeros(len(self.image_ids), dtype=torch.int32, device=dev)
-        d.cap = 0
-        d.det_box = d.det_score = d.det_img = d.det_cat = None
-        self._dev = d
-        self._reserve(1 << 16)
-        return d
-
-    def _reserve(self, need):
-        """grow the detection store to hold `need` entries (device-to-device copies on the current stream, no sync)"""
-        d = self._dev
-        if need <= d.cap:
-            return
-        torch = d.torch
-        cap = max(int(need), 2 * d.cap)
-        new = [torch.empty((cap, 4), dtype=torch.float64, device=d.dev), torch.empty(cap, dtype=torch.float64, device=d.dev),
-               torch.empty(cap, dtype=torch.int32, device=d.dev), torch.empty(cap, dtype=torch.int32, device=d.dev)]
-        if d.cap:
-            for n, o in zip(new, (d.det_box, d.det_score, d.det_img, d.det_cat)):
-                n[:d.cap].copy_(o)
-        d.det_box, d.det_score, d.det_img, d.det_cat = new
-        d.cap = cap
 
     def _desc(self):
         d = self._dev
@@ -538,38 +570,11 @@ class TT100KEvaluator(Evaluator):
         desc.check_type, desc.match_same = int(self.check_type), int(self.match_same)
         return desc
 
-    def _bufs(self, **extra):
-        d = self._dev
-        b = d.lib.TT100KEvalBufs()
-        for k in ('det_box', 'det_score', 'det_img', 'det_cat', 'state', 'img_mask', 'gt_box', 'gt_cat', 'gt_start', 'cat_in_types',
-                  'ious', 'minscores', 'size_ranges'):
-            setattr(b, k, getattr(d, k).data_ptr())
-        for k, t in extra.items():
-            setattr(b, k, t.data_ptr() if t is not None else None)
-        return b
-
-    def _ordinals(self, meta_batch):
-        """image ordinals of a batch; an unknown id, or one that already arrived since the last evaluate(), is a ValueError"""
-        ords = []
-        for m in meta_batch:
-            key = str(m['image_id'])
-            if key not in self._img_ord:
-                raise ValueError('image id %r is not in the annotations' % key)
-            o = self._img_ord[key]
-            if o in self._seen or o in ords:
-                raise ValueError('image id %r arrived twice before evaluate()' % key)
-            ords.append(o)
-        return ords
-
     # ------------------------------------------------------------------ accumulation
     def update(self, results):
         """results: tuple(predict_results, meta_batch); predict_results[i] is a list of [label, score, x, y, w, h] rows for
         image meta_batch[i]['image_id'] (what LFD.get_results / predict_for_single_image return)."""
-        if not (isinstance(results, tuple) and len(results) == 2):
-            raise TypeError('update info should contain two parts: predict bboxes and meta info.')
-        predict_results, meta_batch = results
-        if len(predict_results) != len(meta_batch):
-            raise ValueError('%d prediction lists for %d meta entries' % (len(predict_results), len(meta_batch)))
+        predict_results, meta_batch = self._split(results)
         ords = self._ordinals(meta_batch)
         rows = []
         for o, boxes in zip(ords, predict_results):
@@ -579,17 +584,7 @@ class TT100KEvaluator(Evaluator):
                 rows.append((o, self._cat_idx[self._names[r[0]]], r[1], r[2], r[3], r[4], r[5]))
         if not ords:
             return
-        d = self._state()
-        torch = d.torch
-        self._upper += len(rows)
-        self._reserve(self._upper)
-        with torch.cuda.device(d.dev):
-            rows_t = torch.from_numpy(np.array(rows, np.float64).reshape(len(rows), 7)).to(d.dev) if rows else None
-            mark_t = torch.tensor(ords, dtype=torch.int32).to(d.dev)
-            desc, bufs = self._desc(), self._bufs()
-            d.lib.check(d.lib.lib().lfd_eval_tt100k_append_rows_f64(C.byref(desc), C.byref(bufs), d.lib.ptr(rows_t), len(rows),
-                                                                    d.lib.ptr(mark_t), len(ords), d.lib.stream_ptr()),
-                        'lfd_eval_tt100k_append_rows_f64')
+        self._append_rows('lfd_eval_tt100k_append_rows_f64', rows, 7, ords)
         self._seen.update(ords)
 
     def update_resident(self, outputs, meta_batch):
@@ -597,26 +592,8 @@ class TT100KEvaluator(Evaluator):
         .tolist(), .cpu() or synchronisation; the number of kept boxes is read from outputs.counts by the kernel, which also
         does the reference's arithmetic (fp32 w = x2 - x1 + 1, float64 xmax = w + x1, score * 100).  The only host -> device
         traffic is the batch's image ordinals (pinned, asynchronous)."""
-        n, cap = int(outputs.dets.size(0)), int(outputs.dets.size(1))
-        if len(meta_batch) != n:
-            raise ValueError('%d meta entries for a batch of %d' % (len(meta_batch), n))
-        ords = self._ordinals(meta_batch)
-        d = self._state()
-        torch = d.torch
-        if outputs.dets.device != d.dev:
-            raise RuntimeError('update_resident: the outputs live on %s, the evaluator on %s' % (outputs.dets.device, d.dev))
-        self._upper += n * cap
-        self._reserve(self._upper)
-        with torch.cuda.device(d.dev):
-            host = torch.empty(n, dtype=torch.int32, pin_memory=True)
-            host.numpy()[:] = ords
-            ord_t = host.to(d.dev, non_blocking=True)
-            desc, bufs = self._desc(), self._bufs()
-            d.lib.check(d.lib.lib().lfd_eval_tt100k_append_dets_f32(C.byref(desc), C.byref(bufs), d.lib.ptr(outputs.dets),
-                                                                    d.lib.ptr(outputs.labels), d.lib.ptr(outputs.counts), n, cap,
-                                                                    d.lib.ptr(d.label_map), int(d.label_map.numel()),
-                                                                    d.lib.ptr(ord_t), d.lib.stream_ptr()),
-                        'lfd_eval_tt100k_append_dets_f32')
+        ords = self._append_resident('lfd_eval_tt100k_append_dets_f32', outputs, meta_batch,
+                                     lambda d, ords: (d.lib.ptr(d.label_map), int(d.label_map.numel()), ords))
         self._seen.update(ords)
 
     # ------------------------------------------------------------------ evaluation
@@ -680,10 +657,7 @@ class TT100KEvaluator(Evaluator):
                                   gt_code=out['gt_code'][..., :len(self.gt_cat)].cpu().numpy())
             self._clear()
             if err:
-                msgs = [m for bit, m in ((ERR_CAPACITY, 'the detection store overflowed'), (ERR_IMAGE, 'an image ordinal was out of range'),
-                                         (ERR_LABEL, 'a detection carried a label that label_indexes_to_category_names does not name'))
-                        if err & bit]
-                raise RuntimeError('TT100KEvaluator: ' + '; '.join(msgs) + ' (status bits %d); the accumulated detections were dropped' % err)
+                raise self._status_error(err)
         self.right, self.num_detections, self.num_ground_truth = tot[..., 0].copy(), tot[..., 1].copy(), tot[..., 2].copy()
         ratios = lambda n: np.array([float(_ratio(int(r), int(v))) for r, v in zip(self.right.ravel(), n.ravel())],   # noqa: E731
                                     np.float64).reshape(T, M, S)
@@ -728,16 +702,6 @@ class TT100KEvaluator(Evaluator):
         start = L['det_start']
         return dict(image=np.repeat(np.arange(len(start) - 1), np.diff(start)), index=L['det_index'], det_start=start,
                     det_code=L['det_code'][t, m, s], det_gt=L['det_gt'][t, m], gt_code=L['gt_code'][t, m, s], gt_start=self.gt_start)
-
-    def _clear(self):
-        self._seen = set()
-        self._upper = 0
-        if self._dev is not None:
-            self._dev.state.zero_()
-            self._dev.img_mask.zero_()
-
-    def get_eval_display_str(self):
-        return self._eval_display_str
 
 
 # ====================================================================== WIDERFACE: easy / medium / hard AP
@@ -862,7 +826,7 @@ def load_widerface_mat(gt_dir):
     return annotations
 
 
-class WIDERFACEEvaluator(Evaluator):
+class WIDERFACEEvaluator(_DeviceEvaluator):
     """The WIDERFACE protocol as config_dict['evaluator']: `update`, `update_resident`, `evaluate`, `get_eval_display_str` as
     the other two evaluators; evaluate() returns {'easy': ap, 'medium': ap, 'hard': ap}.  The definition is DESIGN.md 9c: a
     restatement of the dataset's eval_tools (wider_eval.m, evaluation.m, read_pred.m, norm_score.m, boxoverlap.m) and VOC's
@@ -885,18 +849,10 @@ class WIDERFACEEvaluator(Evaluator):
         self.label_index = None if label_index is None else int(label_index)
         if self.label_index is not None and self.label_index < 0:
             raise ValueError('label_index must not be negative')
-        self._device = device
-        self._eval_display_str = ''
         self.thr = widerface_thresholds()
         self._parse(annotations)
         self.ap = self.curve = self.faces = self.precision = self.recall = None
-        self._dev = None
-        self._seen = set()         # image ordinals since the last evaluate()
-        self._upper = 0            # upper bound of the detections stored on the device
-        self._last = None
-        import torch
-        if torch.cuda.is_available():
-            self._state()
+        self._start(device)
 
     # ------------------------------------------------------------------ ground truth (host)
     def _parse(self, annotations):
@@ -923,42 +879,15 @@ class WIDERFACEEvaluator(Evaluator):
         self.keep_len = np.array(keep_len, np.int32).reshape(len(annotations), 3)
 
     # ------------------------------------------------------------------ device state
-    def _state(self):
-        if self._dev is not None:
-            return self._dev
-        import torch
-        from . import _lib
-        if not torch.cuda.is_available():
-            raise RuntimeError('WIDERFACEEvaluator: the evaluation kernels run on the MI355X only; there is no CPU implementation')
-        dev = torch.device(self._device) if self._device is not None else torch.device('cuda', torch.cuda.current_device())
-        d = type('EvalDeviceState', (), {})()
-        d.torch, d.lib, d.dev = torch, _lib, dev
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    _STORE = ('det_box', 'det_score', 'det_img')                 # one class, and no img_mask
+    _BUFS = ('gt_box', 'gt_start', 'gt_kept', 'keep_len', 'thr')
+    _BUFS_STRUCT = 'WFEvalBufs'
+
+    def _upload(self, d, up):
         G = len(self.gt_kept)
         d.gt_box = up(self.gt_box if G else np.zeros((1, 4)))
         d.gt_kept = up(self.gt_kept if G else np.zeros(1, np.uint8))
         d.gt_start, d.keep_len, d.thr = up(self.gt_start), up(self.keep_len), up(self.thr)
-        d.state = torch.zeros(4, dtype=torch.int32, device=dev)
-        d.cap = 0
-        d.det_box = d.det_score = d.det_img = None
-        self._dev = d
-        self._reserve(1 << 16)
-        return d
-
-    def _reserve(self, need):
-        """grow the detection store to hold `need` entries (device-to-device copies on the current stream, no sync)"""
-        d = self._dev
-        if need <= d.cap:
-            return
-        torch = d.torch
-        cap = max(int(need), 2 * d.cap)
-        new = [torch.empty((cap, 4), dtype=torch.float64, device=d.dev), torch.empty(cap, dtype=torch.float64, device=d.dev),
-               torch.empty(cap, dtype=torch.int32, device=d.dev)]
-        if d.cap:
-            for n, o in zip(new, (d.det_box, d.det_score, d.det_img)):
-                n[:d.cap].copy_(o)
-        d.det_box, d.det_score, d.det_img = new
-        d.cap = cap
 
     def _desc(self):
         d = self._dev
@@ -970,38 +899,12 @@ class WIDERFACEEvaluator(Evaluator):
         desc.iou_thresh = self.iou_thresh
         return desc
 
-    def _bufs(self, **extra):
-        d = self._dev
-        b = d.lib.WFEvalBufs()
-        for k in ('det_box', 'det_score', 'det_img', 'state', 'gt_box', 'gt_start', 'gt_kept', 'keep_len', 'thr'):
-            setattr(b, k, getattr(d, k).data_ptr())
-        for k, t in extra.items():
-            setattr(b, k, t.data_ptr() if t is not None else None)
-        return b
-
-    def _ordinals(self, meta_batch):
-        """image ordinals of a batch; an unknown id, or one that already arrived since the last evaluate(), is a ValueError"""
-        ords = []
-        for m in meta_batch:
-            key = m['image_id']
-            if key not in self._img_ord:
-                raise ValueError('image id %r is not in the annotations' % (key,))
-            o = self._img_ord[key]
-            if o in self._seen or o in ords:
-                raise ValueError('image id %r arrived twice before evaluate()' % (key,))
-            ords.append(o)
-        return ords
-
     # ------------------------------------------------------------------ accumulation
     def update(self, results):
         """results: tuple(predict_bboxes, meta_batch); predict_bboxes[i] is a list of [label, score, x, y, w, h] rows for
         image meta_batch[i]['image_id'] (what LFD.get_results / predict_for_single_image return).  With as_written the rows
         are quantised here, on the host, with the reference's own Python expressions."""
-        if not (isinstance(results, tuple) and len(results) == 2):
-            raise TypeError('update info should contain two parts: predict bboxes and meta info.')
-        predict_bboxes, meta_batch = results
-        if len(predict_bboxes) != len(meta_batch):
-            raise ValueError('%d prediction lists for %d meta entries' % (len(predict_bboxes), len(meta_batch)))
+        predict_bboxes, meta_batch = self._split(results)
         ords = self._ordinals(meta_batch)
         rows = []
         for o, boxes in zip(ords, predict_bboxes):
@@ -1019,40 +922,14 @@ class WIDERFACEEvaluator(Evaluator):
         self._seen.update(ords)
         if not rows:
             return
-        d = self._state()
-        torch = d.torch
-        self._upper += len(rows)
-        self._reserve(self._upper)
-        with torch.cuda.device(d.dev):
-            rows_t = torch.from_numpy(np.array(rows, np.float64).reshape(len(rows), 6)).to(d.dev)
-            desc, bufs = self._desc(), self._bufs()
-            d.lib.check(d.lib.lib().lfd_eval_wf_append_rows_f64(C.byref(desc), C.byref(bufs), d.lib.ptr(rows_t), len(rows),
-                                                                d.lib.stream_ptr()), 'lfd_eval_wf_append_rows_f64')
+        self._append_rows('lfd_eval_wf_append_rows_f64', rows, 6)
 
     def update_resident(self, outputs, meta_batch):
         """Appends the kept boxes of an ops.DetectOutputs (LFD.detect / detect_resident) on the device: no .item(),
         .tolist(), .cpu() or synchronisation; the number of kept boxes is read from outputs.counts by the kernel, which also
         forms w = x2 - x1 + 1 and h in fp32 (the two roundings of LFD._pack) and, with as_written, does the quantisation and
         adds the dummy row.  The only host -> device traffic is the batch's image ordinals (pinned, asynchronous)."""
-        n, cap = int(outputs.dets.size(0)), int(outputs.dets.size(1))
-        if len(meta_batch) != n:
-            raise ValueError('%d meta entries for a batch of %d' % (len(meta_batch), n))
-        ords = self._ordinals(meta_batch)
-        d = self._state()
-        torch = d.torch
-        if outputs.dets.device != d.dev:
-            raise RuntimeError('update_resident: the outputs live on %s, the evaluator on %s' % (outputs.dets.device, d.dev))
-        self._upper += n * (cap + 1)
-        self._reserve(self._upper)
-        with torch.cuda.device(d.dev):
-            host = torch.empty(n, dtype=torch.int32, pin_memory=True)
-            host.numpy()[:] = ords
-            ord_t = host.to(d.dev, non_blocking=True)
-            desc, bufs = self._desc(), self._bufs()
-            d.lib.check(d.lib.lib().lfd_eval_wf_append_dets_f32(C.byref(desc), C.byref(bufs), d.lib.ptr(outputs.dets),
-                                                                d.lib.ptr(outputs.labels), d.lib.ptr(outputs.counts), n, cap,
-                                                                d.lib.ptr(ord_t), d.lib.stream_ptr()),
-                        'lfd_eval_wf_append_dets_f32')
+        ords = self._append_resident('lfd_eval_wf_append_dets_f32', outputs, meta_batch, lambda d, ords: (ords,), dummy_rows=1)
         self._seen.update(ords)
 
     # ------------------------------------------------------------------ evaluation
@@ -1112,9 +989,7 @@ class WIDERFACEEvaluator(Evaluator):
                     self._last[k] = out[k][:, :n].cpu().numpy()
             self._clear()
             if err:
-                msgs = [m for bit, m in ((ERR_CAPACITY, 'the detection store overflowed'), (ERR_IMAGE, 'an image ordinal was out of range'))
-                        if err & bit]
-                raise RuntimeError('WIDERFACEEvaluator: ' + '; '.join(msgs) + ' (status bits %d); the accumulated detections were dropped' % err)
+                raise self._status_error(err)
         self.curve, self.faces = curve, faces
         self.precision, self.recall, self.ap = widerface_ap(curve, faces)
         self._eval_display_str = '\n' + ''.join('{:<10}:{:.5f}\n'.format(name + ' AP', self.ap[i]) for i, name in enumerate(DIFFICULTIES))
@@ -1138,12 +1013,3 @@ class WIDERFACEEvaluator(Evaluator):
         flags = L['det_flags'][sel]
         return dict(image=image[sel], index=L['det_index'][sel], rank=rank[sel], m=L['det_gt'][sel], over=(flags & 1).astype(bool),
                     proposal=((flags >> (1 + d)) & 1).astype(bool), rec=L['det_rec'][d][sel])
-
-    def _clear(self):
-        self._seen = set()
-        self._upper = 0
-        if self._dev is not None:
-            self._dev.state.zero_()
-
-    def get_eval_display_str(self):
-        return self._eval_display_str
