@@ -976,7 +976,9 @@ LFD_API int lfd_rows_sum_batched_f32(const lfd_rowsum_job_t* jobs_device, int32_
  *   lfd_head_out_grad_f16: from grad (same layout as out) writes dy [n, hw, 64] fp16 = grad (* *scale) * loss_scale (other rows
  *     zero) and ACCUMULATES dbias[j] += sum grad (* *scale), *dscale += sum grad * float(y) (both nullable) through per-block
  *     partials in `workspace` (>= 512 KB) and one fixed-order fp64 final launch: what autograd computes for
- *     conv bias / Scale, as 2 launches instead of ~20 per level. */
+ *     conv bias / Scale, as 2 launches instead of ~20 per level.
+ * `y` and `dy` must be 16-byte aligned (forward and backward move a pixel's line in 16-byte pieces); a misaligned pointer
+ * returns LFD_ERR_INVALID_ARGUMENT. */
 typedef struct lfd_head_out_seg {
   float* out;          /* split: destination */
   const float* grad;   /* grad: source */
@@ -1011,14 +1013,15 @@ LFD_API int lfd_head_out_grad_levels_f16(const void* y_concat, int32_t n, int64_
                                  int32_t nlevels, float loss_scale, void* dy_concat, void* workspace, size_t workspace_bytes,
                                  lfd_stream_t stream);
 
-/* The six entry points above for an output conv padded to `rows` output rows (csrc/head_out_wide.hip): `rows` is 64 or 128,
- * anything else returns LFD_ERR_INVALID_ARGUMENT.  rows == 64 forwards to the entry point above of the same name; rows == 128
- * serves heads whose level needs more than 64 rows (a merged head with 61..124 class channels + 4 regression rows, separate
- * towers with up to 128 class channels): `y` / `dy` are [n, hw, 128] (`_concat` / `_levels`: [n, points_total, 128]) fp16, a
- * segment must satisfy row0 + channels <= 128, and n * hw * 128 < 2^31.  Same values as the 64-row kernels compute for the
- * same segments: out and dy are single roundings of the fp32 products, rows of dy outside every segment are zero, dbias / dscale
- * accumulate through per-block partials and one fixed-order fp64 final launch.  `workspace` of the 128-row gradient entry
- * points: >= 1 MB (1024 blocks x 2 x 128 floats), `_levels`: >= nlevels x 1 MB; lfd_train_workspace_bytes() covers both. */
+/* The six entry points above for an output conv padded to `rows` output rows: `rows` is 64 or 128, the two instantiations of
+ * the one row-width-templated implementation in csrc/head_out.hip; anything else returns LFD_ERR_INVALID_ARGUMENT.  rows == 64
+ * runs the kernels of the entry point above of the same name; rows == 128 serves heads whose level needs more than 64 rows (a
+ * merged head with 61..124 class channels + 4 regression rows, separate towers with up to 128 class channels): `y` / `dy` are
+ * [n, hw, 128] (`_concat` / `_levels`: [n, points_total, 128]) fp16, 16-byte aligned as above, a segment must satisfy
+ * row0 + channels <= 128, and n * hw * 128 < 2^31.  Same values as the 64-row kernels compute for the same segments: out and dy
+ * are single roundings of the fp32 products, rows of dy outside every segment are zero, dbias / dscale accumulate through
+ * per-block partials and one fixed-order fp64 final launch.  `workspace` of the 128-row gradient entry points: >= 1 MB (1024
+ * blocks x 2 x 128 floats), `_levels`: >= nlevels x 1 MB; lfd_train_workspace_bytes() covers both. */
 LFD_API int lfd_head_out_split_w_f16(const void* y, int32_t n, int32_t hw, int64_t points_total, int64_t point0,
                              const lfd_head_out_seg_t* segs, int32_t nsegs, int32_t rows, lfd_stream_t stream);
 LFD_API int lfd_head_out_grad_w_f16(const void* y, int32_t n, int32_t hw, int64_t points_total, int64_t point0,

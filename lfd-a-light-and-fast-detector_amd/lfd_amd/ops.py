@@ -1347,11 +1347,18 @@ def _head_out_segs(segs, field, tensors):
 
 
 def _head_out_rows(y, what):
-    """output rows of the padded conv whose output `y` is: 64 (csrc/head_out.hip) or 128 (csrc/head_out_wide.hip)"""
+    """output rows of the padded conv whose output `y` is: 64 or 128, the two instantiations of csrc/head_out.hip"""
     rows = y.size(-1)
     if rows not in (64, 128):
         raise RuntimeError('%s: 64 or 128 output rows expected, got %d' % (what, rows))
     return rows
+
+
+def _head_out_call(name, rows, head, tail):
+    """lfd_<name>_f16(*head, *tail) for 64 rows -- the entry points the shipped models have always called --,
+    lfd_<name>_w_f16(*head, rows, *tail) for 128"""
+    entry = 'lfd_%s_f16' % name if rows == 64 else 'lfd_%s_w_f16' % name
+    check(getattr(lib(), entry)(*(head if rows == 64 else head + (rows,)), *tail), entry)
 
 
 def head_out_split_concat(y_concat, hw, segs, outs, point0):
@@ -1361,12 +1368,8 @@ def head_out_split_concat(y_concat, hw, segs, outs, point0):
     rows = _head_out_rows(y_concat, 'head_out_split_concat')
     arr = _head_out_segs(segs, 'out', outs)
     with torch.cuda.device(y_concat.device):
-        if rows == 64:
-            check(lib().lfd_head_out_split_concat_f16(ptr(y_concat), n, int(hw), outs[0].size(1), int(point0), arr, len(segs),
-                                                      stream_ptr()), 'lfd_head_out_split_concat_f16')
-        else:
-            check(lib().lfd_head_out_split_concat_w_f16(ptr(y_concat), n, int(hw), outs[0].size(1), int(point0), arr, len(segs),
-                                                        rows, stream_ptr()), 'lfd_head_out_split_concat_w_f16')
+        _head_out_call('head_out_split_concat', rows, (ptr(y_concat), n, int(hw), outs[0].size(1), int(point0), arr, len(segs)),
+                       (stream_ptr(),))
 
 
 def head_out_grad_concat(y_concat, hw, segs, grads, point0, loss_scale, dy_concat):
@@ -1377,14 +1380,8 @@ def head_out_grad_concat(y_concat, hw, segs, grads, point0, loss_scale, dy_conca
     arr = _head_out_segs(segs, 'grad', grads)
     ws = train_workspace(y_concat.device)       # (covers the 1 MB per level of the 128-row partials too)
     with torch.cuda.device(y_concat.device):
-        if rows == 64:
-            check(lib().lfd_head_out_grad_concat_f16(ptr(y_concat), n, int(hw), grads[0].size(1), int(point0), arr, len(segs),
-                                                     float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
-                  'lfd_head_out_grad_concat_f16')
-        else:
-            check(lib().lfd_head_out_grad_concat_w_f16(ptr(y_concat), n, int(hw), grads[0].size(1), int(point0), arr, len(segs),
-                                                       rows, float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
-                  'lfd_head_out_grad_concat_w_f16')
+        _head_out_call('head_out_grad_concat', rows, (ptr(y_concat), n, int(hw), grads[0].size(1), int(point0), arr, len(segs)),
+                       (float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()))
 
 
 def _head_out_levels(levels, field):
@@ -1405,12 +1402,8 @@ def head_out_split_levels(y_concat, levels):
     rows = _head_out_rows(y_concat, 'head_out_split_levels')
     arr = _head_out_levels(levels, 'out')
     with torch.cuda.device(y_concat.device):
-        if rows == 64:
-            check(lib().lfd_head_out_split_levels_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
-                                                      stream_ptr()), 'lfd_head_out_split_levels_f16')
-        else:
-            check(lib().lfd_head_out_split_levels_w_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
-                                                        rows, stream_ptr()), 'lfd_head_out_split_levels_w_f16')
+        _head_out_call('head_out_split_levels', rows, (ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels)),
+                       (stream_ptr(),))
 
 
 def head_out_grad_levels(y_concat, levels, loss_scale, dy_concat):
@@ -1422,14 +1415,8 @@ def head_out_grad_levels(y_concat, levels, loss_scale, dy_concat):
     arr = _head_out_levels(levels, 'grad')
     ws = train_workspace(y_concat.device)
     with torch.cuda.device(y_concat.device):
-        if rows == 64:
-            check(lib().lfd_head_out_grad_levels_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
-                                                     float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
-                  'lfd_head_out_grad_levels_f16')
-        else:
-            check(lib().lfd_head_out_grad_levels_w_f16(ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels),
-                                                       rows, float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()),
-                  'lfd_head_out_grad_levels_w_f16')
+        _head_out_call('head_out_grad_levels', rows, (ptr(y_concat), y_concat.size(0), levels[0][3][0].size(1), arr, len(levels)),
+                       (float(loss_scale), ptr(dy_concat), ptr(ws), ws.numel(), stream_ptr()))
 
 
 def head_out_split(y, segs, outs, point0):
@@ -1444,12 +1431,7 @@ def head_out_split(y, segs, outs, point0):
             raise RuntimeError('head_out_split: outs must be contiguous fp32 [n, P, channels]')
     arr = _head_out_segs(segs, 'out', outs)
     with torch.cuda.device(y.device):
-        if rows == 64:
-            check(lib().lfd_head_out_split_f16(ptr(y), n, h * w_, outs[0].size(1), int(point0), arr, len(segs), stream_ptr()),
-                  'lfd_head_out_split_f16')
-        else:
-            check(lib().lfd_head_out_split_w_f16(ptr(y), n, h * w_, outs[0].size(1), int(point0), arr, len(segs), rows,
-                                                 stream_ptr()), 'lfd_head_out_split_w_f16')
+        _head_out_call('head_out_split', rows, (ptr(y), n, h * w_, outs[0].size(1), int(point0), arr, len(segs)), (stream_ptr(),))
 
 
 def head_out_grad(y, segs, grads, point0, loss_scale):
@@ -1470,13 +1452,8 @@ def head_out_grad(y, segs, grads, point0, loss_scale):
     ws = train_workspace(y.device)
     with torch.cuda.device(y.device):
         dy = torch.empty_like(y)
-        if rows == 64:
-            check(lib().lfd_head_out_grad_f16(ptr(y), n, h * w_, grads[0].size(1), int(point0), arr, len(segs), float(loss_scale),
-                                              ptr(dy), ptr(ws), ws.numel(), stream_ptr()), 'lfd_head_out_grad_f16')
-        else:
-            check(lib().lfd_head_out_grad_w_f16(ptr(y), n, h * w_, grads[0].size(1), int(point0), arr, len(segs), rows,
-                                                float(loss_scale), ptr(dy), ptr(ws), ws.numel(), stream_ptr()),
-                  'lfd_head_out_grad_w_f16')
+        _head_out_call('head_out_grad', rows, (ptr(y), n, h * w_, grads[0].size(1), int(point0), arr, len(segs)),
+                       (float(loss_scale), ptr(dy), ptr(ws), ws.numel(), stream_ptr()))
     return dy
 
 

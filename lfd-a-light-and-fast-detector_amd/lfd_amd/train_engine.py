@@ -88,7 +88,7 @@ def check_train_input(backbone, x):
 
 def network_supported(model):
     """+ SimpleNeck with BatchNorm2d, LFDHead with 1x1 convs and GroupNorm groups of 8 channels, and output convs that fit the
-    padded 1x1 conv of a level (_out_weight: 64 or 128 rows, csrc/head_out.hip / head_out_wide.hip):
+    padded 1x1 conv of a level (_out_weight: 64 or 128 rows, the two instantiations of csrc/head_out.hip):
       - cls and reg conv reading the same activation (merge_path_flag, or no tower layers) run as ONE conv:
         num_cls_channels + 4 <= 128  (<= 60: the 64-row kernels; 61..124: the 128-row ones)
       - separate towers, one conv each: num_cls_channels <= 128

@@ -1,4 +1,4 @@
-"""csrc/head_out_wide.hip -- the glue around output convs padded to 128 rows -- and what it opens: heads with up to 124 (merged)
+"""The 128-row instantiation of csrc/head_out.hip -- the glue around output convs padded to 128 rows -- and what it opens: heads with up to 124 (merged)
 / 128 (separate towers) class channels on the all-HIP training path, eager and as one graph.
 
 Kernel tests: against a plain torch restatement (split = float(y) * scale, dy = half(grad * scale * loss_scale), dbias / dscale
@@ -322,7 +322,7 @@ class _Recorder(object):
 
 def test_separate_towers_with_80_classes_run_wide_and_narrow_glue_in_one_iteration(monkeypatch):
     """TT100K_LFD_S's separate towers with an 80-class FocalLoss head: per level a 128-row class conv and a 64-row regression
-    conv, so both glue files serve one iteration.  Forward and loss from identical state against the module tree through
+    conv, so both instantiations of the glue serve one iteration.  Forward and loss from identical state against the module tree through
     PyTorch-ROCm autograd (1 % on the loss values: the iteration-1 gate of
     tests/test_train_golden.py::test_every_hip_iteration_from_the_fp32_routes_state for every case), then one whole train_step:
     nothing network_supported admits may fail at launch."""
