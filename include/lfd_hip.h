@@ -1494,6 +1494,44 @@ LFD_API size_t lfd_eval_wf_workspace_bytes(const lfd_eval_wf_desc_t* desc);
 LFD_API int lfd_eval_wf_match(const lfd_eval_wf_desc_t* desc, const lfd_eval_wf_bufs_t* bufs, void* workspace,
                               size_t workspace_bytes, lfd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Eval-mode BatchNorm inside a training iteration (csrc/train_bn_eval.hip): fine-tuning with LFDResNet(frozen_stages=k,
+ * norm_eval=True) (lfd/model/backbone/lfd_resnet.py:476-509).  An eval-mode norm normalises with its running statistics
+ * and updates nothing.
+ */
+/* running_mean / running_var / eps of every eval-mode norm -> its stats row float32[2 * channels] = (mean, 1 / sqrt(var + eps)),
+ * the layout lfd_bn_train_apply_f16 reads: one launch over a job table in device memory.  max_channels >= every job's channels. */
+typedef struct lfd_bn_eval_job {
+  const float* running_mean;
+  const float* running_var;
+  float* stats;
+  int32_t channels;
+  float eps;
+} lfd_bn_eval_job_t;
+LFD_API int lfd_bn_eval_stats_f32(const lfd_bn_eval_job_t* jobs_device, int32_t njobs, int32_t max_channels, lfd_stream_t stream);
+/* Frozen Conv2d(bias=False) -> eval-mode BatchNorm2d units as ONE conv with bias: w_out = w * gamma * rstd (per output row),
+ * bias_out = beta - mean * gamma * rstd, both fp32, from the stats rows above.  One launch over a job table in device memory,
+ * first_elem ascending from 0, total_elems = sum of cout * row_elems (row_elems = cin * ks * ks). */
+typedef struct lfd_bn_fold_job {
+  const float* w;
+  const float* gamma;
+  const float* beta;
+  const float* stats;
+  float* w_out;
+  float* bias_out;
+  int32_t cout, row_elems, first_elem, reserved_;
+} lfd_bn_fold_job_t;
+LFD_API int lfd_conv_bn_eval_fold_f32(const lfd_bn_fold_job_t* jobs_device, int32_t njobs, int32_t total_elems, lfd_stream_t stream);
+/* Backward of z = relu?(gamma * (y - mean) * rstd + beta (+ residual)) with CONSTANT (mean, rstd) in `stats`, in ONE pass over
+ * (dz, y):  g = dz * mask,  dy = gamma * rstd * g,  dgamma (+)= sum(g * xhat) * inv_scale,  dbeta (+)= sum(g) * inv_scale.
+ * Arguments as lfd_bn_train_bwd_f16: z nullable (with relu != 0 and z == NULL the mask is recomputed from y, beta required),
+ * g_out nullable (the gradient of the residual branch), dgamma / dbeta nullable together with the final launch, `workspace`
+ * lfd_train_workspace_bytes().  fp32 per-block partial sums + a fixed-order fp64 final: deterministic. */
+LFD_API int lfd_bn_eval_bwd_f16(const void* dz, const void* y, const void* z, int32_t relu, int64_t pixels, int32_t channels,
+                        const float* stats, const float* gamma, const float* beta, float inv_scale, int32_t accumulate,
+                        void* workspace, size_t workspace_bytes, float* dgamma, float* dbeta, void* dy, void* g_out,
+                        lfd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -171,6 +171,19 @@ class PackJob(C.Structure):
                 ('mode', C.c_int32), ('rows_valid', C.c_int32), ('first_vec', C.c_int32)]
 
 
+class BnEvalJob(C.Structure):
+    """lfd_bn_eval_job_t"""
+    _fields_ = [('running_mean', C.c_void_p), ('running_var', C.c_void_p), ('stats', C.c_void_p), ('channels', C.c_int32),
+                ('eps', C.c_float)]
+
+
+class BnFoldJob(C.Structure):
+    """lfd_bn_fold_job_t"""
+    _fields_ = [('w', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p), ('stats', C.c_void_p), ('w_out', C.c_void_p),
+                ('bias_out', C.c_void_p), ('cout', C.c_int32), ('row_elems', C.c_int32), ('first_elem', C.c_int32),
+                ('reserved_', C.c_int32)]
+
+
 class WgradJob(C.Structure):
     """lfd_wgrad_job_t"""
     _fields_ = [('partials', C.c_void_p), ('dw', C.c_void_p), ('nwg', C.c_int32), ('nblk', C.c_int32), ('cin', C.c_int32),
@@ -347,6 +360,9 @@ _SIGNATURES = {
     'lfd_stem_conv0_wgrad': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _SZ, _P, _P]),
     'lfd_stem_conv0_bn_bwd_wgrad': (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _I32, _P, _SZ, _P, _P, _P, _P]),
     'lfd_stem_conv0_bn_bwd_wgrad_rows': (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
+    'lfd_bn_eval_stats_f32': (C.c_int, [_P, _I32, _I32, _P]),
+    'lfd_conv_bn_eval_fold_f32': (C.c_int, [_P, _I32, _I32, _P]),
+    'lfd_bn_eval_bwd_f16': (C.c_int, [_P, _P, _P, _I32, _I64, _I32, _P, _P, _P, _F, _I32, _P, _SZ, _P, _P, _P, _P, _P]),
     'lfd_bn_train_bwd_rows_f16': (C.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _F, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
     'lfd_conv1x1_dgrad_bn_bwd_sums_nhwc_f16': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, C.POINTER(C.c_int32), _P]),
     'lfd_stem_gray_train_fwd': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P]),

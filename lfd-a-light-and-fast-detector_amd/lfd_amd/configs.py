@@ -55,11 +55,11 @@ ARCHS = {
 
 
 def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, iou_cls, ce_cls, seed=666, qfl_cls=None,
-                  input_channels=3):
+                  input_channels=3, frozen_stages=-1, norm_eval=False):
     """Instantiates (backbone, neck, head, LFD) from `arch` with the given classes (this package's
     or the reference's -- identical kwargs), under torch.manual_seed(seed) (= the config seed,
     WIDERFACE_LFD_S.py:51).  input_channels=1: the grayscale twin (the task scripts' `input_channels`, BGR--3, gray--1,
-    TT100K_LFD_L.py:77-78)."""
+    TT100K_LFD_L.py:77-78).  frozen_stages / norm_eval: the backbone's fine-tuning options (lfd_resnet.py:476-509)."""
     torch.manual_seed(seed)
     if arch['classification_loss_type'] == 'CrossEntropyLoss':
         cls_loss = ce_cls(reduction='mean', loss_weight=1.0)
@@ -70,9 +70,9 @@ def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, io
     reg_loss = iou_cls(eps=1e-6, reduction='mean', loss_weight=1.0)
     bb = backbone_cls(block_mode=arch['block_mode'], stem_mode=arch['stem_mode'], body_mode=None, input_channels=input_channels,
                       stem_channels=arch['stem_channels'], body_architecture=list(arch['body_architecture']),
-                      body_channels=list(arch['body_channels']), out_indices=arch['out_indices'], frozen_stages=-1,
+                      body_channels=list(arch['body_channels']), out_indices=arch['out_indices'], frozen_stages=frozen_stages,
                       activation_cfg=dict(type='ReLU', inplace=True), norm_cfg=dict(type='BatchNorm2d'),
-                      init_with_weight_file=None, norm_eval=False)
+                      init_with_weight_file=None, norm_eval=norm_eval)
     neck = neck_cls(num_neck_channels=arch['num_neck_channels'], num_input_channels_list=bb.num_output_channels_list,
                     num_input_strides_list=bb.num_output_strides_list, norm_cfg=dict(type='BatchNorm2d'),
                     activation_cfg=dict(type='ReLU', inplace=True))
@@ -90,10 +90,12 @@ def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, io
     return model
 
 
-def build_model(name_or_arch, seed=666, input_channels=3, num_classes=None):
+def build_model(name_or_arch, seed=666, input_channels=3, num_classes=None, frozen_stages=-1, norm_eval=False):
     """This package's LFD for a named configuration; input_channels=1 builds its grayscale twin (same ARCHS entry, a
     one-channel first stem conv); num_classes=K the same configuration with a K-class head (the task scripts' `num_classes`,
-    WIDERFACE_LFD_S.py:79 -- 80 for a COCO parser)."""
+    WIDERFACE_LFD_S.py:79 -- 80 for a COCO parser).  frozen_stages=k > 0 freezes the backbone's stem and stage0 .. stage{k-1} (eval
+    mode, no gradients), norm_eval=True keeps every backbone BatchNorm2d on its running statistics while the model trains: the
+    fine-tuning options of LFDResNet (lfd_resnet.py:476-509), both on the all-HIP training path."""
     from .model.backbone import LFDResNet
     from .model.head import LFDHead
     from .model.lfd import LFD
@@ -105,7 +107,7 @@ def build_model(name_or_arch, seed=666, input_channels=3, num_classes=None):
             raise ValueError('num_classes must be >= 1')
         arch = dict(arch, num_classes=int(num_classes))
     return build_modules(arch, LFDResNet, SimpleNeck, LFDHead, LFD, FocalLoss, IoULoss, CrossEntropyLoss, seed, QualityFocalLoss,
-                         input_channels=input_channels)
+                         input_channels=input_channels, frozen_stages=int(frozen_stages), norm_eval=bool(norm_eval))
 
 
 def perturb_weights(model, seed=1):

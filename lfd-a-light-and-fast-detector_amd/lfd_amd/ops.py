@@ -964,6 +964,123 @@ def bn_train_backward(dz, y, z, stats, gamma, inv_scale, dgamma, dbeta, want_g=F
     return dy, g
 
 
+def bn_eval_backward(dz, y, z, stats, gamma, inv_scale, dgamma, dbeta, want_g=False, accumulate=False, relu=None, beta=None):
+    """bn_train_backward for an EVAL-mode norm (`stats` = the constant (mean, rstd) row of its running statistics,
+    BnEvalRows): one pass over (dz, y), dy = gamma * rstd * g (lfd_bn_eval_bwd_f16).  -> (dy, g)"""
+    relu = (z is not None) if relu is None else bool(relu)
+    _nhwc16(dz, 'bn_eval_backward')
+    _nhwc16(y, 'bn_eval_backward')
+    c = y.size(3)
+    if dz.shape != y.shape or (z is not None and z.shape != y.shape) or stats.numel() != 2 * c or gamma.numel() != c:
+        raise RuntimeError('bn_eval_backward: shape mismatch')
+    dy = torch.empty_like(y)
+    g = torch.empty_like(y) if want_g else None
+    ws = train_workspace(y.device)
+    with torch.cuda.device(y.device):
+        check(lib().lfd_bn_eval_bwd_f16(ptr(dz), ptr(y), ptr(z), int(relu), y.numel() // c, c, ptr(stats), ptr(gamma), ptr(beta),
+                                        float(inv_scale), int(bool(accumulate)), ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta),
+                                        ptr(dy), ptr(g), stream_ptr()), 'lfd_bn_eval_bwd_f16')
+    return dy, g
+
+
+def _capturing():
+    return torch.cuda.is_current_stream_capturing()
+
+
+class BnEvalRows(object):
+    """The (mean, rstd) rows of the eval-mode BatchNorm2d modules of a training plan, float32[2 * C] each, from their running
+    statistics in ONE launch (lfd_bn_eval_stats_f32).  The rows keep their addresses; they are recomputed when a buffer's
+    version counter moved (load_state_dict) -- and always inside a graph capture, so that a replay never reads rows older
+    than the buffers."""
+
+    def __init__(self, norms):
+        dev = norms[0].running_mean.device
+        require_cuda(norms[0].running_mean, 'BnEvalRows')
+        self.device, self.norms = dev, list(norms)
+        self.key = self._addresses(norms)
+        self.outs = [torch.empty(2 * m.num_features, dtype=torch.float32, device=dev) for m in norms]
+        jobs = (_lib.BnEvalJob * len(norms))()
+        for j, m, out in zip(jobs, norms, self.outs):
+            for t in (m.running_mean, m.running_var):
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != m.num_features:
+                    raise RuntimeError('BnEvalRows: contiguous float32 running statistics expected')
+            j.running_mean, j.running_var, j.stats = m.running_mean.data_ptr(), m.running_var.data_ptr(), out.data_ptr()
+            j.channels, j.eps = m.num_features, float(m.eps)
+        self.max_c = max(m.num_features for m in norms)
+        self.table = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
+        self.version = None
+
+    @staticmethod
+    def _addresses(norms):
+        return tuple((m.running_mean.data_ptr(), m.running_var.data_ptr(), float(m.eps)) for m in norms)
+
+    def matches(self, norms):
+        return self.key == self._addresses(norms)
+
+    def versions(self):
+        return tuple((m.running_mean._version, m.running_var._version) for m in self.norms)
+
+    def run(self):
+        """-> (rows, True if they were recomputed)"""
+        ver = self.versions()
+        cap = _capturing()
+        if cap or ver != self.version:
+            with torch.cuda.device(self.device):
+                check(lib().lfd_bn_eval_stats_f32(ptr(self.table), len(self.norms), self.max_c, stream_ptr()), 'lfd_bn_eval_stats_f32')
+            self.version = None if cap else ver       # (a captured launch has not run yet)
+            return self.outs, True
+        return self.outs, False
+
+
+class FoldBatch(object):
+    """Frozen Conv2d(bias=False) -> eval-mode BatchNorm2d units as convs with bias: folded fp32 weights and biases of all of
+    them in ONE launch (lfd_conv_bn_eval_fold_f32) from the norms' BnEvalRows rows, then packed in one more (PackBatch).
+    Redone when a parameter's version counter moved or the rows were recomputed, and always inside a graph capture."""
+
+    def __init__(self, items):
+        """items: [(conv weight, gamma, beta, stats row)]"""
+        dev = items[0][0].device
+        self.device = dev
+        self.params = [t for it in items for t in it[:3]]
+        self.key = tuple(t.data_ptr() for it in items for t in it)
+        self.w_outs, self.biases = [], []
+        jobs = (_lib.BnFoldJob * len(items))()
+        first = 0
+        for j, (w, gamma, beta, row) in zip(jobs, items):
+            cout = w.size(0)
+            for t in (w, gamma, beta):
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise RuntimeError('FoldBatch: contiguous float32 parameters expected')
+            if gamma.numel() != cout or beta.numel() != cout or row.numel() != 2 * cout:
+                raise RuntimeError('FoldBatch: shape mismatch')
+            wo = torch.empty_like(w)
+            bo = torch.empty(cout, dtype=torch.float32, device=dev)
+            j.w, j.gamma, j.beta, j.stats, j.w_out, j.bias_out = (w.data_ptr(), gamma.data_ptr(), beta.data_ptr(), row.data_ptr(),
+                                                                  wo.data_ptr(), bo.data_ptr())
+            j.cout, j.row_elems, j.first_elem = cout, w.numel() // cout, first
+            first += w.numel()
+            self.w_outs.append(wo)
+            self.biases.append(bo)
+        self.total, self.njobs = first, len(items)
+        self.table = torch.frombuffer(bytearray(bytes(jobs)), dtype=torch.uint8).to(dev)
+        self.pack = PackBatch(self.w_outs, False)
+        self.version = None
+
+    def matches(self, items):
+        return self.key == tuple(t.data_ptr() for it in items for t in it)
+
+    def run(self, rows_recomputed):
+        """-> (packed fp16 weights, fp32 biases), one per item"""
+        ver = tuple(t._version for t in self.params)
+        cap = _capturing()
+        if cap or rows_recomputed or ver != self.version:
+            with torch.cuda.device(self.device):
+                check(lib().lfd_conv_bn_eval_fold_f32(ptr(self.table), self.njobs, self.total, stream_ptr()), 'lfd_conv_bn_eval_fold_f32')
+            self.pack.run()
+            self.version = None if cap else ver
+        return self.pack.outs, self.biases
+
+
 def gn_train_stats(y, groups, eps):
     _nhwc16(y, 'gn_train_stats')
     n, h, w_, c = y.shape

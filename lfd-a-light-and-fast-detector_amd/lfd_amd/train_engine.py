@@ -37,7 +37,9 @@ def set_loss_scale(v):
 
 
 class _Unit(object):
-    __slots__ = ('conv', 'norm', 'relu', 'src', 'res', 'dst', 'first', 'level')
+    # eval_norm: the unit's BatchNorm2d is in eval mode inside the training model (running statistics, nothing updated);
+    # frozen: eval_norm and none of its parameters takes a gradient -- forward only, never visited by the backward
+    __slots__ = ('conv', 'norm', 'relu', 'src', 'res', 'dst', 'first', 'level', 'frozen', 'eval_norm')
 
 
 class _Out(object):
@@ -53,26 +55,39 @@ def _conv_ok(m, first=False):
     return m.in_channels == 3 or (m.in_channels in (32, 64, 128) and m.out_channels in (32, 64, 128))
 
 
+def frozen_modules(backbone):
+    """the modules LFDResNet.train() freezes for its frozen_stages (lfd_resnet.py:476-487): the stem and stage0 .. stage{k-1}"""
+    k = backbone._frozen_stages
+    return [backbone._stem] + [getattr(backbone, 'stage%d' % i) for i in range(k)] if k > 0 else []
+
+
 def supported(backbone):
-    """The HIP training path covers BatchNorm2d + ReLU backbones with 32/64/128-channel convs, nothing frozen; RGB or
-    grayscale (input_channels 3 or 1)."""
+    """The HIP training path covers BatchNorm2d + ReLU backbones with 32/64/128-channel convs; RGB or grayscale
+    (input_channels 3 or 1).  Frozen parameters and eval-mode norms: exactly what the backbone's own frozen_stages /
+    norm_eval produce in train() -- the stem and the first stages frozen (forward only), every BatchNorm2d on its running
+    statistics."""
     if backbone._norm_cfg is None or backbone._norm_cfg.get('type') != 'BatchNorm2d':
         return False
-    if backbone._activation_cfg.get('type') != 'ReLU' or backbone._frozen_stages > 0 or backbone._norm_eval:
+    if backbone._activation_cfg.get('type') != 'ReLU' or not backbone.training:
         return False
     if backbone._input_channels not in (1, 3):
         return False
-    # the hand-written backward accumulates into EVERY covered parameter's .grad: a frozen parameter (requires_grad=False,
-    # however it was frozen) sends the module through PyTorch-ROCm autograd instead
-    if not all(p.requires_grad for p in backbone.parameters()):
+    # the hand-written backward accumulates into every parameter's .grad but those of the frozen stages: any OTHER frozen
+    # parameter (requires_grad=False, however it was frozen), or a thawed one inside a frozen stage, sends the module through
+    # PyTorch-ROCm autograd instead; the same for a norm layer whose mode is not the one train() gives it
+    fz_params, fz_mods = set(), set()
+    for fm in frozen_modules(backbone):
+        fz_params.update(id(p) for p in fm.parameters())
+        fz_mods.update(id(m) for m in fm.modules())
+    if not all(p.requires_grad == (id(p) not in fz_params) for p in backbone.parameters()):
         return False
     first = backbone._stem[0]
     for m in backbone.modules():
         if isinstance(m, nn.Conv2d) and not _conv_ok(m, m is first):
             return False
         if isinstance(m, nn.BatchNorm2d) and (m.momentum is None or not m.affine or not m.track_running_stats
-                                              or not m.training):
-            return False          # incl. norm layers switched to eval() inside a training model: batch statistics only here
+                                              or m.training == (backbone._norm_eval or id(m) in fz_mods)):
+            return False          # incl. norm layers switched to eval() by hand inside a training model
     return (first.in_channels == backbone._input_channels and first.out_channels in (32, 64) and first.kernel_size == (3, 3)
             and first.stride == (2, 2))
 
@@ -130,6 +145,8 @@ class _Builder(object):
         u = _Unit()
         u.conv, u.norm, u.relu, u.src, u.res, u.dst, u.first = conv, norm, relu, src, res, self.n_act, src == 0
         u.level = self.level            # None: backbone; i: the neck / tower chain of pyramid level i
+        u.eval_norm = isinstance(norm, nn.BatchNorm2d) and not norm.training
+        u.frozen = u.eval_norm and not any(p.requires_grad for p in (conv.weight, norm.weight, norm.bias))
         self.units.append(u)
         self.n_act += 1
         return u.dst
@@ -209,10 +226,18 @@ def _unique(params):
 
 
 def backbone_params(units):
+    """the parameters the backward accumulates gradients into: those of the units that are not frozen"""
     ps = []
     for u in units:
-        ps += [u.conv.weight, u.norm.weight, u.norm.bias]
+        if not u.frozen:
+            ps += [u.conv.weight, u.norm.weight, u.norm.bias]
     return _unique(ps)
+
+
+def dead_activations(units):
+    """activations nobody needs a gradient for: the input image and the outputs of the frozen units (a frozen activation that
+    is a pyramid tap or feeds a trainable unit is read; the gradient that would flow into it is never formed)"""
+    return {0} | {u.dst for u in units if u.frozen}
 
 
 def network_params(units, outs):
@@ -244,7 +269,7 @@ class _Packs(object):
             ws, seen = [], set()
             for u in units:
                 w = u.conv.weight
-                if not u.first and id(w) not in seen:
+                if not u.first and not u.frozen and id(w) not in seen:
                     seen.add(id(w))
                     ws.append(w.detach())
             if ws:
@@ -267,6 +292,85 @@ class _Packs(object):
         return self.c[k]
 
 
+class _EvalNorms(object):
+    """What the eval-mode norms of a plan need per iteration: rows[id(norm)] = the (mean, rstd) row of its running statistics
+    (ops.BnEvalRows, one launch) and folded[unit index] = (packed weight, bias) of every frozen unit but the first conv
+    (ops.FoldBatch, two launches); both cached by the tensors' version counters.  Kept on the plan's owner."""
+
+    def __init__(self):
+        self.rows_batch = self.fold_batch = None
+
+    def run(self, units):
+        self.rows, self.folded = {}, {}
+        norms = _unique_mods([u.norm for u in units if u.eval_norm])
+        if not norms:
+            return self
+        if self.rows_batch is None or not self.rows_batch.matches(norms):
+            self.rows_batch = ops.BnEvalRows(norms)
+        rows, fresh = self.rows_batch.run()
+        self.rows = {id(m): r for m, r in zip(norms, rows)}
+        fz = [(ui, u) for ui, u in enumerate(units) if u.frozen and not u.first]
+        if fz:
+            items = [(u.conv.weight.detach(), u.norm.weight.detach(), u.norm.bias.detach(), self.rows[id(u.norm)]) for _, u in fz]
+            if self.fold_batch is None or not self.fold_batch.matches(items):
+                self.fold_batch = ops.FoldBatch(items)
+                fresh = True
+            packed, biases = self.fold_batch.run(fresh)
+            self.folded = {ui: (wp, b) for (ui, _), wp, b in zip(fz, packed, biases)}
+        return self
+
+
+def _unique_mods(mods):
+    seen, out = set(), []
+    for m in mods:
+        if id(m) not in seen:
+            seen.add(id(m))
+            out.append(m)
+    return out
+
+
+def _eval_norms(owner, units):
+    ev = owner.__dict__.get('_lfd_eval_norms')
+    if ev is None:
+        ev = owner.__dict__['_lfd_eval_norms'] = _EvalNorms()
+    return ev.run(units)
+
+
+def _frozen_forward(ui, u, acts, ev):
+    """a frozen unit: relu?(conv(x, w') + b' (+ residual)) in one launch on the folded weights; the first conv (3 or 1 input
+    channels) through its training forward kernel and an apply pass on the running statistics.  Nothing is kept for a backward."""
+    conv, norm = u.conv, u.norm
+    res = acts[u.res] if u.res is not None else None
+    if u.first:
+        y = ops.stem_conv0_train_fwd(acts[u.src], conv.weight)
+        return ops.bn_train_apply(y, ev.rows[id(norm)], norm.weight.detach(), norm.bias.detach(), res, u.relu)
+    wp, bias = ev.folded[ui]
+    return ops.conv2d_nhwc(acts[u.src], wp, bias, conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.stride[0], u.relu,
+                           residual=res)
+
+
+def _eval_unit_forward(u, acts, packs, zeros, ev):
+    """a trainable unit with an eval-mode norm: the plain conv (no batch statistics), then the apply pass on the row of the
+    running statistics; -> (y, stats) for the one-pass backward (ops.bn_eval_backward)"""
+    conv, norm = u.conv, u.norm
+    if u.first:
+        y = ops.stem_conv0_train_fwd(acts[u.src], conv.weight)
+    else:
+        cout = conv.out_channels
+        y = ops.conv2d_nhwc(acts[u.src], packs(conv.weight), zeros(cout), conv.in_channels, cout, conv.kernel_size[0], conv.stride[0], False)
+    stats = ev.rows[id(norm)]
+    acts[u.dst] = ops.bn_train_apply(y, stats, norm.weight.detach(), norm.bias.detach(), acts[u.res] if u.res is not None else None,
+                                     u.relu)
+    return y, stats
+
+
+def _count_batches(units):
+    """num_batches_tracked += 1 for the training-mode norms (an eval-mode BatchNorm2d updates nothing)"""
+    nbt = [u.norm.num_batches_tracked for u in units if isinstance(u.norm, nn.BatchNorm2d) and not u.eval_norm]
+    if nbt:
+        torch._foreach_add_(nbt, 1)
+
+
 _zero_cache = {}
 
 
@@ -283,15 +387,26 @@ class _Zeros(object):
         return _zero_cache[k]
 
 
-def forward(units, tap_ids, x):
-    """x: NCHW fp32 image batch (as LFD.forward receives it, lfd.py:511).  -> (requested activations NHWC fp16, saved)."""
+def forward(units, tap_ids, x, owner=None):
+    """x: NCHW fp32 image batch (as LFD.forward receives it, lfd.py:511).  -> (requested activations NHWC fp16, saved).
+    owner: the module that keeps the plan (the per-iteration state of eval-mode norms lives on it)."""
     acts = {0: x}
     tape = []
     zeros = _Zeros(x.device)
     packs = _Packs(units, False)
     fused_stats = os.environ.get('LFD_CONV_BN_STATS', '1') == '1'     # A/B switch: 0 = conv, then a statistics pass over y
-    for u in units:
+    ev = None
+    if any(u.eval_norm for u in units):
+        ev = _eval_norms(owner, units) if owner is not None else _EvalNorms().run(units)
+    for ui, u in enumerate(units):
         conv, norm = u.conv, u.norm
+        if u.frozen:
+            acts[u.dst] = _frozen_forward(ui, u, acts, ev)
+            tape.append(None)
+            continue
+        if u.eval_norm:
+            tape.append(_eval_unit_forward(u, acts, packs, zeros, ev))
+            continue
         xin = acts[u.src]
         ks, st = conv.kernel_size[0], conv.stride[0]
         stats = None
@@ -318,7 +433,7 @@ def forward(units, tap_ids, x):
                                    acts[u.res] if u.res is not None else None, u.relu)
         acts[u.dst] = z
         tape.append((y, stats))
-    torch._foreach_add_([u.norm.num_batches_tracked for u in units if isinstance(u.norm, nn.BatchNorm2d)], 1)
+    _count_batches(units)
     return [acts[t] for t in tap_ids], (acts, tape)
 
 
@@ -361,10 +476,11 @@ def backward(units, saved, grads, scale=None, store=None, trace=None):
     store = store if store is not None else _GradStore()
     zeros = _Zeros(acts[0].device)
     packs = _Packs(units, True)
+    dead = dead_activations(units)
     for ui in range(len(units) - 1, -1, -1):
         u = units[ui]
         dz = grads.pop(u.dst, None)
-        if dz is None:
+        if dz is None or u.frozen:
             continue
         conv, norm = u.conv, u.norm
         y, stats = tape[ui]
@@ -374,12 +490,16 @@ def backward(units, saved, grads, scale=None, store=None, trace=None):
         snap = [t.clone() for t in (dgamma, dbeta, dw)] if trace is not None else None
         if isinstance(norm, nn.GroupNorm):
             dy = ops.gn_train_backward(dz, y, z, norm.num_groups, stats, norm.weight.detach(), inv, dgamma, dbeta, True)
+        elif u.eval_norm:
+            dy, g = ops.bn_eval_backward(dz, y, z if u.res is not None else None, stats, norm.weight.detach(), inv, dgamma, dbeta,
+                                         want_g=u.res is not None and u.res not in dead, accumulate=True, relu=u.relu,
+                                         beta=norm.bias.detach())
         else:
             # without a residual input the ReLU mask is recomputed from y (one tensor less to read in both passes)
             dy, g = ops.bn_train_backward(dz, y, z if u.res is not None else None, stats, norm.weight.detach(), inv, dgamma,
                                           dbeta, want_g=u.res is not None, accumulate=True, relu=u.relu,
                                           beta=norm.bias.detach())
-        if u.res is not None:
+        if u.res is not None and u.res not in dead:
             grads[u.res] = g if u.res not in grads else grads[u.res] + g
         xin = acts[u.src]
         ks, st = conv.kernel_size[0], conv.stride[0]
@@ -389,7 +509,9 @@ def backward(units, saved, grads, scale=None, store=None, trace=None):
         else:
             ops.conv_wgrad(xin, dy, ks, st, inv, out=dw, accumulate=True)
             cin = conv.in_channels
-            if (st == 2 and ks == 3 and cin == 64 and conv.out_channels == 64 and os.environ.get('LFD_DGRAD_S2', '1') == '1'):
+            if u.src in dead:          # the input is a frozen activation: no data gradient
+                pass
+            elif (st == 2 and ks == 3 and cin == 64 and conv.out_channels == 64 and os.environ.get('LFD_DGRAD_S2', '1') == '1'):
                 # per output parity, 9 tap-products per 2 x 2 pixels instead of 36 and no zero-inserted tensor (csrc/dgrad_s2.hip)
                 grads[u.src] = ops.conv3x3s2_dgrad(dy, packs(conv.weight, True), xin.size(1), xin.size(2), residual=grads.get(u.src))
             else:
@@ -398,7 +520,7 @@ def backward(units, saved, grads, scale=None, store=None, trace=None):
                 grads[u.src] = ops.conv2d_nhwc(dy, packs(conv.weight, True), zeros(cin), conv.out_channels, cin, ks, 1,
                                                False, residual=grads.get(u.src))
             if rec is not None:
-                rec['dx'] = grads[u.src]
+                rec['dx'] = grads.get(u.src)
         if rec is not None:      # this unit's own contribution (the buffers accumulate over shared modules)
             rec.update(dgamma=dgamma - snap[0], dbeta=dbeta - snap[1], dw=dw - snap[2])
             trace.append(rec)
@@ -772,8 +894,9 @@ def _concat_forward(cl, units, outs, acts, tape, packs, opk, zeros, fused_stats,
     return dict(A=A, Y=Y, yo=yo, seg_hw=seg_hw, ptot=ptot)
 
 
-def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, full, starts, store, wgrad, grads, scale, inv, n, dev):
-    """the backward of _concat_forward; leaves the gradients of the backbone taps in `grads`"""
+def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, full, starts, store, wgrad, grads, scale, inv, n, dev, dead=()):
+    """the backward of _concat_forward; leaves the gradients of the backbone taps in `grads` (none for a tap in `dead`: the
+    output of a frozen unit)"""
     A, Y, seg_hw, ptot = cs['A'], cs['Y'], cs['seg_hw'], cs['ptot']
     dA = [None] * cl['npos']
     nlev = len(seg_hw)
@@ -843,6 +966,8 @@ def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, full, starts,
         xin = acts[u.src]
         wgrad(xin, dy, 1, 1, [(store.target(conv.weight), 0, conv.out_channels)])
         cin = conv.in_channels
+        if u.src in dead:
+            continue
         grads[u.src] = ops.conv2d_nhwc(dy, packs(conv.weight, True), zeros(cin), conv.out_channels, cin, 1, 1, False,
                                        residual=grads.get(u.src))
 
@@ -863,6 +988,8 @@ def _stem_pairs(units, outs):
     out = {}
     for ui, vi in _single_consumers(units, outs).items():
         v = units[vi]
+        if units[ui].frozen or units[ui].eval_norm or v.frozen or v.eval_norm:
+            continue             # the pair fusions take batch statistics from the conv epilogues: training-mode norms only
         if (isinstance(v.norm, nn.BatchNorm2d) and v.conv.kernel_size[0] == 1 and v.conv.stride[0] == 1
                 and v.conv.in_channels == 64 and v.conv.out_channels in (64, 128)):     # (the kernel's two instances: ADVICE r4)
             out[ui] = vi
@@ -928,8 +1055,13 @@ def network_forward(model, plan, x):
     cs = None
     defer = _deferred_units(units, outs) if fused_stats else {}
     fed = {v: u for u, v in defer.items()}
+    ev = _eval_norms(model, units) if any(u.eval_norm for u in units) else None
     for ui, u in enumerate(units):
-        if u.level is None:
+        if u.frozen:
+            acts[u.dst] = _frozen_forward(ui, u, acts, ev)
+        elif u.eval_norm:
+            tape[ui] = _eval_unit_forward(u, acts, packs, zeros, ev)
+        elif u.level is None:
             tape[ui] = _unit_forward(u, acts, packs, zeros, fused_stats, store=ui not in defer,
                                      producer=(units[fed[ui]], tape[fed[ui]]) if ui in fed else None)
     if cl is not None:
@@ -948,7 +1080,7 @@ def network_forward(model, plan, x):
             segs = _out_segs(o)
             ops.head_out_split(y, segs, [full[sg['kind']] for sg in segs], starts[o.level])
             osaved.append((wp, y))
-    torch._foreach_add_([u.norm.num_batches_tracked for u in units if isinstance(u.norm, nn.BatchNorm2d)], 1)
+    _count_batches(units)
     return full['cls'], full['reg'], sizes, ((acts, tape), osaved, opk)
 
 
@@ -1030,9 +1162,10 @@ def network_backward(model, plan, saved, sizes, dcls, dreg, scale):
                if v == u_ + 1 and units[u_].conv.out_channels == 64 and units[v].conv.out_channels == 64}
     sum_rows = {}
     concat = isinstance(osaved, dict)
+    dead = dead_activations(units)
     if concat:
         _concat_backward(model.__dict__['_lfd_concat_layout'], osaved, units, acts, tape, packs, opk, zeros, full, starts, store,
-                         wgrad, grads, scale, inv, dcls.size(0), dev)
+                         wgrad, grads, scale, inv, dcls.size(0), dev, dead)
     # ---- output convs, level by level
     for o, (wp, y) in (() if concat else zip(outs, osaved)):
         xo = acts[o.src]
@@ -1054,11 +1187,13 @@ def network_backward(model, plan, saved, sizes, dcls, dreg, scale):
         if u.dst not in grads or (concat and u.level is not None):
             continue
         dz = grads.pop(u.dst)
+        if u.frozen:
+            continue
         conv, norm = u.conv, u.norm
         y, stats = tape[ui]
         z = acts[u.dst] if u.relu else None
         g = None
-        if (u.first and isinstance(norm, nn.BatchNorm2d) and u.relu and u.res is None and conv.out_channels == 64
+        if (u.first and isinstance(norm, nn.BatchNorm2d) and not u.eval_norm and u.relu and u.res is None and conv.out_channels == 64
                 and os.environ.get('LFD_CONV0_BN_WGRAD', '1') == '1'):
             # the first unit has no data gradient: BatchNorm's sums, then the weight gradient straight from dz and y (no dy tensor)
             ops.stem_conv0_bn_bwd_wgrad(acts[u.src], dz, y, stats, norm.weight.detach(), norm.bias.detach(), inv,
@@ -1068,6 +1203,12 @@ def network_backward(model, plan, saved, sizes, dcls, dreg, scale):
         if isinstance(norm, nn.GroupNorm):
             dy = ops.gn_train_backward(dz, y, z, norm.num_groups, stats, norm.weight.detach(), inv, store.target(norm.weight),
                                        store.target(norm.bias), True)
+        elif u.eval_norm:
+            # constant statistics: dy does not wait for the sums -- one pass over (dz, y) instead of two
+            dy, g = ops.bn_eval_backward(dz, y, z if u.res is not None else None, stats, norm.weight.detach(), inv,
+                                         store.target(norm.weight), store.target(norm.bias),
+                                         want_g=u.res is not None and u.res not in dead, accumulate=True, relu=u.relu,
+                                         beta=norm.bias.detach())
         elif ui in sum_rows:
             dy = ops.bn_train_backward_rows(dz, y, stats, norm.weight.detach(), norm.bias.detach(), inv, store.target(norm.weight),
                                             store.target(norm.bias), sum_rows[ui])
@@ -1076,7 +1217,7 @@ def network_backward(model, plan, saved, sizes, dcls, dreg, scale):
             dy, g = ops.bn_train_backward(dz, y, z if u.res is not None else None, stats, norm.weight.detach(), inv,
                                           store.target(norm.weight), store.target(norm.bias), want_g=u.res is not None,
                                           accumulate=True, relu=u.relu, beta=norm.bias.detach())
-        if u.res is not None:
+        if u.res is not None and u.res not in dead:
             grads[u.res] = g if u.res not in grads else grads[u.res] + g
         xin = acts[u.src]
         ks, st = conv.kernel_size[0], conv.stride[0]
@@ -1090,6 +1231,8 @@ def network_backward(model, plan, saved, sizes, dcls, dreg, scale):
             xin = tape[pi][0]
         wgrad(xin, dy, ks, st, [(store.target(conv.weight), 0, conv.out_channels)], producer)
         cin = conv.in_channels
+        if u.src in dead:          # the input is a frozen activation: no data gradient
+            continue
         if st == 2 and ks == 3 and cin == 64 and conv.out_channels == 64 and os.environ.get('LFD_DGRAD_S2', '1') == '1':
             # per output parity, 9 tap-products per 2 x 2 pixels instead of 36 and no zero-inserted tensor (csrc/dgrad_s2.hip)
             grads[u.src] = ops.conv3x3s2_dgrad(dy, packs(conv.weight, True), xin.size(1), xin.size(2), residual=grads.get(u.src))
@@ -1110,14 +1253,14 @@ class BackboneTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, x, *params):
-        units, tap_ids = plan
-        taps, saved = forward(units, tap_ids, x)
+        units, tap_ids = plan[:2]
+        taps, saved = forward(units, tap_ids, x, plan[2] if len(plan) > 2 else None)
         ctx.plan, ctx.saved = plan, saved
         return tuple(t.permute(0, 3, 1, 2).float() for t in taps)
 
     @staticmethod
     def backward(ctx, *tap_grads):
-        units, tap_ids = ctx.plan
+        units, tap_ids = ctx.plan[:2]
         grads = {}
         scale = loss_scale()
         for t, g in zip(tap_ids, tap_grads):
@@ -1158,7 +1301,7 @@ def backbone_train_forward(backbone, x):
     check_train_input(backbone, x)
     plan = backbone.__dict__.get('_lfd_train_plan')
     if plan is None:
-        plan = build_units(backbone)
+        plan = build_units(backbone) + (backbone,)
         backbone.__dict__['_lfd_train_plan'] = plan
     return BackboneTrainFunction.apply(plan, x, *backbone_params(plan[0]))
 

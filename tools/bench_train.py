@@ -1,7 +1,8 @@
 """Training-step timing (BASELINE.json configs[4]: WIDERFACE_LFD_S, synthetic 640x640, bs 32 per GPU): forward, fused
 get_loss, backward, gradient clipping + SGD.  --input-channels 1 times the model's grayscale twin on [N,1,H,W] batches;
 --num-classes K the configuration with a K-class head (80: a COCO-sized head, the 128-row output convs) and box labels of
-all K classes.
+all K classes; --frozen-stages K / --norm-eval the fine-tuning options of the backbone (stem and first K stages frozen, BatchNorm
+on its running statistics).
 Prints one JSON line per mode:
   hip   : the whole network on the hand-written kernels (train_engine) + fused loss + flat SGD
   graph : the same iteration replayed as one HIP graph (lfd_amd.train.GraphedTrainStep)
@@ -35,7 +36,8 @@ def run(mode, args):
     os.environ['LFD_HIP_TRAIN'] = '1' if hip else '0'
     os.environ['LFD_FUSED_LOSS'] = '1' if hip else '0'
     torch.manual_seed(0)
-    m = configs.build_model(args.model, input_channels=args.input_channels, num_classes=args.num_classes).cuda().train()
+    m = configs.build_model(args.model, input_channels=args.input_channels, num_classes=args.num_classes,
+                            frozen_stages=args.frozen_stages, norm_eval=args.norm_eval).cuda().train()
     kw = dict(lr=0.01, momentum=0.9, weight_decay=1e-4)
     opt = optim.SGD(m.parameters(), **kw) if hip else torch.optim.SGD(m.parameters(), **kw)
     rng = np.random.default_rng(0)
@@ -56,7 +58,7 @@ def run(mode, args):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     print(json.dumps(dict(mode=mode, model=args.model, num_classes=m._num_classes, input_channels=args.input_channels,
-                          batch=args.batch, size=args.size, ms_per_step=round(dt * 1e3, 3), images_per_s=round(args.batch / dt, 1),
+                          frozen_stages=args.frozen_stages, norm_eval=args.norm_eval, batch=args.batch, size=args.size, ms_per_step=round(dt * 1e3, 3), images_per_s=round(args.batch / dt, 1),
                           loss=lv['loss'], peak_mem_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))))
 
 
@@ -70,6 +72,8 @@ if __name__ == '__main__':
     ap.add_argument('--modes', default='hip,torch')
     ap.add_argument('--input-channels', type=int, default=3, choices=(1, 3), help='3: RGB, 1: the grayscale twin')
     ap.add_argument('--num-classes', type=int, default=None, help='classes of the head (default: the configuration\'s own)')
+    ap.add_argument('--frozen-stages', type=int, default=-1, help='LFDResNet frozen_stages: K > 0 freezes the stem and stage0 .. stage{K-1}')
+    ap.add_argument('--norm-eval', action='store_true', help='LFDResNet norm_eval: backbone BatchNorm on its running statistics')
     ap.add_argument('--concat', type=int, default=-1, help='train_engine.CONCAT_HEAD: 1 = shared head towers once over all pyramid '
                     'levels, 0 = level by level (default: the module\'s setting)')
     a = ap.parse_args()
