@@ -11,6 +11,7 @@ scale), fp32 accumulation on MFMA, fp32 statistics, parameters and parameter gra
 The backward is a hand-written schedule over the recorded units (no autograd inside):
     g, dy = bn_bwd(dz)  ->  dW = wgrad(x, dy)  ->  dx = conv(dy, W^T flipped) (+ gradient already collected for x)
 """
+import collections
 import os
 
 import torch
@@ -34,6 +35,24 @@ def set_loss_scale(v):
     if not (1.0 <= v <= 65536.0) or v != 2.0 ** round(__import__('math').log2(v)):
         raise ValueError('loss scale must be a power of two in [1, 65536]')
     _scale_state['value'] = v
+
+
+_Switches = collections.namedtuple('_Switches', 'conv_bn_stats dgrad_s2 out_fused bn_levels head_out_levels bn_apply_in_conv '
+                                                'bn_sums_in_dgrad conv0_bn_wgrad')
+
+
+def switches():
+    """The A/B switches of the training schedules (all on by default; what '0' runs instead stands beside each), read from the
+    environment at every call: the public entries call this once per pass and hand the record down."""
+    return _Switches(
+        conv_bn_stats=os.environ.get('LFD_CONV_BN_STATS', '1') == '1',           # conv, then a statistics pass over y
+        dgrad_s2=os.environ.get('LFD_DGRAD_S2', '1') == '1',                     # zero_insert2 + stride-1 conv (3x3 stride-2 dgrad)
+        out_fused=os.environ.get('LFD_OUT_FUSED', '1') == '1',                   # output-conv glue as PyTorch ops (serial API only)
+        bn_levels=os.environ.get('LFD_BN_LEVELS', '1') == '1',                   # neck BatchNorm passes level after level
+        head_out_levels=os.environ.get('LFD_HEAD_OUT_LEVELS', '1') == '1',       # output-conv glue level after level
+        bn_apply_in_conv=not os.environ.get('LFD_BN_APPLY_IN_CONV', '1') != '1',  # every unit stores its activation
+        bn_sums_in_dgrad=os.environ.get('LFD_BN_SUMS_IN_DGRAD', '1') == '1',     # every BatchNorm backward sums for itself
+        conv0_bn_wgrad=os.environ.get('LFD_CONV0_BN_WGRAD', '1') == '1')         # first unit: norm backward, then weight gradient
 
 
 class _Unit(object):
@@ -349,21 +368,6 @@ def _frozen_forward(ui, u, acts, ev):
                            residual=res)
 
 
-def _eval_unit_forward(u, acts, packs, zeros, ev):
-    """a trainable unit with an eval-mode norm: the plain conv (no batch statistics), then the apply pass on the row of the
-    running statistics; -> (y, stats) for the one-pass backward (ops.bn_eval_backward)"""
-    conv, norm = u.conv, u.norm
-    if u.first:
-        y = ops.stem_conv0_train_fwd(acts[u.src], conv.weight)
-    else:
-        cout = conv.out_channels
-        y = ops.conv2d_nhwc(acts[u.src], packs(conv.weight), zeros(cout), conv.in_channels, cout, conv.kernel_size[0], conv.stride[0], False)
-    stats = ev.rows[id(norm)]
-    acts[u.dst] = ops.bn_train_apply(y, stats, norm.weight.detach(), norm.bias.detach(), acts[u.res] if u.res is not None else None,
-                                     u.relu)
-    return y, stats
-
-
 def _count_batches(units):
     """num_batches_tracked += 1 for the training-mode norms (an eval-mode BatchNorm2d updates nothing)"""
     nbt = [u.norm.num_batches_tracked for u in units if isinstance(u.norm, nn.BatchNorm2d) and not u.eval_norm]
@@ -387,52 +391,58 @@ class _Zeros(object):
         return _zero_cache[k]
 
 
+def _unit_forward(ui, u, acts, packs, zeros, sw, ev=None, store=True, producer=None):
+    """conv -> norm (batch / group / running statistics) -> (+ residual) -> ReLU of one unit on the current stream: the one unit
+    forward of both schedules.  -> what the backward needs, (y, stats); None for a frozen unit (one launch on the folded weights).
+    ev: the _EvalNorms of the pass (plans with eval-mode norms).  store=False: the activation is not written (_deferred_units:
+    its consumer forms it from (y, stats)); producer = (unit, (y, stats)) of such an input."""
+    if u.frozen:
+        acts[u.dst] = _frozen_forward(ui, u, acts, ev)
+        return None
+    conv, norm = u.conv, u.norm
+    xin = acts[u.src]
+    ks, st, cout = conv.kernel_size[0], conv.stride[0], conv.out_channels
+    # the batch statistics come out of the conv's epilogue: no separate read of y (csrc/conv_stats.hip)
+    conv_stats = sw.conv_bn_stats and isinstance(norm, nn.BatchNorm2d) and not u.eval_norm
+    stats = None
+    if producer is not None:
+        pu, (py, pstats) = producer
+        y, stats = ops.conv1x1_of_bn_relu_bn_stats(py, pstats, pu.norm.weight.detach(), pu.norm.bias.detach(), packs(conv.weight),
+                                                   zeros(cout), cout, norm.eps, norm.momentum, norm.running_mean, norm.running_var)
+    elif u.first and conv_stats:
+        y, stats = ops.stem_conv0_train_fwd_bn_stats(xin, conv.weight, norm.eps, norm.momentum, norm.running_mean,
+                                                     norm.running_var)
+    elif u.first:
+        y = ops.stem_conv0_train_fwd(xin, conv.weight)
+    elif conv_stats:
+        y, stats = ops.conv2d_bn_stats(xin, packs(conv.weight), zeros(cout), conv.in_channels, cout, ks, st, norm.eps,
+                                       norm.momentum, norm.running_mean, norm.running_var)
+    else:
+        y = ops.conv2d_nhwc(xin, packs(conv.weight), zeros(cout), conv.in_channels, cout, ks, st, False)
+    if isinstance(norm, nn.GroupNorm):
+        stats, z = ops.gn_train_stats_apply(y, norm.num_groups, norm.eps, norm.weight.detach(), norm.bias.detach(), u.relu)
+    else:
+        if u.eval_norm:       # the row of the running statistics; the backward is one pass (ops.bn_eval_backward)
+            stats = ev.rows[id(norm)]
+        elif stats is None:
+            stats = ops.bn_train_stats(y, norm.eps, norm.momentum, norm.running_mean, norm.running_var)
+        z = ops.bn_train_apply(y, stats, norm.weight.detach(), norm.bias.detach(),
+                               acts[u.res] if u.res is not None else None, u.relu) if store else None
+    acts[u.dst] = z
+    return y, stats
+
+
 def forward(units, tap_ids, x, owner=None):
     """x: NCHW fp32 image batch (as LFD.forward receives it, lfd.py:511).  -> (requested activations NHWC fp16, saved).
     owner: the module that keeps the plan (the per-iteration state of eval-mode norms lives on it)."""
+    sw = switches()
     acts = {0: x}
-    tape = []
     zeros = _Zeros(x.device)
     packs = _Packs(units, False)
-    fused_stats = os.environ.get('LFD_CONV_BN_STATS', '1') == '1'     # A/B switch: 0 = conv, then a statistics pass over y
     ev = None
     if any(u.eval_norm for u in units):
         ev = _eval_norms(owner, units) if owner is not None else _EvalNorms().run(units)
-    for ui, u in enumerate(units):
-        conv, norm = u.conv, u.norm
-        if u.frozen:
-            acts[u.dst] = _frozen_forward(ui, u, acts, ev)
-            tape.append(None)
-            continue
-        if u.eval_norm:
-            tape.append(_eval_unit_forward(u, acts, packs, zeros, ev))
-            continue
-        xin = acts[u.src]
-        ks, st = conv.kernel_size[0], conv.stride[0]
-        stats = None
-        if u.first and isinstance(norm, nn.BatchNorm2d) and fused_stats:
-            y, stats = ops.stem_conv0_train_fwd_bn_stats(xin, conv.weight, norm.eps, norm.momentum, norm.running_mean,
-                                                         norm.running_var)
-        elif u.first:
-            y = ops.stem_conv0_train_fwd(xin, conv.weight)
-        elif isinstance(norm, nn.BatchNorm2d) and fused_stats:
-            # the batch statistics come out of the conv's epilogue: no separate read of y (csrc/conv_stats.hip)
-            cout = conv.out_channels
-            y, stats = ops.conv2d_bn_stats(xin, packs(conv.weight), zeros(cout), conv.in_channels, cout, ks, st, norm.eps,
-                                           norm.momentum, norm.running_mean, norm.running_var)
-        else:
-            cout = conv.out_channels
-            y = ops.conv2d_nhwc(xin, packs(conv.weight), zeros(cout), conv.in_channels, cout, ks, st, False)
-        if isinstance(norm, nn.GroupNorm):
-            stats = ops.gn_train_stats(y, norm.num_groups, norm.eps)
-            z = ops.gn_train_apply(y, norm.num_groups, stats, norm.weight.detach(), norm.bias.detach(), u.relu)
-        else:
-            if stats is None:
-                stats = ops.bn_train_stats(y, norm.eps, norm.momentum, norm.running_mean, norm.running_var)
-            z = ops.bn_train_apply(y, stats, norm.weight.detach(), norm.bias.detach(),
-                                   acts[u.res] if u.res is not None else None, u.relu)
-        acts[u.dst] = z
-        tape.append((y, stats))
+    tape = [_unit_forward(ui, u, acts, packs, zeros, sw, ev) for ui, u in enumerate(units)]
     _count_batches(units)
     return [acts[t] for t in tap_ids], (acts, tape)
 
@@ -464,66 +474,108 @@ class _GradStore(object):
         return p.grad if self.in_place else self.g.get(id(p))
 
 
+def _data_gradient(conv, dy, h, w, residual, packs, zeros, sw):
+    """dL/dx [N, h, w, cin] (+ residual: the gradient already collected for x) of a unit's conv from dL/dy"""
+    ks, st, cin, cout = conv.kernel_size[0], conv.stride[0], conv.in_channels, conv.out_channels
+    if st == 2 and ks == 3 and cin == 64 and cout == 64 and sw.dgrad_s2:
+        # per output parity, 9 tap-products per 2 x 2 pixels instead of 36 and no zero-inserted tensor (csrc/dgrad_s2.hip)
+        return ops.conv3x3s2_dgrad(dy, packs(conv.weight, True), h, w, residual=residual)
+    if st == 2:
+        dy = ops.zero_insert2(dy, h, w)
+    return ops.conv2d_nhwc(dy, packs(conv.weight, True), zeros(cin), cout, cin, ks, 1, False, residual=residual)
+
+
+# what only the whole-network schedule does in a unit's backward: fed = {1x1 conv unit: the unit in front of it, whose BatchNorm
+# backward sums that conv's data gradient leaves behind}, sum_rows = {unit: the rows of such sums} (filled on the way)
+_Fusions = collections.namedtuple('_Fusions', 'fed sum_rows')
+
+
+def _unit_backward(ui, u, dz, units, saved, grads, dead, store, packs, zeros, inv, sw, wgrad, fus=None, trace=None):
+    """The backward of unit ui from dz = dL/d(its activation): norm backward, residual hand-off, weight gradient, data gradient
+    (added to what `grads` holds for the unit's input; none for an input in `dead`).  The one unit backward of both schedules:
+    wgrad(xin, dy, ks, st, targets, producer) forms the conv's weight gradient (targets as ops.WgradFinals.add_wgrad);
+    fus: the _Fusions of the whole-network schedule, which also takes the first unit's one-launch shortcut and re-forms inputs
+    that were never stored; trace: optional list that receives this unit's tensors."""
+    acts, tape = saved
+    conv, norm = u.conv, u.norm
+    y, stats = tape[ui]
+    z = acts[u.dst] if u.relu else None
+    g = None
+    gamma, beta = norm.weight.detach(), norm.bias.detach()
+    dgamma, dbeta = store.target(norm.weight), store.target(norm.bias)
+    snap = [t.clone() for t in (dgamma, dbeta, store.target(conv.weight))] if trace is not None else None
+    if (fus is not None and u.first and isinstance(norm, nn.BatchNorm2d) and not u.eval_norm and u.relu and u.res is None
+            and conv.out_channels == 64 and sw.conv0_bn_wgrad):
+        # the first unit has no data gradient: BatchNorm's sums, then the weight gradient straight from dz and y (no dy tensor)
+        ops.stem_conv0_bn_bwd_wgrad(acts[u.src], dz, y, stats, gamma, beta, inv, dgamma, dbeta, store.target(conv.weight),
+                                    sum_rows=fus.sum_rows.get(ui, 0))
+        return
+    if isinstance(norm, nn.GroupNorm):
+        dy = ops.gn_train_backward(dz, y, z, norm.num_groups, stats, gamma, inv, dgamma, dbeta, True)
+    elif u.eval_norm:
+        # constant statistics: dy does not wait for the sums -- one pass over (dz, y) instead of two
+        dy, g = ops.bn_eval_backward(dz, y, z if u.res is not None else None, stats, gamma, inv, dgamma, dbeta,
+                                     want_g=u.res is not None and u.res not in dead, accumulate=True, relu=u.relu, beta=beta)
+    elif fus is not None and ui in fus.sum_rows:
+        dy = ops.bn_train_backward_rows(dz, y, stats, gamma, beta, inv, dgamma, dbeta, fus.sum_rows[ui])
+    else:
+        # without a residual input the ReLU mask is recomputed from y (one tensor less to read in both passes)
+        dy, g = ops.bn_train_backward(dz, y, z if u.res is not None else None, stats, gamma, inv, dgamma, dbeta,
+                                      want_g=u.res is not None, accumulate=True, relu=u.relu, beta=beta)
+    if u.res is not None and u.res not in dead:
+        grads[u.res] = g if u.res not in grads else grads[u.res] + g
+    xin = acts[u.src]
+    rec = dict(ui=ui, dz=dz, dy=dy, g=g, dx_prev=grads.get(u.src), dx=None) if trace is not None else None
+    dw = store.target(conv.weight)
+    if u.first:
+        ops.stem_conv0_wgrad(xin, dy, inv, out=dw, accumulate=True)
+    else:
+        producer = None
+        if xin is None:         # the input activation was never stored (_deferred_units): re-formed from its producer's y
+            pi = [i for i, p_ in enumerate(units) if p_.dst == u.src][0]
+            producer = (units[pi], tape[pi])
+            xin = tape[pi][0]
+        wgrad(xin, dy, conv.kernel_size[0], conv.stride[0], [(dw, 0, conv.out_channels)], producer)
+        if u.src in dead:          # the input is a frozen activation: no data gradient
+            pass
+        elif fus is not None and ui in fus.fed and u.src not in grads:       # (a 1x1 stride-1 conv)
+            pu, (py, pstats) = units[fus.fed[ui]], tape[fus.fed[ui]]
+            grads[u.src], fus.sum_rows[fus.fed[ui]] = ops.conv1x1_dgrad_bn_bwd_sums(
+                dy, packs(conv.weight, True), zeros(conv.in_channels), py, pstats, pu.norm.weight.detach(), pu.norm.bias.detach())
+        else:
+            grads[u.src] = _data_gradient(conv, dy, xin.size(1), xin.size(2), grads.get(u.src), packs, zeros, sw)
+        if rec is not None:
+            rec['dx'] = grads.get(u.src)
+    if rec is not None:      # this unit's own contribution (the buffers accumulate over shared modules)
+        rec.update(dgamma=dgamma - snap[0], dbeta=dbeta - snap[1], dw=dw - snap[2])
+        trace.append(rec)
+
+
 def backward(units, saved, grads, scale=None, store=None, trace=None):
     """grads: {activation index: dL/dact NHWC fp16 multiplied by `scale`} for the activations consumed outside the units
     (taps for the backbone alone, tower outputs for the whole network).  -> _GradStore of fp32 parameter gradients.
     trace: optional list that receives the per-unit tensors (tests check every unit against PyTorch given the same
     inputs)."""
-    acts, tape = saved
+    sw = switches()
     scale = loss_scale() if scale is None else scale
     inv = 1.0 / scale
     grads = dict(grads)
     store = store if store is not None else _GradStore()
-    zeros = _Zeros(acts[0].device)
+    zeros = _Zeros(saved[0][0].device)
     packs = _Packs(units, True)
     dead = dead_activations(units)
+
+    def wgrad(xin, dy, ks, st, targets, producer=None):
+        ops.conv_wgrad(xin, dy, ks, st, inv, out=targets[0][0], accumulate=True)
+
     for ui in range(len(units) - 1, -1, -1):
         u = units[ui]
         dz = grads.pop(u.dst, None)
         if dz is None or u.frozen:
             continue
-        conv, norm = u.conv, u.norm
-        y, stats = tape[ui]
-        z = acts[u.dst] if u.relu else None
-        g = None
-        dgamma, dbeta, dw = store.target(norm.weight), store.target(norm.bias), store.target(conv.weight)
-        snap = [t.clone() for t in (dgamma, dbeta, dw)] if trace is not None else None
-        if isinstance(norm, nn.GroupNorm):
-            dy = ops.gn_train_backward(dz, y, z, norm.num_groups, stats, norm.weight.detach(), inv, dgamma, dbeta, True)
-        elif u.eval_norm:
-            dy, g = ops.bn_eval_backward(dz, y, z if u.res is not None else None, stats, norm.weight.detach(), inv, dgamma, dbeta,
-                                         want_g=u.res is not None and u.res not in dead, accumulate=True, relu=u.relu,
-                                         beta=norm.bias.detach())
-        else:
-            # without a residual input the ReLU mask is recomputed from y (one tensor less to read in both passes)
-            dy, g = ops.bn_train_backward(dz, y, z if u.res is not None else None, stats, norm.weight.detach(), inv, dgamma,
-                                          dbeta, want_g=u.res is not None, accumulate=True, relu=u.relu,
-                                          beta=norm.bias.detach())
-        if u.res is not None and u.res not in dead:
-            grads[u.res] = g if u.res not in grads else grads[u.res] + g
-        xin = acts[u.src]
-        ks, st = conv.kernel_size[0], conv.stride[0]
-        rec = dict(ui=ui, dz=dz, dy=dy, g=g, dx_prev=grads.get(u.src), dx=None) if trace is not None else None
-        if u.first:
-            ops.stem_conv0_wgrad(xin, dy, inv, out=dw, accumulate=True)
-        else:
-            ops.conv_wgrad(xin, dy, ks, st, inv, out=dw, accumulate=True)
-            cin = conv.in_channels
-            if u.src in dead:          # the input is a frozen activation: no data gradient
-                pass
-            elif (st == 2 and ks == 3 and cin == 64 and conv.out_channels == 64 and os.environ.get('LFD_DGRAD_S2', '1') == '1'):
-                # per output parity, 9 tap-products per 2 x 2 pixels instead of 36 and no zero-inserted tensor (csrc/dgrad_s2.hip)
-                grads[u.src] = ops.conv3x3s2_dgrad(dy, packs(conv.weight, True), xin.size(1), xin.size(2), residual=grads.get(u.src))
-            else:
-                if st == 2:
-                    dy = ops.zero_insert2(dy, xin.size(1), xin.size(2))
-                grads[u.src] = ops.conv2d_nhwc(dy, packs(conv.weight, True), zeros(cin), conv.out_channels, cin, ks, 1,
-                                               False, residual=grads.get(u.src))
-            if rec is not None:
-                rec['dx'] = grads.get(u.src)
-        if rec is not None:      # this unit's own contribution (the buffers accumulate over shared modules)
-            rec.update(dgamma=dgamma - snap[0], dbeta=dbeta - snap[1], dw=dw - snap[2])
-            trace.append(rec)
+        for p in (u.norm.weight, u.norm.bias, u.conv.weight):      # (this path zero-fills a missing gradient buffer before the
+            store.target(p)                                         #  unit's first kernel, the whole-network one where it is used)
+        _unit_backward(ui, u, dz, units, saved, grads, dead, store, packs, zeros, inv, sw, wgrad, trace=trace)
     return store
 
 
@@ -543,7 +595,7 @@ def _out_weight(o):
 
 def _fused_outputs():
     """A/B switch: LFD_OUT_FUSED=0 runs the glue around the output convs as PyTorch ops (~25 launches per level)"""
-    return os.environ.get('LFD_OUT_FUSED', '1') == '1'
+    return switches().out_fused
 
 
 def _out_segs(o):
@@ -555,63 +607,82 @@ def _out_segs(o):
     return segs
 
 
-def _outputs_forward_fused(outs, acts, num_levels):
-    """outputs_forward with one launch per level behind the padded conv (ops.head_out_split) writing straight into the
-    level-concatenated tensors"""
-    sizes = [None] * num_levels
-    for o in outs:
-        sizes[o.level] = tuple(acts[o.src].shape[1:3])
+def _level_starts(sizes):
+    """-> (first point of every pyramid level in the level-concatenated [N, P, C] layout, P)"""
     starts, p = [], 0
     for h, w_ in sizes:
         starts.append(p)
         p += h * w_
-    x0 = acts[outs[0].src]
-    n = x0.size(0)
+    return starts, p
+
+
+def _alloc_full(outs, n, p, dev):
+    """the level-concatenated fp32 prediction tensors {'cls': [N, P, C'], 'reg': [N, P, 4]}"""
     width = {}
     for o in outs:
         for kind, conv in o.convs:
             width[kind] = conv.out_channels
-    full = {k: torch.empty((n, p, c), dtype=torch.float32, device=x0.device) for k, c in width.items()}
+    return {k: torch.empty((n, p, c), dtype=torch.float32, device=dev) for k, c in width.items()}
+
+
+def _out_forward(o, x, wp, bp, wpk, full, start):
+    """the padded conv of one level's output convs, then one launch (ops.head_out_split) that writes its rows straight into the
+    level-concatenated tensors; -> y, kept for the backward"""
+    y = ops.conv2d_nhwc(x, wpk, bp, x.size(3), wp.size(0), 1, 1, False)
+    segs = _out_segs(o)
+    ops.head_out_split(y, segs, [full[sg['kind']] for sg in segs], start)
+    return y
+
+
+def _out_backward(o, x, y, wp, dpack, full, start, store, scale, zeros, wgrad, grads):
+    """the backward of _out_forward: bias / Scale gradients and dy in one launch, wgrad(o, wp, x, dy) for the padded weight, the
+    data gradient (dpack(): the padded weight's data-gradient pack) added to what `grads` holds for the level's activation"""
+    segs = _out_segs(o)
+    for sg in segs:
+        sg['dbias'] = store.target(sg['conv'].bias)
+        sg['dscale'] = store.target(o.scale._scale) if sg['scale'] is not None else None
+    dy = ops.head_out_grad(y, segs, [full[sg['kind']] for sg in segs], start, scale)
+    wgrad(o, wp, x, dy)
+    c = x.size(3)
+    grads[o.src] = ops.conv2d_nhwc(dy, dpack(), zeros(c), wp.size(0), c, 1, 1, False, residual=grads.get(o.src))
+
+
+def _outputs_forward_fused(outs, acts, num_levels):
+    """outputs_forward with one launch per level behind the padded conv writing straight into the level-concatenated tensors"""
+    sizes = [None] * num_levels
+    for o in outs:
+        sizes[o.level] = tuple(acts[o.src].shape[1:3])
+    starts, p = _level_starts(sizes)
+    x0 = acts[outs[0].src]
+    full = _alloc_full(outs, x0.size(0), p, x0.device)
     cache, saved = {}, []
     for o in outs:
-        x = acts[o.src]
-        c = x.size(3)
         key = tuple(id(cv) for _, cv in o.convs)
         if key not in cache:
             wp, bp = _out_weight(o)
             cache[key] = (wp, bp, ops.pack_conv_weight_train(wp))
         wp, bp, wpk = cache[key]
-        y = ops.conv2d_nhwc(x, wpk, bp, c, wp.size(0), 1, 1, False)
-        segs = _out_segs(o)
-        ops.head_out_split(y, segs, [full[sg['kind']] for sg in segs], starts[o.level])
-        saved.append((wp, y))
+        saved.append((wp, _out_forward(o, acts[o.src], wp, bp, wpk, full, starts[o.level])))
     return full['cls'], full['reg'], sizes, saved
 
 
 def _outputs_backward_fused(outs, acts, saved, sizes, dcls, dreg, store, scale):
     grads = {}
     inv = 1.0 / scale
-    starts, p = [], 0
-    for h, w_ in sizes:
-        starts.append(p)
-        p += h * w_
+    starts, _ = _level_starts(sizes)
     zeros = _Zeros(dcls.device)
     packs = _Packs()
     full = {'cls': dcls.contiguous(), 'reg': dreg.contiguous()}
     dws = {}
-    for o, (wp, y) in zip(outs, saved):
-        x = acts[o.src]
-        c = x.size(3)
-        segs = _out_segs(o)
-        for sg in segs:
-            sg['dbias'] = store.target(sg['conv'].bias)
-            sg['dscale'] = store.target(o.scale._scale) if sg['scale'] is not None else None
-        dy = ops.head_out_grad(y, segs, [full[sg['kind']] for sg in segs], starts[o.level], scale)
+
+    def wgrad(o, wp, x, dy):
         key = tuple(id(cv) for _, cv in o.convs)
         if key not in dws:         # one padded weight-gradient buffer per set of (possibly shared) output convs
             dws[key] = (torch.zeros_like(wp), o)
         ops.conv_wgrad(x, dy, 1, 1, inv, out=dws[key][0], accumulate=True)
-        grads[o.src] = ops.conv2d_nhwc(dy, packs(wp, True), zeros(c), wp.size(0), c, 1, 1, False, residual=grads.get(o.src))
+
+    for o, (wp, y) in zip(outs, saved):
+        _out_backward(o, acts[o.src], y, wp, lambda: packs(wp, True), full, starts[o.level], store, scale, zeros, wgrad, grads)
     for dw, o in dws.values():
         r0 = 0
         for _, conv in o.convs:
@@ -623,7 +694,7 @@ def _outputs_backward_fused(outs, acts, saved, sizes, dcls, dreg, store, scale):
 def outputs_forward(outs, acts, num_levels):
     """-> (cls [N,P,C'], reg [N,P,4]) fp32 in the level-concatenated layout of LFD.forward (lfd.py:526-542), sizes per level,
     and what the backward needs."""
-    if _fused_outputs():
+    if switches().out_fused:
         return _outputs_forward_fused(outs, acts, num_levels)
     cls_l, reg_l, sizes, saved = [None] * num_levels, [None] * num_levels, [None] * num_levels, []
     cache = {}
@@ -658,10 +729,7 @@ def outputs_backward(outs, acts, saved, sizes, dcls, dreg, store, scale=None):
     if saved and saved[0][1] is not None and saved[0][1].dtype == torch.float16:      # saved by _outputs_forward_fused
         return _outputs_backward_fused(outs, acts, saved, sizes, dcls, dreg, store, scale)
     inv = 1.0 / scale
-    starts, p = [], 0
-    for h, w_ in sizes:
-        starts.append(p)
-        p += h * w_
+    starts, _ = _level_starts(sizes)
     zeros = _Zeros(dcls.device)
     packs = _Packs()
     for o, (wp, raw) in zip(outs, saved):
@@ -830,7 +898,7 @@ def _as_image(t):
     return None
 
 
-def _concat_forward(cl, units, outs, acts, tape, packs, opk, zeros, fused_stats, full, sizes, starts, n, dev, sc=None):
+def _concat_forward(cl, units, outs, acts, tape, packs, opk, zeros, sw, full, sizes, starts, n, dev, sc=None):
     """neck units per level into A[0]; shared tower units over all levels; output convs over all levels + per-level slices"""
     seg_hw = [h_ * w_ for h_, w_ in sizes]
     ptot = sum(seg_hw)
@@ -842,7 +910,7 @@ def _concat_forward(cl, units, outs, acts, tape, packs, opk, zeros, fused_stats,
     # the neck units: independent of each other -- every conv leaves its statistics rows in a buffer of its own, then TWO launches
     # finish all levels (per-channel finals; apply passes into A[0]) instead of two per level (LFD_BN_LEVELS=0; the same values)
     pending = []
-    batched = fused_stats and sc is not None and os.environ.get('LFD_BN_LEVELS', '1') == '1'
+    batched = sw.conv_bn_stats and sc is not None and sw.bn_levels
     for l in range(len(sizes)):
         ui = cl['lv_units'][l][0]
         u = units[ui]
@@ -855,7 +923,7 @@ def _concat_forward(cl, units, outs, acts, tape, packs, opk, zeros, fused_stats,
                 pending.append((l, ui, (starts[l], r[0], rows, r[1], norm.eps, norm.momentum, norm.running_mean, norm.running_var,
                                         norm.weight.detach(), norm.bias.detach())))
                 continue
-        if fused_stats:
+        if sw.conv_bn_stats:
             y, stats = ops.conv2d_bn_stats(xin, packs(conv.weight), zeros(conv.out_channels), conv.in_channels, conv.out_channels, 1, 1,
                                            norm.eps, norm.momentum, norm.running_mean, norm.running_var)
         else:
@@ -885,7 +953,7 @@ def _concat_forward(cl, units, outs, acts, tape, packs, opk, zeros, fused_stats,
         for l in range(len(sizes)):
             segs = _out_segs(cl['lv_outs'][l][j])
             lv.append((seg_hw[l], starts[l], segs, [full[sg['kind']] for sg in segs]))
-        if os.environ.get('LFD_HEAD_OUT_LEVELS', '1') == '1':
+        if sw.head_out_levels:
             ops.head_out_split_levels(y, lv)          # all levels (their own Scale each) in one launch
         else:
             for hw_, p0_, segs, outs_ in lv:
@@ -894,7 +962,7 @@ def _concat_forward(cl, units, outs, acts, tape, packs, opk, zeros, fused_stats,
     return dict(A=A, Y=Y, yo=yo, seg_hw=seg_hw, ptot=ptot)
 
 
-def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, full, starts, store, wgrad, grads, scale, inv, n, dev, dead=()):
+def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, sw, full, starts, store, wgrad, grads, scale, inv, n, dev, dead=()):
     """the backward of _concat_forward; leaves the gradients of the backbone taps in `grads` (none for a tap in `dead`: the
     output of a frozen unit)"""
     A, Y, seg_hw, ptot = cs['A'], cs['Y'], cs['seg_hw'], cs['ptot']
@@ -913,7 +981,7 @@ def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, full, starts,
                 sg['dbias'] = store.target(sg['conv'].bias)
                 sg['dscale'] = store.target(o.scale._scale) if sg['scale'] is not None else None
             lv.append((seg_hw[l], starts[l], segs, [full[sg['kind']] for sg in segs]))
-        if os.environ.get('LFD_HEAD_OUT_LEVELS', '1') == '1':
+        if sw.head_out_levels:
             ops.head_out_grad_levels(y, lv, scale, dyo)        # all levels in one launch + one final
         else:
             for hw_, p0_, segs, grads_ in lv:
@@ -946,7 +1014,7 @@ def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, full, starts,
     # the neck units' BatchNorm backward: the levels are independent of each other -- three launches for all of them
     # (LFD_BN_LEVELS=0: three per level; the same values)
     dys = None
-    if os.environ.get('LFD_BN_LEVELS', '1') == '1':
+    if sw.bn_levels:
         lv = []
         for l in range(nlev):
             u = units[cl['lv_units'][l][0]]
@@ -972,13 +1040,13 @@ def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, full, starts,
                                        residual=grads.get(u.src))
 
 
-def _deferred_units(units, outs):
+def _deferred_units(units, outs, sw=None):
     """-> {index of a unit whose activation is never stored: index of its only consumer}.  A BatchNorm + ReLU unit without a
     residual whose output feeds exactly one 1x1 stride-1 conv unit (the first conv of each stem pair, lfd_resnet.py:376-413):
     the consumer normalises its operand inside the conv kernel (ops.conv1x1_of_bn_relu_bn_stats) and its weight gradient
     re-forms it (ops.conv1x1_wgrad_partials_of_bn_relu) -- one write and one read of the largest tensors of the iteration less.
     LFD_BN_APPLY_IN_CONV=0: every unit stores its activation."""
-    if os.environ.get('LFD_BN_APPLY_IN_CONV', '1') != '1':
+    if not (sw or switches()).bn_apply_in_conv:
         return {}
     return _stem_pairs(units, outs)
 
@@ -1021,6 +1089,7 @@ def _single_consumers(units, outs):
 
 def network_forward(model, plan, x):
     """-> (cls [N,P,C'], reg [N,P,4], sizes, saved): LFD.forward in train mode (lfd.py:511-542) over the unit schedule"""
+    sw = switches()
     units, outs, nlev = plan
     dev = x.device
     sc = _sched(model, dev)
@@ -1036,16 +1105,8 @@ def network_forward(model, plan, x):
     sizes = [None] * nlev
     for o in outs:
         sizes[o.level] = hw[o.src]
-    starts, p = [], 0
-    for h_, w_ in sizes:
-        starts.append(p)
-        p += h_ * w_
-    width = {}
-    for o in outs:
-        for kind, conv in o.convs:
-            width[kind] = conv.out_channels
-    full = {k: torch.empty((x.size(0), p, c), dtype=torch.float32, device=dev) for k, c in width.items()}
-    fused_stats = os.environ.get('LFD_CONV_BN_STATS', '1') == '1'
+    starts, p = _level_starts(sizes)
+    full = _alloc_full(outs, x.size(0), p, dev)
     cl = None
     if CONCAT_HEAD:
         cl = model.__dict__.get('_lfd_concat_layout', 0)
@@ -1053,75 +1114,31 @@ def network_forward(model, plan, x):
             cl = _concat_layout(units, outs, nlev)
             model.__dict__['_lfd_concat_layout'] = cl
     cs = None
-    defer = _deferred_units(units, outs) if fused_stats else {}
+    defer = _deferred_units(units, outs, sw) if sw.conv_bn_stats else {}
     fed = {v: u for u, v in defer.items()}
     ev = _eval_norms(model, units) if any(u.eval_norm for u in units) else None
     for ui, u in enumerate(units):
-        if u.frozen:
-            acts[u.dst] = _frozen_forward(ui, u, acts, ev)
-        elif u.eval_norm:
-            tape[ui] = _eval_unit_forward(u, acts, packs, zeros, ev)
-        elif u.level is None:
-            tape[ui] = _unit_forward(u, acts, packs, zeros, fused_stats, store=ui not in defer,
+        if u.level is None:
+            tape[ui] = _unit_forward(ui, u, acts, packs, zeros, sw, ev, store=ui not in defer,
                                      producer=(units[fed[ui]], tape[fed[ui]]) if ui in fed else None)
     if cl is not None:
-        cs = _concat_forward(cl, units, outs, acts, tape, packs, opk, zeros, fused_stats, full, sizes, starts, x.size(0), dev, sc)
+        cs = _concat_forward(cl, units, outs, acts, tape, packs, opk, zeros, sw, full, sizes, starts, x.size(0), dev, sc)
     osaved = cs
     if cs is None:     # level by level: heads that do not share their towers, or no usable image view of N * P pixels
         for ui, u in enumerate(units):
             if u.level is not None:
-                tape[ui] = _unit_forward(u, acts, packs, zeros, fused_stats)
+                tape[ui] = _unit_forward(ui, u, acts, packs, zeros, sw, ev)
         osaved = []
         for o in outs:
-            xo = acts[o.src]
-            c = xo.size(3)
             wp, bp, wpk, _ = _out_pack(o, opk)
-            y = ops.conv2d_nhwc(xo, wpk, bp, c, wp.size(0), 1, 1, False)
-            segs = _out_segs(o)
-            ops.head_out_split(y, segs, [full[sg['kind']] for sg in segs], starts[o.level])
-            osaved.append((wp, y))
+            osaved.append((wp, _out_forward(o, acts[o.src], wp, bp, wpk, full, starts[o.level])))
     _count_batches(units)
     return full['cls'], full['reg'], sizes, ((acts, tape), osaved, opk)
 
 
-def _unit_forward(u, acts, packs, zeros, fused_stats, store=True, producer=None):
-    """conv -> norm (batch / group statistics) -> (+ residual) -> ReLU of one unit on the current stream; -> (y, stats).
-    store=False: the activation is not written (_deferred_units: its consumer forms it from (y, stats)); producer = (unit,
-    (y, stats)) of such an input."""
-    conv, norm = u.conv, u.norm
-    xin = acts[u.src]
-    ks, st = conv.kernel_size[0], conv.stride[0]
-    stats = None
-    if producer is not None:
-        pu, (py, pstats) = producer
-        cout = conv.out_channels
-        y, stats = ops.conv1x1_of_bn_relu_bn_stats(py, pstats, pu.norm.weight.detach(), pu.norm.bias.detach(), packs(conv.weight),
-                                                   zeros(cout), cout, norm.eps, norm.momentum, norm.running_mean, norm.running_var)
-    elif u.first and isinstance(norm, nn.BatchNorm2d) and fused_stats:
-        y, stats = ops.stem_conv0_train_fwd_bn_stats(xin, conv.weight, norm.eps, norm.momentum, norm.running_mean,
-                                                     norm.running_var)
-    elif u.first:
-        y = ops.stem_conv0_train_fwd(xin, conv.weight)
-    elif isinstance(norm, nn.BatchNorm2d) and fused_stats:
-        cout = conv.out_channels
-        y, stats = ops.conv2d_bn_stats(xin, packs(conv.weight), zeros(cout), conv.in_channels, cout, ks, st, norm.eps,
-                                       norm.momentum, norm.running_mean, norm.running_var)
-    else:
-        cout = conv.out_channels
-        y = ops.conv2d_nhwc(xin, packs(conv.weight), zeros(cout), conv.in_channels, cout, ks, st, False)
-    if isinstance(norm, nn.GroupNorm):
-        stats, z = ops.gn_train_stats_apply(y, norm.num_groups, norm.eps, norm.weight.detach(), norm.bias.detach(), u.relu)
-    else:
-        if stats is None:
-            stats = ops.bn_train_stats(y, norm.eps, norm.momentum, norm.running_mean, norm.running_var)
-        z = ops.bn_train_apply(y, stats, norm.weight.detach(), norm.bias.detach(),
-                               acts[u.res] if u.res is not None else None, u.relu) if store else None
-    acts[u.dst] = z
-    return y, stats
-
-
 def network_backward(model, plan, saved, sizes, dcls, dreg, scale):
     """the backward of network_forward: parameter gradients accumulate into `.grad` (created zeroed when missing)."""
+    sw = switches()
     units, outs, nlev = plan
     (acts, tape), osaved, opk = saved
     dev = dcls.device
@@ -1134,10 +1151,7 @@ def network_backward(model, plan, saved, sizes, dcls, dreg, scale):
     packs = _Packs(units, True)
     dcls, dreg = dcls.contiguous(), dreg.contiguous()
     full = {'cls': dcls, 'reg': dreg}
-    starts, p = [], 0
-    for h, w_ in sizes:
-        starts.append(p)
-        p += h * w_
+    starts, _ = _level_starts(sizes)
     nj = [0]
 
     def wgrad(xin, dy, ks, st, targets, producer=None):
@@ -1153,98 +1167,37 @@ def network_backward(model, plan, saved, sizes, dcls, dreg, scale):
             ops.conv_wgrad_partials(xin, dy, ks, st, part)
         fin.add_wgrad(part, nwg, nblk, xin.size(3), dy.size(3), ks * ks, inv, targets)
 
-    grads = {}
-    # stem pairs (_stem_pairs, adjacent units only: nothing else may touch the training workspace in between): the 1x1 conv's
-    # data gradient leaves the BatchNorm backward sums of the unit in front of it behind (LFD_BN_SUMS_IN_DGRAD=0: separate pass)
-    fed = {}
-    if os.environ.get('LFD_BN_SUMS_IN_DGRAD', '1') == '1' and os.environ.get('LFD_CONV_BN_STATS', '1') == '1':
-        fed = {v: u_ for u_, v in _stem_pairs(units, outs).items()
-               if v == u_ + 1 and units[u_].conv.out_channels == 64 and units[v].conv.out_channels == 64}
-    sum_rows = {}
-    concat = isinstance(osaved, dict)
-    dead = dead_activations(units)
-    if concat:
-        _concat_backward(model.__dict__['_lfd_concat_layout'], osaved, units, acts, tape, packs, opk, zeros, full, starts, store,
-                         wgrad, grads, scale, inv, dcls.size(0), dev, dead)
-    # ---- output convs, level by level
-    for o, (wp, y) in (() if concat else zip(outs, osaved)):
-        xo = acts[o.src]
-        c = xo.size(3)
-        segs = _out_segs(o)
-        for sg in segs:
-            sg['dbias'] = store.target(sg['conv'].bias)
-            sg['dscale'] = store.target(o.scale._scale) if sg['scale'] is not None else None
-        dy = ops.head_out_grad(y, segs, [full[sg['kind']] for sg in segs], starts[o.level], scale)
+    def out_wgrad(o, wp, xo, dy):
         r0, targets = 0, []
         for _, cv in o.convs:
             targets.append((store.target(cv.weight), r0, r0 + cv.out_channels))
             r0 += cv.out_channels
         wgrad(xo, dy, 1, 1, targets)
-        grads[o.src] = ops.conv2d_nhwc(dy, _out_pack(o, opk)[3], zeros(c), wp.size(0), c, 1, 1, False, residual=grads.get(o.src))
+
+    grads = {}
+    # stem pairs (_stem_pairs, adjacent units only: nothing else may touch the training workspace in between): the 1x1 conv's
+    # data gradient leaves the BatchNorm backward sums of the unit in front of it behind (LFD_BN_SUMS_IN_DGRAD=0: separate pass)
+    fed = {}
+    if sw.bn_sums_in_dgrad and sw.conv_bn_stats:
+        fed = {v: u_ for u_, v in _stem_pairs(units, outs).items()
+               if v == u_ + 1 and units[u_].conv.out_channels == 64 and units[v].conv.out_channels == 64}
+    fus = _Fusions(fed, {})
+    concat = isinstance(osaved, dict)
+    dead = dead_activations(units)
+    if concat:
+        _concat_backward(model.__dict__['_lfd_concat_layout'], osaved, units, acts, tape, packs, opk, zeros, sw, full, starts, store,
+                         wgrad, grads, scale, inv, dcls.size(0), dev, dead)
+    # ---- output convs, level by level
+    for o, (wp, y) in (() if concat else zip(outs, osaved)):
+        _out_backward(o, acts[o.src], y, wp, lambda: _out_pack(o, opk)[3], full, starts[o.level], store, scale, zeros, out_wgrad, grads)
     # ---- conv / norm / ReLU units, last to first
     for ui in range(len(units) - 1, -1, -1):
         u = units[ui]
         if u.dst not in grads or (concat and u.level is not None):
             continue
         dz = grads.pop(u.dst)
-        if u.frozen:
-            continue
-        conv, norm = u.conv, u.norm
-        y, stats = tape[ui]
-        z = acts[u.dst] if u.relu else None
-        g = None
-        if (u.first and isinstance(norm, nn.BatchNorm2d) and not u.eval_norm and u.relu and u.res is None and conv.out_channels == 64
-                and os.environ.get('LFD_CONV0_BN_WGRAD', '1') == '1'):
-            # the first unit has no data gradient: BatchNorm's sums, then the weight gradient straight from dz and y (no dy tensor)
-            ops.stem_conv0_bn_bwd_wgrad(acts[u.src], dz, y, stats, norm.weight.detach(), norm.bias.detach(), inv,
-                                        store.target(norm.weight), store.target(norm.bias), store.target(conv.weight),
-                                        sum_rows=sum_rows.get(ui, 0))
-            continue
-        if isinstance(norm, nn.GroupNorm):
-            dy = ops.gn_train_backward(dz, y, z, norm.num_groups, stats, norm.weight.detach(), inv, store.target(norm.weight),
-                                       store.target(norm.bias), True)
-        elif u.eval_norm:
-            # constant statistics: dy does not wait for the sums -- one pass over (dz, y) instead of two
-            dy, g = ops.bn_eval_backward(dz, y, z if u.res is not None else None, stats, norm.weight.detach(), inv,
-                                         store.target(norm.weight), store.target(norm.bias),
-                                         want_g=u.res is not None and u.res not in dead, accumulate=True, relu=u.relu,
-                                         beta=norm.bias.detach())
-        elif ui in sum_rows:
-            dy = ops.bn_train_backward_rows(dz, y, stats, norm.weight.detach(), norm.bias.detach(), inv, store.target(norm.weight),
-                                            store.target(norm.bias), sum_rows[ui])
-        else:
-            # without a residual input the ReLU mask is recomputed from y (one tensor less to read in both passes)
-            dy, g = ops.bn_train_backward(dz, y, z if u.res is not None else None, stats, norm.weight.detach(), inv,
-                                          store.target(norm.weight), store.target(norm.bias), want_g=u.res is not None,
-                                          accumulate=True, relu=u.relu, beta=norm.bias.detach())
-        if u.res is not None and u.res not in dead:
-            grads[u.res] = g if u.res not in grads else grads[u.res] + g
-        xin = acts[u.src]
-        ks, st = conv.kernel_size[0], conv.stride[0]
-        if u.first:
-            ops.stem_conv0_wgrad(xin, dy, inv, out=store.target(conv.weight), accumulate=True)
-            continue
-        producer = None
-        if xin is None:         # the input activation was never stored (_deferred_units): re-formed from its producer's y
-            pi = [i for i, p_ in enumerate(units) if p_.dst == u.src][0]
-            producer = (units[pi], tape[pi])
-            xin = tape[pi][0]
-        wgrad(xin, dy, ks, st, [(store.target(conv.weight), 0, conv.out_channels)], producer)
-        cin = conv.in_channels
-        if u.src in dead:          # the input is a frozen activation: no data gradient
-            continue
-        if st == 2 and ks == 3 and cin == 64 and conv.out_channels == 64 and os.environ.get('LFD_DGRAD_S2', '1') == '1':
-            # per output parity, 9 tap-products per 2 x 2 pixels instead of 36 and no zero-inserted tensor (csrc/dgrad_s2.hip)
-            grads[u.src] = ops.conv3x3s2_dgrad(dy, packs(conv.weight, True), xin.size(1), xin.size(2), residual=grads.get(u.src))
-        elif ui in fed and u.src not in grads:
-            pu, (py, pstats) = units[fed[ui]], tape[fed[ui]]
-            grads[u.src], sum_rows[fed[ui]] = ops.conv1x1_dgrad_bn_bwd_sums(dy, packs(conv.weight, True), zeros(cin), py, pstats,
-                                                                            pu.norm.weight.detach(), pu.norm.bias.detach())
-        else:
-            if st == 2:
-                dy = ops.zero_insert2(dy, xin.size(1), xin.size(2))
-            grads[u.src] = ops.conv2d_nhwc(dy, packs(conv.weight, True), zeros(cin), conv.out_channels, cin, ks, 1, False,
-                                           residual=grads.get(u.src))
+        if not u.frozen:
+            _unit_backward(ui, u, dz, units, (acts, tape), grads, dead, store, packs, zeros, inv, sw, wgrad, fus)
     fin.launch()
 
 

@@ -386,6 +386,27 @@ def test_output_conv_segments_follow_the_padded_weight_rows(monkeypatch):
     assert not te._fused_outputs()
 
 
+def test_training_switches_are_read_at_call_time(monkeypatch):
+    """train_engine.switches(): the eight A/B switches of the training schedules default to on, '0' flips exactly the
+    field of the variable set, and the environment is read by every call (the GPU tests flip switches between two passes of
+    one process)."""
+    from lfd_amd import train_engine as te
+    env = dict(conv_bn_stats='LFD_CONV_BN_STATS', dgrad_s2='LFD_DGRAD_S2', out_fused='LFD_OUT_FUSED', bn_levels='LFD_BN_LEVELS',
+               head_out_levels='LFD_HEAD_OUT_LEVELS', bn_apply_in_conv='LFD_BN_APPLY_IN_CONV',
+               bn_sums_in_dgrad='LFD_BN_SUMS_IN_DGRAD', conv0_bn_wgrad='LFD_CONV0_BN_WGRAD')
+    for name in env.values():
+        monkeypatch.delenv(name, raising=False)
+    defaults = te.switches()
+    assert defaults._fields == tuple(env) and all(v is True for v in defaults)
+    with pytest.raises(AttributeError):
+        defaults.dgrad_s2 = False                      # immutable: a pass cannot change its switches half way
+    for field, name in env.items():
+        monkeypatch.setenv(name, '0')
+        assert te.switches() == defaults._replace(**{field: False}), name
+        monkeypatch.delenv(name)
+        assert te.switches() == defaults, name
+
+
 def test_every_loss_the_lfd_constructor_accepts_is_provided():
     """lfd.py:52-66: classification loss in {BCEWithLogitsLoss, FocalLoss, CrossEntropyLoss, QualityFocalLoss}, regression
     loss in {SmoothL1Loss, MSELoss} ('independent') or {IoULoss, GIoULoss, DIoULoss, CIoULoss} ('union'): all importable
