@@ -524,6 +524,35 @@ LFD_API int lfd_pack_level_outputs_f32(const float* src, float* dst, int32_t n, 
                                        int32_t count, int32_t total_points, int32_t point_offset, float scale, int32_t op,
                                        lfd_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training pass of the FPN / SimpleFPN necks: the backward of the element-wise operators above and the bias gradient of a plain
+ * conv (csrc/sibling_train.hip).  Gradients are NHWC fp16 carrying the loss scale; fp32 arithmetic, one rounding to fp16.  Every
+ * kernel is a gather (no atomics): two runs give the same bits.  Nothing is launched when a status code is returned.
+ *   lfd_upsample_nearest_add_bwd_nhwc_f16  replaces the autograd backward of `lateral[i-1] += nn.Upsample(size,
+ *                                       mode='nearest')(lateral[i])` (lfd/model/neck/fpn.py:133-135, simple_fpn.py:147-157):
+ *                                       g_src[n,yy,xx,:] += sum of g_dst[n,y,x,:] over the (y, x) whose forward source index
+ *                                       min(floorf(y * float(h)/H), h-1) (same for x) is (yy, xx) -- the forward's expression
+ *                                       evaluated per candidate.  g_src [n,h,w,c] in place, g_dst [n,H,W,c]; no aliasing.
+ *   lfd_maxpool3x3s2_bwd_nhwc_f16       replaces the autograd backward of the extra_type='pooling' level, nn.MaxPool2d(3, 2, 1)
+ *                                       (fpn.py:74, simple_fpn.py:92): g_in[n,y,x,:] (+= if accumulate) g_out of every window
+ *                                       whose argmax is (y, x); x [n,h,w,c] is the forward input, the argmax is recomputed:
+ *                                       the FIRST position in scan order that attains the maximum (ATen's strict `>` update).
+ *   lfd_relu_bwd_add_f16                replaces the autograd backward of the nn.ReLU(inplace=True) in front of an extra level
+ *                                       (fpn.py:66-79, simple_fpn.py:84-99), which rewrites the previous output level as well:
+ *                                       out = (g_a + g_b) * [y > 0], g_b nullable; out may be g_a or g_b.
+ *   lfd_bias_grad_nhwc_f16              replaces the autograd bias gradient of the nn.Conv2d(bias=True) laterals / output
+ *                                       convs (fpn.py:57-82): dbias[c] += inv_scale * sum over rows of dy[row, c]; dy
+ *                                       [rows, c] fp16, c in {32, 64, 128}; fp32 partial sums per block, fixed-order fp64
+ *                                       final.  workspace: lfd_bias_grad_workspace_bytes(). */
+LFD_API int lfd_upsample_nearest_add_bwd_nhwc_f16(void* g_src, const void* g_dst, int32_t n, int32_t H, int32_t W, int32_t h,
+                                                  int32_t w, int32_t c, lfd_stream_t stream);
+LFD_API int lfd_maxpool3x3s2_bwd_nhwc_f16(const void* x, const void* g_out, void* g_in, int32_t n, int32_t h, int32_t w,
+                                          int32_t c, int32_t accumulate, lfd_stream_t stream);
+LFD_API int lfd_relu_bwd_add_f16(const void* y, const void* g_a, const void* g_b, void* out, int64_t count, lfd_stream_t stream);
+LFD_API size_t lfd_bias_grad_workspace_bytes(void);
+LFD_API int lfd_bias_grad_nhwc_f16(const void* dy, int64_t rows, int32_t c, float inv_scale, float* dbias, void* workspace,
+                                   size_t workspace_bytes, lfd_stream_t stream);
+
 /* Parity instrument (not on the product path): the same MFMA conv kernels with the fp32 accumulators (conv + bias, no
  * activation, no fp16 rounding) written to out_f32 [n, oh, ow, cout].  Used by the engine's G1 mode (SURVEY 8d gate G1:
  * fp32 inter-layer storage, operands split into fp16 hi + lo parts, three launches per conv).  desc->relu / tail_* ignored

@@ -285,6 +285,11 @@ _SIGNATURES = {
     'lfd_relu_inplace_f16': (C.c_int, [_P, _I64, _P]),
     'lfd_maxpool3x3s2_nhwc_f16': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
     'lfd_pack_level_outputs_f32': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _I32, _P]),
+    'lfd_upsample_nearest_add_bwd_nhwc_f16': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    'lfd_maxpool3x3s2_bwd_nhwc_f16': (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P]),
+    'lfd_relu_bwd_add_f16': (C.c_int, [_P, _P, _P, _P, _I64, _P]),
+    'lfd_bias_grad_workspace_bytes': (_SZ, []),
+    'lfd_bias_grad_nhwc_f16': (C.c_int, [_P, _I64, _I32, _F, _P, _P, _SZ, _P]),
     'lfd_detect_workspace_reset': (C.c_int, [C.POINTER(DetectDesc), _I32, _P, _SZ, _P]),
     'lfd_detect_from_candidates': (C.c_int, [C.POINTER(DetectDesc), _I32, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     'lfd_decode_all': (C.c_int, [C.POINTER(DetectDesc), _I32, _P, _P, _I32, _P, _P, _P, _P]),

@@ -14,8 +14,12 @@ Same constructor kwargs, `forward(x) -> (cls [N,P,C], reg [N,P,4] distances, cen
                       batch) and the three-launch fused loss (csrc/getloss_fcos.hip), one host sync; with
                       `device_targets = False`, or loss modules the fused kernels do not cover: targets with the
                       reference's [P,G] tensor algebra on the host (:108-209), losses op by op on the HIP loss kernels
-  train-mode forward  PyTorch-ROCm autograd over the same parameters (training-only route, as for LFD)
+  train-mode forward  backbone + FPN neck as one autograd node on the hand-written kernels (train_engine.PyramidTrainFunction,
+                      when train_engine.pyramid_supported holds; LFD_HIP_NECK=0: backbone node + the neck under autograd); the
+                      head under PyTorch-ROCm autograd over the same parameters (training-only route, as for LFD)
 """
+import os
+
 import torch
 import torch.nn as nn
 
@@ -109,11 +113,17 @@ class FCOS(nn.Module):
 
     def _forward_train(self, x):
         _lib.require_cuda(x, 'FCOS.forward')
-        if train_engine.supported(self._backbone):
-            feats = list(train_engine.backbone_train_forward(self._backbone, x))
+        hip = os.environ.get('LFD_HIP_TRAIN', '1') != '0'
+        if hip and train_engine.switches().hip_neck and train_engine.pyramid_supported(self._backbone, self._neck):
+            # backbone + neck as one node: the taps stay NHWC fp16, the neck runs on the hand-written kernels
+            feats = train_engine.backbone_neck_train_forward(self._backbone, self._neck, x)
         else:
-            feats = LFD._backbone_train_torch(self, x)
-        cls_l, reg_l, ctr_l = self._head(self._neck(feats))
+            if train_engine.supported(self._backbone):
+                feats = list(train_engine.backbone_train_forward(self._backbone, x))
+            else:
+                feats = LFD._backbone_train_torch(self, x)
+            feats = self._neck(feats)
+        cls_l, reg_l, ctr_l = self._head(feats)
         outs = []
         for i, c in enumerate(cls_l):
             self._head_indexes_to_feature_map_sizes[i] = (c.shape[2], c.shape[3])

@@ -253,7 +253,8 @@ class LFD(nn.Module):
         """Train-mode forward (batch-statistic BatchNorm, per-image GroupNorm, autograd graph).  For the shipped
         configurations the WHOLE network -- backbone, neck, head towers, output convs -- runs forward and backward on the
         hand-written kernels as one autograd node (train_engine.NetworkTrainFunction); a supported backbone under an
-        unsupported neck / head runs as its own node with PyTorch-ROCm modules behind it.  LFD_HIP_TRAIN=0 or an
+        unsupported neck / head runs as its own node with PyTorch-ROCm modules behind it -- together with an FPN / SimpleFPN
+        neck that train_engine.pyramid_supported admits (PyramidTrainFunction; LFD_HIP_NECK=0: the backbone alone).  LFD_HIP_TRAIN=0 or an
         unsupported backbone: everything through PyTorch-ROCm autograd (same parameters, same semantics)."""
         neck, head = self._neck, self._head
         hip = x.is_cuda and os.environ.get('LFD_HIP_TRAIN', '1') != '0'
@@ -262,14 +263,18 @@ class LFD(nn.Module):
             for i, sz in enumerate(sizes):
                 self._head_indexes_to_feature_map_sizes[i] = sz
             return cls, reg
-        if hip and train_engine.supported(self._backbone):
-            feats = list(train_engine.backbone_train_forward(self._backbone, x))
+        if hip and train_engine.switches().hip_neck and train_engine.pyramid_supported(self._backbone, neck):
+            # FPN / SimpleFPN: backbone + neck as one node (the taps stay NHWC fp16, the neck runs on the hand-written kernels)
+            feats = train_engine.backbone_neck_train_forward(self._backbone, neck, x)
         else:
-            feats = self._backbone_train_torch(x)
-        if type(neck).__name__ == 'SimpleNeck':
-            feats = [getattr(neck, 'neck%d' % i)(f) for i, f in enumerate(feats)]
-        else:
-            feats = neck(feats)                    # FPN / SimpleFPN: autograd over their PyTorch-ROCm children
+            if hip and train_engine.supported(self._backbone):
+                feats = list(train_engine.backbone_train_forward(self._backbone, x))
+            else:
+                feats = self._backbone_train_torch(x)
+            if type(neck).__name__ == 'SimpleNeck':
+                feats = [getattr(neck, 'neck%d' % i)(f) for i, f in enumerate(feats)]
+            else:
+                feats = neck(feats)                    # FPN / SimpleFPN: autograd over their PyTorch-ROCm children
         cls_l, reg_l = [], []
         for i, t in enumerate(feats):
             t = getattr(head, 'head%d_merge_path' % i)(t)

@@ -7,8 +7,16 @@ nn.Sequential with the reference's member order, so state_dict keys match (`late
 
 Inference arithmetic runs on the gfx950 kernels (..engine_sibling: conv / upsample-add / relu / maxpool behind the C ABI).
 Inside a meta-architecture the whole network goes through the engine at once; called stand-alone in eval mode the neck
-converts its NCHW fp32 inputs, runs the same kernels and returns NCHW fp32.  Under autograd (training) the children run as
-PyTorch-ROCm modules on the device -- the training-only route the LFD class documents as well; CPU tensors are refused.
+converts its NCHW fp32 inputs, runs the same kernels and returns NCHW fp32.
+
+Training.  Inside FCOS / LFD / LFDv2 the neck does not run through this module's forward at all when
+train_engine.pyramid_supported(backbone, neck) holds: backbone + neck are ONE autograd node on NHWC fp16 activations
+(train_engine.PyramidTrainFunction) -- laterals, smoothing and extra-level convs on the conv / norm training kernels, the merge,
+the in-place ReLU and the pooling forward on csrc/sibling.hip, their backward and the bias gradients on
+csrc/sibling_train.hip.  That includes the configurations autograd refuses (ReLU laterals merged with `+=`, or re-ReLU'd in
+place in front of an extra level).  Called stand-alone under autograd, with LFD_HIP_NECK=0, or in a configuration the node does
+not cover (other widths, a frozen parameter, an eval-mode lateral BatchNorm), the children run as PyTorch-ROCm modules on the
+device -- the route below; CPU tensors are refused.
 """
 import torch
 import torch.nn as nn

@@ -797,6 +797,70 @@ def pack_level_outputs(src, dst, c0, count, point_offset, scale=1.0, exp=False):
     return dst
 
 
+def upsample_nearest_add_backward_(g_src, g_dst):
+    """g_src [N,h,w,C] += the adjoint of upsample_nearest_add_ applied to g_dst [N,H,W,C] (fp16 NHWC, in place)"""
+    _nhwc16(g_src, 'upsample_nearest_add_backward')
+    _nhwc16(g_dst, 'upsample_nearest_add_backward')
+    n, H, W, c = g_dst.shape
+    if g_src.shape[0] != n or g_src.shape[3] != c:
+        raise RuntimeError('upsample_nearest_add_backward: batch / channel mismatch')
+    with torch.cuda.device(g_src.device):
+        check(lib().lfd_upsample_nearest_add_bwd_nhwc_f16(ptr(g_src), ptr(g_dst), n, H, W, g_src.shape[1], g_src.shape[2], c,
+                                                          stream_ptr()), 'lfd_upsample_nearest_add_bwd_nhwc_f16')
+    return g_src
+
+
+def maxpool3x3s2_backward(x, g_out, g_in=None):
+    """gradient of maxpool3x3s2(x) w.r.t. x from g_out; added to g_in when given (in place), else a new tensor"""
+    _nhwc16(x, 'maxpool3x3s2_backward')
+    _nhwc16(g_out, 'maxpool3x3s2_backward')
+    n, h, w_, c = x.shape
+    if tuple(g_out.shape) != (n, (h - 1) // 2 + 1, (w_ - 1) // 2 + 1, c) or (g_in is not None and g_in.shape != x.shape):
+        raise RuntimeError('maxpool3x3s2_backward: shape mismatch')
+    acc = g_in is not None
+    with torch.cuda.device(x.device):
+        if not acc:
+            g_in = torch.empty_like(x)
+        else:
+            _nhwc16(g_in, 'maxpool3x3s2_backward')
+        check(lib().lfd_maxpool3x3s2_bwd_nhwc_f16(ptr(x), ptr(g_out), ptr(g_in), n, h, w_, c, int(acc), stream_ptr()),
+              'lfd_maxpool3x3s2_bwd_nhwc_f16')
+    return g_in
+
+
+def relu_backward_add(y, g_a, g_b=None, out=None):
+    """(g_a + g_b) * [y > 0] as fp16 (fp32 add, one rounding); g_b optional; out may be g_a"""
+    _nhwc16(y, 'relu_backward_add')
+    _nhwc16(g_a, 'relu_backward_add')
+    if g_a.shape != y.shape or (g_b is not None and (g_b.shape != y.shape or g_b.dtype != torch.float16 or not g_b.is_contiguous())):
+        raise RuntimeError('relu_backward_add: shape mismatch')
+    with torch.cuda.device(y.device):
+        if out is None:
+            out = torch.empty_like(y)
+        check(lib().lfd_relu_bwd_add_f16(ptr(y), ptr(g_a), ptr(g_b), ptr(out), y.numel(), stream_ptr()), 'lfd_relu_bwd_add_f16')
+    return out
+
+
+_bias_ws = {}
+
+
+def bias_grad_(dy, inv_scale, dbias):
+    """dbias [C] fp32 += inv_scale * sum of dy [.., C] fp16 over every leading axis (deterministic two-stage sum)"""
+    require_cuda(dy, 'bias_grad')
+    c = dy.size(-1)
+    if dy.dtype != torch.float16 or not dy.is_contiguous() or dbias.dtype != torch.float32 or dbias.numel() != c \
+            or not dbias.is_contiguous():
+        raise RuntimeError('bias_grad: contiguous fp16 [.., C] gradient and fp32 [C] target expected')
+    key = (dy.device.type, dy.device.index, torch.cuda.current_stream(dy.device).cuda_stream)
+    ws = _bias_ws.get(key)
+    if ws is None:
+        ws = _bias_ws[key] = torch.empty(lib().lfd_bias_grad_workspace_bytes(), dtype=torch.uint8, device=dy.device)
+    with torch.cuda.device(dy.device):
+        check(lib().lfd_bias_grad_nhwc_f16(ptr(dy), dy.numel() // c, c, float(inv_scale), ptr(dbias), ptr(ws), ws.numel(),
+                                           stream_ptr()), 'lfd_bias_grad_nhwc_f16')
+    return dbias
+
+
 def fasterblock_fused(x, w1_packed, b1, w2_packed, b2, out=None):
     """relu(conv3x3(relu(conv3x3(x, w1) + b1), w2) + b2 + x) for NHWC fp16 [N,H,W,64] in one launch (csrc/block.hip)."""
     require_cuda(x, 'fasterblock_fused')

@@ -37,14 +37,22 @@ def set_loss_scale(v):
     _scale_state['value'] = v
 
 
-_Switches = collections.namedtuple('_Switches', 'conv_bn_stats dgrad_s2 out_fused bn_levels head_out_levels bn_apply_in_conv '
-                                                'bn_sums_in_dgrad conv0_bn_wgrad')
+_SchedSwitches = collections.namedtuple('_Switches', 'conv_bn_stats dgrad_s2 out_fused bn_levels head_out_levels bn_apply_in_conv '
+                                                     'bn_sums_in_dgrad conv0_bn_wgrad')
+
+
+class _Switches(_SchedSwitches):
+    """the eight switches of the training schedules (the tuple: what a pass hands down) and, beside them, hip_neck: the ROUTING
+    switch of the pyramid-neck node, read by the models when they choose a route and by no schedule"""
+    hip_neck = True
 
 
 def switches():
     """The A/B switches of the training schedules (all on by default; what '0' runs instead stands beside each), read from the
-    environment at every call: the public entries call this once per pass and hand the record down."""
-    return _Switches(
+    environment at every call: the public entries call this once per pass and hand the record down.  `.hip_neck`
+    (LFD_HIP_NECK, default on): FPN / SimpleFPN necks run inside the backbone's autograd node (PyramidTrainFunction); '0'
+    restores the backbone node with the neck as PyTorch-ROCm modules under autograd."""
+    sw = _Switches(
         conv_bn_stats=os.environ.get('LFD_CONV_BN_STATS', '1') == '1',           # conv, then a statistics pass over y
         dgrad_s2=os.environ.get('LFD_DGRAD_S2', '1') == '1',                     # zero_insert2 + stride-1 conv (3x3 stride-2 dgrad)
         out_fused=os.environ.get('LFD_OUT_FUSED', '1') == '1',                   # output-conv glue as PyTorch ops (serial API only)
@@ -53,6 +61,8 @@ def switches():
         bn_apply_in_conv=not os.environ.get('LFD_BN_APPLY_IN_CONV', '1') != '1',  # every unit stores its activation
         bn_sums_in_dgrad=os.environ.get('LFD_BN_SUMS_IN_DGRAD', '1') == '1',     # every BatchNorm backward sums for itself
         conv0_bn_wgrad=os.environ.get('LFD_CONV0_BN_WGRAD', '1') == '1')         # first unit: norm backward, then weight gradient
+    sw.hip_neck = os.environ.get('LFD_HIP_NECK', '1') == '1'
+    return sw
 
 
 class _Unit(object):
@@ -1269,3 +1279,266 @@ def network_train_forward(model, x):
         model.__dict__['_lfd_train_plan'] = plan
     cls, reg = NetworkTrainFunction.apply(model, plan, x, *network_params(plan[0], plan[1]))
     return cls, reg, NetworkTrainFunction.last_sizes
+
+
+# ---------------------------------------------------------------------------------------------- backbone + pyramid neck
+# FPN / SimpleFPN (lfd/model/neck/fpn.py:127-152, simple_fpn.py:141-172) behind the backbone in ONE autograd node: the taps stay
+# NHWC fp16, the neck's convs / norms run on the kernels of the units, its element-wise operators on csrc/sibling.hip forward
+# and csrc/sibling_train.hip backward.  The plan is a list of steps over activation indices (the units' numbering goes on):
+#   ('unit', ui)                 lateral conv (no bias) -> norm -> ReLU?: a _Unit, through _unit_forward / _unit_backward
+#   ('conv', _NeckConv)          conv + bias (-> ReLU): laterals without a norm, FPN's 3x3 smoothing convs, 'conv' extra levels
+#   ('merge', dst, src, new)     new = dst + nearest_upsample(src), written over dst (a copy of dst is kept only when its
+#                                producer's backward needs its own output as the ReLU mask)
+#   ('relu', a, new)             nn.ReLU(inplace=True) in front of an extra level: a's tensor is rewritten, so EVERY consumer of
+#                                it -- the head, which gets the previous output level -- sees relu(a)
+#   ('pool', src, dst)           'pooling' extra level, MaxPool2d(3, 2, 1)
+class _NeckConv(object):
+    __slots__ = ('conv', 'relu', 'src', 'dst')
+    first = frozen = False           # (what _Packs asks of a unit)
+
+
+class _PyramidPlan(object):
+    __slots__ = ('bb_units', 'units', 'tap_ids', 'steps', 'out_ids', 'convs', 'params', 'owner')
+
+
+def _lateral_parts(neck, i):
+    """-> (conv, norm | None, relu) of lateral{i}: Sequential(conv, [norm], [ReLU])"""
+    mods = list(getattr(neck, 'lateral%d' % i))
+    norm = mods[1] if len(mods) > 1 and isinstance(mods[1], (nn.BatchNorm2d, nn.GroupNorm)) else None
+    return mods[0], norm, isinstance(mods[-1], nn.ReLU)
+
+
+def pyramid_supported(backbone, neck):
+    """backbone + neck as one node (PyramidTrainFunction): a `supported` backbone under an FPN or a SimpleFPN (top-down or
+    neighbouring_mode) whose taps and outputs have 64 or 128 channels, every parameter taking a gradient.  Lateral norm: none, a
+    train-mode affine BatchNorm2d that tracks its statistics, or an affine GroupNorm in groups of 8 channels -- with or without
+    relu_on_lateral: the GroupNorm backward kernel takes its ReLU mask from an optional stored output, so it has a form
+    without a ReLU (lfd_gn_train_bwd_f16 with z == NULL) and nothing is refused on that account.  The combination autograd
+    refuses -- ReLU laterals re-ReLU'd in place in front of an extra level -- is admitted: the second ReLU is the identity on
+    values and its mask equals the first one's.  Everything else keeps the backbone node with the neck under autograd."""
+    if type(neck).__name__ not in ('FPN', 'SimpleFPN') or not neck.training or not supported(backbone):
+        return False
+    chans = list(neck._num_input_channels_list) + [neck._num_output_channels]
+    if any(c not in (64, 128) for c in chans) or list(backbone.num_output_channels_list) != list(neck._num_input_channels_list):
+        return False
+    if not all(p.requires_grad for p in neck.parameters()):
+        return False
+    for m in neck.modules():
+        if isinstance(m, nn.Conv2d) and not (_conv_ok(m) and m.in_channels in (64, 128) and m.out_channels in (64, 128)):
+            return False
+    for i in range(neck._num_inputs):
+        conv, norm, _ = _lateral_parts(neck, i)
+        if (norm is None) != (conv.bias is not None):
+            return False
+        if isinstance(norm, nn.BatchNorm2d) and (norm.momentum is None or not norm.affine or not norm.track_running_stats
+                                                 or not norm.training):
+            return False
+        if isinstance(norm, nn.GroupNorm) and (not norm.affine or norm.num_channels != 8 * norm.num_groups):
+            return False
+    return True
+
+
+def build_pyramid(backbone, neck):
+    """-> _PyramidPlan: the backbone's units, then the neck's steps in the order FPN.forward / SimpleFPN.forward run them"""
+    b = _Builder()
+    taps = _build_backbone(b, backbone)
+    p = _PyramidPlan()
+    p.bb_units, p.tap_ids, p.steps, p.convs, p.owner = list(b.units), taps, [], [], backbone
+
+    def new_act():
+        b.n_act += 1
+        return b.n_act - 1
+
+    def conv_step(conv, relu, src):
+        nc = _NeckConv()
+        nc.conv, nc.relu, nc.src, nc.dst = conv, relu, src, new_act()
+        p.steps.append(('conv', nc))
+        p.convs.append(nc)
+        return nc.dst
+
+    L = neck._num_inputs
+    lat = []
+    for i, tap in enumerate(taps):
+        conv, norm, relu = _lateral_parts(neck, i)
+        if norm is not None:
+            lat.append(b.add(conv, norm, relu, tap))
+            p.steps.append(('unit', len(b.units) - 1))
+            p.convs.append(b.units[-1])
+        else:
+            lat.append(conv_step(conv, relu, tap))
+    for i in (range(L - 1) if neck._bottom_up else range(L - 1, 0, -1)):
+        dst, src = (i, i + 1) if neck._bottom_up else (i - 1, i)
+        # top-down lat[src] is already merged, bottom-up it is not yet (its own merge is the next step): the index says which
+        merged = new_act()
+        p.steps.append(('merge', lat[dst], lat[src], merged))
+        lat[dst] = merged
+    outs = []
+    for i in range(neck._num_outputs):
+        mods = list(getattr(neck, 'fpn_out%d' % i))
+        if i < L:
+            outs.append(conv_step(mods[0], False, lat[i]) if mods else lat[i])
+            continue
+        from_input = i == L and neck._extra_on_input
+        src = taps[-1] if from_input else outs[-1]
+        if isinstance(mods[0], nn.ReLU):
+            mods = mods[1:]
+            if not from_input:          # (a backbone tap left a ReLU: the in-place ReLU changes neither it nor its gradient)
+                r = new_act()
+                p.steps.append(('relu', src, r))
+                outs[-1] = src = r
+        if isinstance(mods[0], nn.Conv2d):
+            outs.append(conv_step(mods[0], False, src))
+        else:
+            d = new_act()
+            p.steps.append(('pool', src, d))
+            outs.append(d)
+    p.units, p.out_ids = b.units, outs
+    ps = backbone_params(b.units)
+    for kind, *a in p.steps:
+        if kind == 'conv':
+            ps += [a[0].conv.weight, a[0].conv.bias]
+    p.params = _unique(ps)
+    return p
+
+
+def _needs_own_output(plan, act):
+    """does the backward of the step that produced `act` read act's own values (the ReLU mask)?  A BatchNorm unit recomputes the
+    mask from its conv output; a GroupNorm unit and a conv + bias + ReLU step read the stored output."""
+    for kind, *a in plan.steps:
+        if kind == 'unit' and plan.units[a[0]].dst == act:
+            u = plan.units[a[0]]
+            return u.relu and isinstance(u.norm, nn.GroupNorm)
+        if kind == 'conv' and a[0].dst == act:
+            return a[0].relu
+    return False
+
+
+def pyramid_forward(plan, x):
+    """-> (neck outputs NHWC fp16, saved)"""
+    sw = switches()
+    n_bb = len(plan.bb_units)
+    _, (acts, tape) = forward(plan.bb_units, plan.tap_ids, x, plan.owner)
+    tape = tape + [None] * (len(plan.units) - n_bb)
+    zeros = _Zeros(x.device)
+    packs = _Packs(plan.convs, False)
+    for kind, *a in plan.steps:
+        if kind == 'unit':
+            tape[a[0]] = _unit_forward(a[0], plan.units[a[0]], acts, packs, zeros, sw)
+        elif kind == 'conv':
+            nc, cv = a[0], a[0].conv
+            acts[nc.dst] = ops.conv2d_nhwc(acts[nc.src], packs(cv.weight), cv.bias.detach(), cv.in_channels, cv.out_channels,
+                                           cv.kernel_size[0], cv.stride[0], nc.relu)
+        elif kind == 'merge':
+            dst, src, new = a
+            t = acts[dst].clone() if _needs_own_output(plan, dst) else acts[dst]
+            acts[new] = ops.upsample_nearest_add_(t, acts[src])
+        elif kind == 'relu':
+            acts[a[1]] = ops.relu_(acts[a[0]])
+        else:
+            acts[a[1]] = ops.maxpool3x3s2(acts[a[0]])
+    _count_batches(plan.units[n_bb:])
+    return [acts[o] for o in plan.out_ids], (acts, tape)
+
+
+def pyramid_backward(plan, saved, grads, scale=None, store=None):
+    """grads: {activation index: dL/d(neck output) NHWC fp16 times `scale`}.  The neck's steps last to first, then the backbone's
+    units (backward); parameter gradients go to `store`."""
+    sw = switches()
+    scale = loss_scale() if scale is None else scale
+    inv = 1.0 / scale
+    acts, tape = saved
+    grads = dict(grads)
+    store = store if store is not None else _GradStore()
+    zeros = _Zeros(acts[0].device)
+    packs = _Packs(plan.convs, True)
+    dead = dead_activations(plan.units)
+    relu_made = {a[1] for kind, *a in plan.steps if kind == 'relu'}
+    side = {}          # {ReLU'd activation: the gradient of the extra level behind it}: joined with the head's by the ReLU backward
+
+    def wgrad(xin, dy, ks, st, targets, producer=None):
+        ops.conv_wgrad(xin, dy, ks, st, inv, out=targets[0][0], accumulate=True)
+
+    for kind, *a in reversed(plan.steps):
+        if kind == 'unit':
+            ui, u = a[0], plan.units[a[0]]
+            dz = grads.pop(u.dst, None)
+            if dz is not None:
+                for p_ in (u.norm.weight, u.norm.bias, u.conv.weight):
+                    store.target(p_)
+                _unit_backward(ui, u, dz, plan.units, saved, grads, dead, store, packs, zeros, inv, sw, wgrad)
+        elif kind == 'conv':
+            nc, cv = a[0], a[0].conv
+            dz = grads.pop(nc.dst, None)
+            if dz is None:
+                continue
+            if nc.relu:
+                dz = ops.relu_backward_add(acts[nc.dst], dz)
+            xin = acts[nc.src]
+            ops.bias_grad_(dz, inv, store.target(cv.bias))
+            wgrad(xin, dz, cv.kernel_size[0], cv.stride[0], [(store.target(cv.weight), 0, cv.out_channels)])
+            if nc.src in dead:
+                continue
+            prev = None if nc.src in relu_made else grads.get(nc.src)
+            gx = _data_gradient(cv, dz, xin.size(1), xin.size(2), prev, packs, zeros, sw)
+            (side if nc.src in relu_made else grads)[nc.src] = gx
+        elif kind == 'merge':
+            dst, src, new = a
+            g = grads.pop(new, None)
+            if g is None:
+                continue
+            grads[dst] = g          # (dst has no other consumer: its tensor became `new`)
+            if src not in grads:
+                grads[src] = torch.zeros_like(acts[src])
+            ops.upsample_nearest_add_backward_(grads[src], g)
+        elif kind == 'relu':
+            src, r = a
+            g, gb = grads.pop(r, None), side.pop(r, None)
+            if g is None and gb is None:
+                continue
+            if g is None:
+                g, gb = gb, None
+            grads[src] = ops.relu_backward_add(acts[r], g, gb, out=g)
+        else:
+            src, d = a
+            g = grads.pop(d, None)
+            if g is None:
+                continue
+            if src in relu_made:
+                side[src] = ops.maxpool3x3s2_backward(acts[src], g)
+            elif src not in dead:
+                grads[src] = ops.maxpool3x3s2_backward(acts[src], g, grads.get(src))
+    n_bb = len(plan.bb_units)
+    return backward(plan.bb_units, (acts, tape[:n_bb]), grads, scale=scale, store=store)
+
+
+class PyramidTrainFunction(torch.autograd.Function):
+    """neck outputs (NCHW fp32) = neck(backbone(x)) as one autograd node: the taps never leave NHWC fp16 (used when the head is not
+    covered by network_supported and pyramid_supported holds)."""
+
+    @staticmethod
+    def forward(ctx, plan, x, *params):
+        outs, saved = pyramid_forward(plan, x)
+        ctx.plan, ctx.saved = plan, saved
+        return tuple(t.permute(0, 3, 1, 2).float() for t in outs)
+
+    @staticmethod
+    def backward(ctx, *out_grads):
+        plan = ctx.plan
+        grads = {}
+        scale = loss_scale()
+        for o, g in zip(plan.out_ids, out_grads):
+            if g is not None:
+                grads[o] = (g * scale).permute(0, 2, 3, 1).contiguous().half()
+        pyramid_backward(plan, ctx.saved, grads, scale=scale, store=_GradStore(in_place=True))
+        ctx.saved = None
+        return (None, None) + (None,) * len(plan.params)     # gradients were accumulated into .grad directly
+
+
+def backbone_neck_train_forward(backbone, neck, x):
+    """-> the neck's outputs, NCHW fp32 (what `neck(backbone taps)` returns under autograd)"""
+    check_train_input(backbone, x)
+    plan = neck.__dict__.get('_lfd_pyramid_plan')
+    if plan is None or plan.owner is not backbone:
+        plan = build_pyramid(backbone, neck)
+        neck.__dict__['_lfd_pyramid_plan'] = plan
+    return PyramidTrainFunction.apply(plan, x, *plan.params)
