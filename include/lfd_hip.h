@@ -1067,6 +1067,46 @@ LFD_API int lfd_head_out_grad_levels_w_f16(const void* y_concat, int32_t n, int6
                                    int32_t nlevels, int32_t rows, float loss_scale, void* dy_concat, void* workspace,
                                    size_t workspace_bytes, lfd_stream_t stream);
 
+/* The glue around FCOSHead's output convs in a training iteration (csrc/fcos_out.hip), all pyramid levels in one launch.
+ * Replaces, forward, fcos_head.py:140-150 (`exp(Scale_i(regression conv))`, the classification / centerness outputs) and
+ * fcos.py:414-449 (permute + reshape + concatenation of the levels along the point axis), and, backward, what autograd runs for
+ * them.  The engine runs a level's three 3x3 convs as TWO convs padded to `rows` (32 | 64) output rows with fp32 outputs
+ * (lfd_conv2d_nhwc_f16_acc32): raw_cls [n, hw, rows] holds classification in rows [0, C) and centerness in row C, raw_reg
+ * [n, hw, rows] the regression rows [0, 4); the other rows are zero.
+ *   lfd_fcos_out_pack_levels_f32: cls[img, point0 + p, c] = raw_cls[img, p, c], ctr[img, point0 + p, 0] = raw_cls[img, p, C],
+ *     reg[img, point0 + p, k] = expf(raw_reg[img, p, k] * *scale) -- the bits lfd_pack_level_outputs_f32 gives on the same raw
+ *     values.  cls [n, points_total, C], reg [n, points_total, 4], ctr [n, points_total, 1] fp32; every element of a level's
+ *     point range is written.
+ *   lfd_fcos_out_grad_levels_f32: from dcls / dreg / dctr (layouts of cls / reg / ctr), the stored `reg` and raw_reg writes
+ *     dy_cls = d * loss_scale and dy_reg = dreg * reg * *scale * loss_scale [n, hw, rows] fp16 (one fp16 rounding of the
+ *     correctly rounded fp32 value; rows outside the segments ZERO) and ACCUMULATES dbias_cls[c] += sum dcls,
+ *     dbias_ctr[0] += sum dctr, dbias_reg[k] += sum dreg * reg * *scale over ALL levels (one rounding of the fp64 total) and, per
+ *     level, *dscale += sum_k sum dreg * reg * raw_reg, through per-block fp32 partials in `workspace`
+ *     (lfd_fcos_out_grad_workspace_bytes; lfd_train_workspace_bytes() covers it) and one fixed-order fp64 final launch: no
+ *     atomics, equal bits run after run.
+ * `levels`: host array.  raw_*, dy_*, reg, dreg, workspace: 16-byte aligned.  LFD_ERR_INVALID_ARGUMENT: a null / misaligned
+ * pointer, rows not 32 | 64, num_classes + 1 > rows, nlevels > LFD_MAX_LEVELS, a point range outside points_total;
+ * LFD_ERR_UNSUPPORTED: n * hw * rows >= 2^31 (32-bit indices); LFD_ERR_WORKSPACE_TOO_SMALL. */
+typedef struct lfd_fcos_out_level {
+  const float* raw_cls;  /* pack: [n, hw, rows] fp32 (grad: unused, nullable) */
+  const float* raw_reg;  /* [n, hw, rows] fp32 */
+  const float* scale;    /* device scalar: the level's Scale */
+  float* dscale;         /* grad: device scalar, += */
+  void* dy_cls;          /* grad: [n, hw, rows] fp16 */
+  void* dy_reg;          /* grad: [n, hw, rows] fp16 */
+  int32_t hw;            /* pixels per image of the level */
+  int32_t reserved;
+  int64_t point0;        /* first point of the level inside an image of the concatenated tensors */
+} lfd_fcos_out_level_t;
+LFD_API size_t lfd_fcos_out_grad_workspace_bytes(int32_t nlevels, int32_t rows);
+LFD_API int lfd_fcos_out_pack_levels_f32(const lfd_fcos_out_level_t* levels, int32_t nlevels, int32_t n, int32_t rows,
+                                         int32_t num_classes, int64_t points_total, float* cls, float* reg, float* ctr,
+                                         lfd_stream_t stream);
+LFD_API int lfd_fcos_out_grad_levels_f32(const lfd_fcos_out_level_t* levels, int32_t nlevels, int32_t n, int32_t rows,
+                                         int32_t num_classes, int64_t points_total, const float* dcls, const float* dreg,
+                                         const float* dctr, const float* reg, float loss_scale, float* dbias_cls, float* dbias_ctr,
+                                         float* dbias_reg, void* workspace, size_t workspace_bytes, lfd_stream_t stream);
+
 /* first stem conv (3 -> channels, 3x3 stride 2 pad 1, lfd_resnet.py:358,:378) on the NCHW fp32 image batch:
  * forward -> y NHWC fp16 (pre-norm), and its weight gradient (OIHW fp32); channels in {32, 64} */
 LFD_API int lfd_stem_conv0_train_fwd(const float* x_nchw, int32_t n, int32_t h, int32_t w, int32_t channels,

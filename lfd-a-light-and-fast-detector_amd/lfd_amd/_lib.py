@@ -51,6 +51,12 @@ class HeadOutLevel(C.Structure):
     _fields_ = [('hw', C.c_int32), ('nsegs', C.c_int32), ('point0', C.c_int64), ('segs', HeadOutSeg * 2)]
 
 
+class FcosOutLevel(C.Structure):
+    """lfd_fcos_out_level_t"""
+    _fields_ = [('raw_cls', C.c_void_p), ('raw_reg', C.c_void_p), ('scale', C.c_void_p), ('dscale', C.c_void_p),
+                ('dy_cls', C.c_void_p), ('dy_reg', C.c_void_p), ('hw', C.c_int32), ('reserved', C.c_int32), ('point0', C.c_int64)]
+
+
 class BnBwdLevel(C.Structure):
     """lfd_bn_bwd_level_t"""
     _fields_ = [('y', C.c_void_p), ('dy', C.c_void_p), ('stats', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p),
@@ -361,6 +367,11 @@ _SIGNATURES = {
     'lfd_head_out_grad_concat_w_f16': (C.c_int, [_P, _I32, _I32, _I64, _I64, C.POINTER(HeadOutSeg), _I32, _I32, _F, _P, _P, _SZ, _P]),
     'lfd_head_out_split_levels_w_f16': (C.c_int, [_P, _I32, _I64, C.POINTER(HeadOutLevel), _I32, _I32, _P]),
     'lfd_head_out_grad_levels_w_f16': (C.c_int, [_P, _I32, _I64, C.POINTER(HeadOutLevel), _I32, _I32, _F, _P, _P, _SZ, _P]),
+    # the glue around FCOSHead's output convs, all levels in one launch (csrc/fcos_out.hip)
+    'lfd_fcos_out_grad_workspace_bytes': (_SZ, [_I32, _I32]),
+    'lfd_fcos_out_pack_levels_f32': (C.c_int, [C.POINTER(FcosOutLevel), _I32, _I32, _I32, _I32, _I64, _P, _P, _P, _P]),
+    'lfd_fcos_out_grad_levels_f32': (C.c_int, [C.POINTER(FcosOutLevel), _I32, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _F, _P, _P, _P,
+                                               _P, _SZ, _P]),
     'lfd_stem_conv0_train_fwd_bn_stats': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _F, _F, _P, _P, _P, _SZ, _P, _P]),
     'lfd_stem_conv0_wgrad': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _SZ, _P, _P]),
     'lfd_stem_conv0_bn_bwd_wgrad': (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _I32, _P, _SZ, _P, _P, _P, _P]),

@@ -14,9 +14,12 @@ Same constructor kwargs, `forward(x) -> (cls [N,P,C], reg [N,P,4] distances, cen
                       batch) and the three-launch fused loss (csrc/getloss_fcos.hip), one host sync; with
                       `device_targets = False`, or loss modules the fused kernels do not cover: targets with the
                       reference's [P,G] tensor algebra on the host (:108-209), losses op by op on the HIP loss kernels
-  train-mode forward  backbone + FPN neck as one autograd node on the hand-written kernels (train_engine.PyramidTrainFunction,
-                      when train_engine.pyramid_supported holds; LFD_HIP_NECK=0: backbone node + the neck under autograd); the
-                      head under PyTorch-ROCm autograd over the same parameters (training-only route, as for LFD)
+  train-mode forward  backbone + FPN neck + GroupNorm FCOSHead as ONE autograd node on the hand-written kernels
+                      (train_engine.DetectorTrainFunction, when train_engine.fcos_head_supported holds: towers through the
+                      engine's conv / GroupNorm units, output convs with fp32 logits, csrc/fcos_out.hip around them).
+                      LFD_HIP_HEAD=0, or a head the node does not admit: backbone + neck as one node
+                      (train_engine.PyramidTrainFunction) and the head under PyTorch-ROCm autograd over the same parameters;
+                      LFD_HIP_NECK=0: backbone node, neck and head under autograd
 """
 import os
 
@@ -114,7 +117,14 @@ class FCOS(nn.Module):
     def _forward_train(self, x):
         _lib.require_cuda(x, 'FCOS.forward')
         hip = os.environ.get('LFD_HIP_TRAIN', '1') != '0'
-        if hip and train_engine.switches().hip_neck and train_engine.pyramid_supported(self._backbone, self._neck):
+        sw = train_engine.switches()
+        if hip and sw.hip_neck and sw.hip_head and train_engine.fcos_head_supported(self._backbone, self._neck, self._head):
+            # backbone + neck + head as one node: it returns the level-concatenated tensors get_loss reads
+            cls, reg, ctr, sizes = train_engine.detector_train_forward(self._backbone, self._neck, self._head, x)
+            for i, hw in enumerate(sizes):
+                self._head_indexes_to_feature_map_sizes[i] = hw
+            return cls, reg, ctr
+        if hip and sw.hip_neck and train_engine.pyramid_supported(self._backbone, self._neck):
             # backbone + neck as one node: the taps stay NHWC fp16, the neck runs on the hand-written kernels
             feats = train_engine.backbone_neck_train_forward(self._backbone, self._neck, x)
         else:

@@ -6,8 +6,11 @@ the level's learnable Scale and exp (:145-146).  Member names follow the referen
 `_regression_path.{k}`, `_classification`, `_centerness`, `_regression`, `_scales.{i}._scale`) so state_dict keys match;
 init: N(0, 0.01) weights, zero biases, classification bias = -log((1 - 0.01) / 0.01) (:83-127).
 
-Execution: inside FCOS.forward the whole network runs on the gfx950 engine (..engine_sibling); under autograd the children
-run as PyTorch-ROCm modules on the device (training-only route); CPU tensors are refused.
+Execution: inside FCOS.forward the whole network runs on the gfx950 engine (..engine_sibling).  In training mode a GroupNorm
+head behind an FPN runs inside the detector's autograd node on the hand-written kernels (train_engine.fcos_head_supported /
+DetectorTrainFunction), which reads these modules' parameters and never calls `forward`; every other head (no norm, BatchNorm
+towers, no tower layers, LFD_HIP_HEAD=0) runs `forward` below: the children as PyTorch-ROCm modules under autograd.  CPU tensors
+are refused.
 """
 import math
 

@@ -1638,6 +1638,67 @@ def head_out_grad(y, segs, grads, point0, loss_scale):
     return dy
 
 
+def _f32c(t, what, shape=None):
+    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError('%s: contiguous fp32 tensor%s expected, got %s %s'
+                           % (what, '' if shape is None else ' %s' % (tuple(shape),), t.dtype, tuple(t.shape)))
+    return t
+
+
+def _fcos_out_levels(levels, n, rows, backward, what):
+    """levels: [dict(raw_cls, raw_reg [n, h, w, rows] fp32, scale, point0 (+ dscale, dy_cls, dy_reg [n, h, w, rows] fp16))] ->
+    lfd_fcos_out_level_t array"""
+    arr = (_lib.FcosOutLevel * len(levels))()
+    for a, lv in zip(arr, levels):
+        raw = _f32c(lv['raw_reg'], what)
+        if raw.dim() != 4 or raw.size(0) != n or raw.size(3) != rows:
+            raise RuntimeError('%s: raw_reg must be [n, h, w, %d]' % (what, rows))
+        a.raw_reg, a.scale = raw.data_ptr(), _f32c(lv['scale'], what).data_ptr()
+        a.hw, a.point0 = raw.size(1) * raw.size(2), int(lv['point0'])
+        if backward:
+            for k in ('dy_cls', 'dy_reg'):
+                t = lv[k]
+                if t.dtype != torch.float16 or not t.is_contiguous() or tuple(t.shape) != tuple(raw.shape):
+                    raise RuntimeError('%s: %s must be contiguous fp16 %s' % (what, k, tuple(raw.shape)))
+            a.dy_cls, a.dy_reg, a.dscale = lv['dy_cls'].data_ptr(), lv['dy_reg'].data_ptr(), _f32c(lv['dscale'], what).data_ptr()
+        else:
+            a.raw_cls = _f32c(lv['raw_cls'], what, raw.shape).data_ptr()
+    return arr
+
+
+def fcos_out_pack_levels(levels, cls, reg, ctr):
+    """FCOSHead's outputs of ALL levels in one launch (lfd_fcos_out_pack_levels_f32): from the levels' padded fp32 conv outputs
+    raw_cls (rows [0, C) classification, row C centerness) and raw_reg (rows [0, 4)) into the level-concatenated cls [n, P, C],
+    reg [n, P, 4] = expf(raw * scale_i), ctr [n, P, 1].  levels: [dict(raw_cls, raw_reg, scale, point0)]."""
+    require_cuda(cls, 'fcos_out_pack_levels')
+    n, p, c = cls.shape
+    _f32c(cls, 'fcos_out_pack_levels'), _f32c(reg, 'fcos_out_pack_levels', (n, p, 4)), _f32c(ctr, 'fcos_out_pack_levels', (n, p, 1))
+    rows = levels[0]['raw_reg'].size(-1)
+    arr = _fcos_out_levels(levels, n, rows, False, 'fcos_out_pack_levels')
+    with torch.cuda.device(cls.device):
+        check(lib().lfd_fcos_out_pack_levels_f32(arr, len(levels), n, rows, c, p, ptr(cls), ptr(reg), ptr(ctr), stream_ptr()),
+              'lfd_fcos_out_pack_levels_f32')
+
+
+def fcos_out_grad_levels(levels, dcls, dreg, dctr, reg, loss_scale, dbias_cls, dbias_ctr, dbias_reg):
+    """the backward of fcos_out_pack_levels in one launch + one final (lfd_fcos_out_grad_levels_f32): writes every level's dy_cls /
+    dy_reg (fp16, times loss_scale, padded rows zero) and accumulates dbias_cls [C], dbias_ctr [1], dbias_reg [4] and the levels'
+    dscale in place.  levels: [dict(raw_reg, scale, point0, dscale, dy_cls, dy_reg)]; reg: the forward's output."""
+    require_cuda(dcls, 'fcos_out_grad_levels')
+    n, p, c = dcls.shape
+    what = 'fcos_out_grad_levels'
+    _f32c(dcls, what), _f32c(dreg, what, (n, p, 4)), _f32c(dctr, what, (n, p, 1)), _f32c(reg, what, (n, p, 4))
+    if _f32c(dbias_cls, what).numel() != c or _f32c(dbias_ctr, what).numel() != 1 or _f32c(dbias_reg, what).numel() != 4:
+        raise RuntimeError('fcos_out_grad_levels: bias gradients of %d, 1 and 4 elements expected' % c)
+    rows = levels[0]['raw_reg'].size(-1)
+    arr = _fcos_out_levels(levels, n, rows, True, what)
+    ws = train_workspace(dcls.device)
+    with torch.cuda.device(dcls.device):
+        check(lib().lfd_fcos_out_grad_levels_f32(arr, len(levels), n, rows, c, p, ptr(dcls), ptr(dreg), ptr(dctr), ptr(reg),
+                                                 float(loss_scale), ptr(dbias_cls), ptr(dbias_ctr), ptr(dbias_reg), ptr(ws),
+                                                 ws.numel(), stream_ptr()), 'lfd_fcos_out_grad_levels_f32')
+
+
 def _stem_conv0_cin(x_nchw, weight, what):
     """input channels of a first-stem-conv call: 3 (RGB, csrc/train.hip) or 1 (gray, csrc/stem_gray_train.hip); anything else,
     or a weight whose in_channels disagree with the batch, raises before any launch"""

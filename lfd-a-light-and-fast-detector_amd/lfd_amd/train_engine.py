@@ -42,16 +42,20 @@ _SchedSwitches = collections.namedtuple('_Switches', 'conv_bn_stats dgrad_s2 out
 
 
 class _Switches(_SchedSwitches):
-    """the eight switches of the training schedules (the tuple: what a pass hands down) and, beside them, hip_neck: the ROUTING
-    switch of the pyramid-neck node, read by the models when they choose a route and by no schedule"""
+    """the eight switches of the training schedules (the tuple: what a pass hands down) and, beside them, hip_neck / hip_head: the
+    ROUTING switches of the pyramid-neck node and of the detector node on top of it, read by the models when they choose a route
+    and by no schedule"""
     hip_neck = True
+    hip_head = True
 
 
 def switches():
     """The A/B switches of the training schedules (all on by default; what '0' runs instead stands beside each), read from the
     environment at every call: the public entries call this once per pass and hand the record down.  `.hip_neck`
     (LFD_HIP_NECK, default on): FPN / SimpleFPN necks run inside the backbone's autograd node (PyramidTrainFunction); '0'
-    restores the backbone node with the neck as PyTorch-ROCm modules under autograd."""
+    restores the backbone node with the neck as PyTorch-ROCm modules under autograd.  `.hip_head` (LFD_HIP_HEAD, default on): an
+    FCOSHead behind such a neck runs inside the same node (DetectorTrainFunction); '0' keeps the pyramid node with the head
+    under autograd.  The head node sits on the pyramid node: LFD_HIP_NECK=0 turns both off."""
     sw = _Switches(
         conv_bn_stats=os.environ.get('LFD_CONV_BN_STATS', '1') == '1',           # conv, then a statistics pass over y
         dgrad_s2=os.environ.get('LFD_DGRAD_S2', '1') == '1',                     # zero_insert2 + stride-1 conv (3x3 stride-2 dgrad)
@@ -62,6 +66,7 @@ def switches():
         bn_sums_in_dgrad=os.environ.get('LFD_BN_SUMS_IN_DGRAD', '1') == '1',     # every BatchNorm backward sums for itself
         conv0_bn_wgrad=os.environ.get('LFD_CONV0_BN_WGRAD', '1') == '1')         # first unit: norm backward, then weight gradient
     sw.hip_neck = os.environ.get('LFD_HIP_NECK', '1') == '1'
+    sw.hip_head = os.environ.get('LFD_HIP_HEAD', '1') == '1'
     return sw
 
 
@@ -813,8 +818,8 @@ def _sched(plan_owner, dev):
 
 
 def _out_packs(sc, outs):
-    """{ids of a level's output convs: (padded weight [rows, C, 1, 1], padded bias [rows], forward pack, data-gradient pack), rows
-    64 or 128}: the
+    """{ids of a level's output convs: (padded weight [rows, C, k, k], padded bias [rows], forward pack, data-gradient pack), rows
+    64 or 128; k = 1 for LFDHead, 3 for FCOSHead}: the
     rows of the convs are gathered into persistent zero-padded buffers by ONE launch (lfd_rows_sum_batched_f32 with one source
     row = a batched copy), then packed; shared heads: once for all levels"""
     cache, jobs = {}, []
@@ -826,7 +831,7 @@ def _out_packs(sc, outs):
         rows = -(-sum(cv.out_channels for _, cv in o.convs) // 64) * 64
         wp = sc.bufs.get(('outw', key))
         if wp is None:
-            wp = torch.zeros((rows, c, 1, 1), dtype=torch.float32, device=sc.dev)
+            wp = torch.zeros((rows,) + tuple(o.convs[0][1].weight.shape[1:]), dtype=torch.float32, device=sc.dev)
             sc.bufs[('outw', key)] = wp
             sc.bufs[('outb', key)] = torch.zeros(rows, dtype=torch.float32, device=sc.dev)
         bp = sc.bufs[('outb', key)]
@@ -1298,7 +1303,8 @@ class _NeckConv(object):
 
 
 class _PyramidPlan(object):
-    __slots__ = ('bb_units', 'units', 'tap_ids', 'steps', 'out_ids', 'convs', 'params', 'owner')
+    # n_act: the first activation index the plan does not use (the detector plan numbers the head's activations from it)
+    __slots__ = ('bb_units', 'units', 'tap_ids', 'steps', 'out_ids', 'convs', 'params', 'owner', 'n_act')
 
 
 def _lateral_parts(neck, i):
@@ -1392,7 +1398,7 @@ def build_pyramid(backbone, neck):
             d = new_act()
             p.steps.append(('pool', src, d))
             outs.append(d)
-    p.units, p.out_ids = b.units, outs
+    p.units, p.out_ids, p.n_act = b.units, outs, b.n_act
     ps = backbone_params(b.units)
     for kind, *a in p.steps:
         if kind == 'conv':
@@ -1537,8 +1543,217 @@ class PyramidTrainFunction(torch.autograd.Function):
 def backbone_neck_train_forward(backbone, neck, x):
     """-> the neck's outputs, NCHW fp32 (what `neck(backbone taps)` returns under autograd)"""
     check_train_input(backbone, x)
+    plan = _pyramid_plan(backbone, neck)
+    return PyramidTrainFunction.apply(plan, x, *plan.params)
+
+
+def _pyramid_plan(backbone, neck):
     plan = neck.__dict__.get('_lfd_pyramid_plan')
     if plan is None or plan.owner is not backbone:
         plan = build_pyramid(backbone, neck)
         neck.__dict__['_lfd_pyramid_plan'] = plan
-    return PyramidTrainFunction.apply(plan, x, *plan.params)
+    return plan
+
+
+# ---------------------------------------------------------------------------------------------- backbone + pyramid neck + FCOSHead
+# FCOSHead (lfd/model/head/fcos_head.py:20-154) behind the pyramid node, in the SAME autograd node: two towers of 3x3 conv ->
+# GroupNorm -> ReLU units shared by all levels (through _unit_forward / _unit_backward: shared weights are packed once, every
+# parameter gradient accumulates over the levels), then per level two output convs padded to FCOS_OUT_ROWS rows with fp32
+# outputs (ops.conv2d_nhwc_f32out) -- rows [0, C) `_classification` and row C `_centerness` on the classification tower, rows
+# [0, 4) `_regression` on the regression tower -- and csrc/fcos_out.hip on both sides of them.  The node returns what
+# FCOS.get_loss reads: (cls [N,P,C], reg [N,P,4], ctr [N,P,1]) fp32, level-concatenated.
+FCOS_OUT_ROWS = 64       # both tower widths: forward 128 -> 64 and 64 -> 64 are instances of csrc/conv_acc32.hip, the data gradient
+#                          64 -> 128 and 64 -> 64 (3x3 stride 1) of csrc/conv.hip; the glue also has a 32-row form
+
+
+def fcos_head_supported(backbone, neck, head):
+    """backbone + neck + head as one node (DetectorTrainFunction): pyramid_supported(backbone, neck) and a training-mode FCOSHead
+    with one Scale per neck output whose towers are num_layers >= 1 units of 3x3 conv -> affine GroupNorm in groups of 8
+    channels -> ReLU, 64 or 128 input and head channels, every parameter taking a gradient, and
+    num_classes + 1 <= FCOS_OUT_ROWS (classification and centerness share one padded conv).  NOT admitted -- these keep the
+    pyramid node with the head under PyTorch-ROCm autograd: norm_cfg=None, BatchNorm towers (a BatchNorm shared by the levels
+    updates its running statistics level after level: its own piece of work), num_layers == 0, more classes, and
+    LFDHead / LFDHeadV1 behind an FPN."""
+    if type(head).__name__ != 'FCOSHead' or not head.training:
+        return False
+    if not pyramid_supported(backbone, neck) or len(head._scales) != neck._num_outputs:
+        return False
+    cfg = head._norm_cfg
+    if cfg is None or cfg.get('type') != 'GroupNorm' or head._num_head_channels != 8 * cfg.get('num_groups', 0):
+        return False
+    if head._num_layers < 1 or head._num_input_channels not in (64, 128) or head._num_head_channels not in (64, 128):
+        return False
+    if head._num_input_channels != neck._num_output_channels:
+        return False
+    if any(isinstance(m, nn.GroupNorm) and not m.affine for m in head.modules()):
+        return False
+    if not all(p.requires_grad for p in head.parameters()):
+        return False
+    return head._num_classes + 1 <= FCOS_OUT_ROWS
+
+
+class _DetectorPlan(object):
+    """pyramid: the _PyramidPlan; units: the head's tower units (their own list: tape indices are positions in it, activation
+    indices go on from the pyramid's); outs: per level two _Out records, (cls + ctr) then (reg, with the level's Scale)"""
+    __slots__ = ('pyramid', 'units', 'outs', 'rows', 'num_classes', 'params', 'head')
+
+
+def out_row_ranges(o):
+    """[(conv, first row, end row)] of an output record's convs inside its padded conv"""
+    return [(sg['conv'], sg['row0'], sg['row0'] + sg['channels']) for sg in _out_segs(o)]
+
+
+def build_detector(backbone, neck, head):
+    """-> _DetectorPlan: the pyramid plan, then per level, in FCOSHead.forward's order (fcos_head.py:129-150), the classification
+    tower's units, the regression tower's units and the two output records"""
+    pp = _pyramid_plan(backbone, neck)
+    b = _Builder()
+    b.n_act = pp.n_act
+    d = _DetectorPlan()
+    d.pyramid, d.outs, d.rows, d.num_classes, d.head = pp, [], FCOS_OUT_ROWS, head._num_classes, head
+
+    def tower(path, cur):
+        mods = list(path)
+        for i in range(0, len(mods), 3):          # (conv, norm, ReLU) triples
+            cur = b.add(mods[i], mods[i + 1], True, cur)
+        return cur
+
+    for i, src in enumerate(pp.out_ids):
+        b.level = i
+        csrc, rsrc = tower(head._classification_path, src), tower(head._regression_path, src)
+        for convs, s, scale in (([('cls', head._classification), ('ctr', head._centerness)], csrc, None),
+                                ([('reg', head._regression)], rsrc, head._scales[i])):
+            o = _Out()
+            o.level, o.convs, o.src, o.scale = i, convs, s, scale
+            d.outs.append(o)
+    d.units = b.units
+    ps = list(pp.params)
+    for u in d.units:
+        ps += [u.conv.weight, u.norm.weight, u.norm.bias]
+    for o in d.outs:
+        for _, conv in o.convs:
+            ps += [conv.weight, conv.bias]
+        if o.scale is not None:
+            ps.append(o.scale._scale)
+    d.params = _unique(ps)
+    return d
+
+
+def detector_forward(plan, x):
+    """-> (cls [N,P,C], reg [N,P,4], ctr [N,P,1] fp32, [(h, w)] per level, saved)"""
+    sw = switches()
+    pp = plan.pyramid
+    feats, (acts, tape) = pyramid_forward(pp, x)
+    dev = x.device
+    n = x.size(0)
+    zeros = _Zeros(dev)
+    packs = _Packs(plan.units, False)
+    htape = [_unit_forward(ui, u, acts, packs, zeros, sw) for ui, u in enumerate(plan.units)]
+    sizes = [tuple(f.shape[1:3]) for f in feats]
+    starts, p = _level_starts(sizes)
+    opk = _out_packs(_sched(plan.head, dev), plan.outs)
+    raws = {}
+    for o in plan.outs:
+        wp, bp, wpk, _ = _out_pack(o, opk)
+        xin = acts[o.src]
+        raws[(o.level, o.convs[0][0])] = ops.conv2d_nhwc_f32out(xin, wpk, bp, xin.size(3), wp.size(0), 3, 1)
+    cls = torch.empty((n, p, plan.num_classes), dtype=torch.float32, device=dev)
+    reg = torch.empty((n, p, 4), dtype=torch.float32, device=dev)
+    ctr = torch.empty((n, p, 1), dtype=torch.float32, device=dev)
+    scales = {o.level: o.scale._scale.detach() for o in plan.outs if o.scale is not None}
+    ops.fcos_out_pack_levels([dict(raw_cls=raws[(l, 'cls')], raw_reg=raws[(l, 'reg')], scale=scales[l], point0=starts[l])
+                              for l in range(len(sizes))], cls, reg, ctr)
+    raw_reg = [raws[(l, 'reg')] for l in range(len(sizes))]
+    return cls, reg, ctr, sizes, ((acts, tape), htape, opk, raw_reg, starts)
+
+
+def detector_backward(plan, saved, reg, dcls, dreg, dctr, scale):
+    """the backward of detector_forward: output-conv glue (+ the bias / Scale finals), the output convs' weight and data
+    gradients, the tower units last to first, then pyramid_backward with the gradients collected at the neck's outputs.
+    Parameter gradients accumulate into `.grad` (created zeroed when missing)."""
+    sw = switches()
+    pp, head = plan.pyramid, plan.head
+    (acts, tape), htape, opk, raw_reg, starts = saved
+    dev = dcls.device
+    inv = 1.0 / scale
+    store = _GradStore(in_place=True)
+    sc = _sched(head, dev)
+    fin = sc.finals
+    fin.reset()
+    zeros = _Zeros(dev)
+    packs = _Packs(plan.units, True)
+    dead = dead_activations(pp.units)
+    dys, levels = {}, []
+    for o in plan.outs:
+        if o.scale is None:
+            continue
+        l = o.level
+        dys[(l, 'cls')], dys[(l, 'reg')] = (torch.empty(raw_reg[l].shape, dtype=torch.float16, device=dev) for _ in range(2))
+        levels.append(dict(raw_reg=raw_reg[l], scale=o.scale._scale.detach(), point0=starts[l], dscale=store.target(o.scale._scale),
+                           dy_cls=dys[(l, 'cls')], dy_reg=dys[(l, 'reg')]))
+    ops.fcos_out_grad_levels(levels, dcls.contiguous(), dreg.contiguous(), dctr.contiguous(), reg, scale,
+                             store.target(head._classification.bias), store.target(head._centerness.bias),
+                             store.target(head._regression.bias))
+    grads = {}
+    for j, o in enumerate(plan.outs):
+        # the padded conv's weight gradient: partial sums into this conv's own buffer, its rows routed to the parameters they
+        # belong to by the one final launch below (a padded buffer never reaches a parameter gradient)
+        wp = _out_pack(o, opk)
+        xin, dy = acts[o.src], dys[(o.level, o.convs[0][0])]
+        floats, nwg, nblk = ops.conv_wgrad_partial_floats(xin, dy, 3, 1)
+        part = sc.buf(('wg', j), floats)
+        ops.conv_wgrad_partials(xin, dy, 3, 1, part)
+        fin.add_wgrad(part, nwg, nblk, xin.size(3), dy.size(3), 9, inv, [(store.target(cv.weight), lo, hi) for cv, lo, hi in out_row_ranges(o)])
+        c = xin.size(3)
+        # both towers' chains end in the same neck output: the second data gradient takes the first as its residual
+        grads[o.src] = ops.conv2d_nhwc(dy, wp[3], zeros(c), wp[0].size(0), c, 3, 1, False, residual=grads.get(o.src))
+    fin.launch()
+
+    def wgrad(xin, dy, ks, st, targets, producer=None):
+        ops.conv_wgrad(xin, dy, ks, st, inv, out=targets[0][0], accumulate=True)
+
+    for ui in range(len(plan.units) - 1, -1, -1):
+        u = plan.units[ui]
+        dz = grads.pop(u.dst, None)
+        if dz is None:
+            continue
+        for p_ in (u.norm.weight, u.norm.bias, u.conv.weight):
+            store.target(p_)
+        _unit_backward(ui, u, dz, plan.units, (acts, htape), grads, dead, store, packs, zeros, inv, sw, wgrad)
+    pyramid_backward(pp, (acts, tape), {o: grads[o] for o in pp.out_ids if o in grads}, scale=scale, store=store)
+
+
+class DetectorTrainFunction(torch.autograd.Function):
+    """(cls [N,P,C], reg [N,P,4], ctr [N,P,1]) = FCOS.forward(x) in train mode as ONE autograd node: backbone, pyramid neck and
+    FCOSHead forward and backward on the hand-written kernels (detector_forward / detector_backward)."""
+
+    @staticmethod
+    def forward(ctx, plan, x, *params):
+        cls, reg, ctr, sizes, saved = detector_forward(plan, x)
+        ctx.plan, ctx.saved = plan, saved
+        ctx.save_for_backward(reg)
+        DetectorTrainFunction.last_sizes = sizes
+        return cls, reg, ctr
+
+    @staticmethod
+    def backward(ctx, dcls, dreg, dctr):
+        reg, = ctx.saved_tensors
+        n, p = reg.shape[:2]
+        zero = lambda c: torch.zeros((n, p, c), dtype=torch.float32, device=reg.device)         # noqa: E731
+        dcls = zero(ctx.plan.num_classes) if dcls is None else dcls
+        dreg = zero(4) if dreg is None else dreg
+        dctr = zero(1) if dctr is None else dctr
+        detector_backward(ctx.plan, ctx.saved, reg.detach(), dcls, dreg, dctr, loss_scale())
+        ctx.saved = None
+        return (None, None) + (None,) * len(ctx.plan.params)     # gradients were accumulated into .grad directly
+
+
+def detector_train_forward(backbone, neck, head, x):
+    """-> (cls, reg, ctr, [(h, w)] per level)"""
+    check_train_input(backbone, x)
+    plan = head.__dict__.get('_lfd_detector_plan')
+    if plan is None or plan.pyramid is not neck.__dict__.get('_lfd_pyramid_plan') or plan.pyramid.owner is not backbone:
+        plan = build_detector(backbone, neck, head)
+        head.__dict__['_lfd_detector_plan'] = plan
+    cls, reg, ctr = DetectorTrainFunction.apply(plan, x, *plan.params)
+    return cls, reg, ctr, DetectorTrainFunction.last_sizes

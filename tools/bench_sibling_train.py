@@ -1,13 +1,15 @@
 """tools/bench_sibling_train.py -- one training iteration of the pyramid siblings: forward, device targets, fused loss, backward
 (no optimizer) of FCOS_FPN and LFDV2_SFPN at 640x640, batch 32, 2-6 boxes per image (seeded; the shape of
-tools/bench_sibling_loss.py), with the backbone + neck autograd node (LFD_HIP_NECK=1, train_engine.PyramidTrainFunction) and with
-the backbone node + the neck as PyTorch-ROCm modules under autograd (LFD_HIP_NECK=0) where that route exists -- autograd refuses
-LFDV2_SFPN's neck (an in-place op on a tensor ReluBackward saved), which is reported as such.
+tools/bench_sibling_loss.py), on the routes a model has:
+    head_node      (FCOS_FPN) LFD_HIP_HEAD=1: backbone + neck + FCOSHead as one autograd node (train_engine.DetectorTrainFunction)
+    node           LFD_HIP_HEAD=0: the backbone + neck node (train_engine.PyramidTrainFunction), the head under autograd
+    autograd_neck  LFD_HIP_NECK=0: the backbone node, neck and head as PyTorch-ROCm modules under autograd, where that route
+                   exists -- autograd refuses LFDV2_SFPN's neck (an in-place op on a tensor ReluBackward saved), reported as such.
 
     python tools/bench_sibling_train.py [--procs 3] [--iters 10] [--rounds 3] [--warmup 3] [--batch 32] [--size 640]
 
-Protocol: every process warms both routes up, then times `--rounds` x (`--iters` iterations of one route, then of the other) --
-the routes alternate inside one process, so clock and neighbours hit both alike.  An iteration is timed with device events
+Protocol: every process warms the routes up, then times `--rounds` x (`--iters` iterations of one route, then of the next) --
+the routes alternate inside one process, so clock and neighbours hit all alike.  An iteration is timed with device events
 (get_loss ends in a host synchronisation by contract).  A process reports its median per route; the parent starts `--procs` fresh
 processes one after the other and prints, per model, one JSON line with the median [min - max] of the processes' medians."""
 import argparse
@@ -22,6 +24,10 @@ for p in (ROOT, os.path.join(ROOT, 'lfd-a-light-and-fast-detector_amd'), os.path
     sys.path.insert(0, p)
 
 MODELS = ('FCOS_FPN', 'LFDV2_SFPN')
+# route -> the environment that selects it (the head switch only moves a model whose head the detector node admits)
+ROUTES = {'FCOS_FPN': (('head_node', dict(LFD_HIP_NECK='1', LFD_HIP_HEAD='1')), ('node', dict(LFD_HIP_NECK='1', LFD_HIP_HEAD='0')),
+                       ('autograd_neck', dict(LFD_HIP_NECK='0', LFD_HIP_HEAD='0'))),
+          'LFDV2_SFPN': (('node', dict(LFD_HIP_NECK='1', LFD_HIP_HEAD='0')), ('autograd_neck', dict(LFD_HIP_NECK='0', LFD_HIP_HEAD='0')))}
 
 
 def worker(args):
@@ -44,33 +50,32 @@ def worker(args):
             return lo['loss_values']['loss']
 
         routes = {}
-        for sw in ('1', '0'):
-            os.environ['LFD_HIP_NECK'] = sw
+        for route, env in ROUTES[name]:
+            os.environ.update(env)
             try:
                 for _ in range(args.warmup):
                     loss = iteration()
-                routes[sw] = dict(ms=[], loss=loss)
+                routes[route] = dict(ms=[], loss=loss)
             except RuntimeError as e:
                 if 'inplace' not in str(e):
                     raise
-                routes[sw] = None          # autograd refuses this neck
+                routes[route] = None          # autograd refuses this neck
                 model.zero_grad()
         torch.cuda.synchronize()
         for _ in range(args.rounds):
-            for sw in ('1', '0'):
-                if routes[sw] is None:
+            for route, env in ROUTES[name]:
+                if routes[route] is None:
                     continue
-                os.environ['LFD_HIP_NECK'] = sw
+                os.environ.update(env)
                 for _ in range(args.iters):
                     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     a.record()
                     iteration()
                     b.record()
                     b.synchronize()
-                    routes[sw]['ms'].append(a.elapsed_time(b))
-        out[name] = {('node' if sw == '1' else 'autograd_neck'):
-                     (None if r is None else dict(median_ms=statistics.median(r['ms']), min_ms=min(r['ms']), max_ms=max(r['ms']),
-                                                  loss=r['loss'])) for sw, r in routes.items()}
+                    routes[route]['ms'].append(a.elapsed_time(b))
+        out[name] = {route: (None if r is None else dict(median_ms=statistics.median(r['ms']), min_ms=min(r['ms']), max_ms=max(r['ms']),
+                                                         loss=r['loss'])) for route, r in routes.items()}
         del model, x
         torch.cuda.empty_cache()
     print('WORKER ' + json.dumps(out))
@@ -99,7 +104,7 @@ def main():
         runs.append(json.loads([l for l in r.stdout.splitlines() if l.startswith('WORKER ')][-1][7:]))
     for name in MODELS:
         line = dict(model=name, batch=args.batch, size=args.size, procs=args.procs, iters_per_route=args.iters * args.rounds)
-        for route in ('node', 'autograd_neck'):
+        for route, _ in ROUTES[name]:
             rs = [r[name][route] for r in runs]
             if any(v is None for v in rs):
                 line[route] = 'refused by autograd'
@@ -110,6 +115,9 @@ def main():
         if isinstance(line['node'], dict) and isinstance(line['autograd_neck'], dict):
             a, b = line['node'], line['autograd_neck']
             line['medians_separate'] = a['max_ms'] < b['min_ms'] or b['max_ms'] < a['min_ms']
+        if isinstance(line.get('head_node'), dict) and isinstance(line['node'], dict):
+            # the head node stays default-on only if its slowest process beats the fastest process of the LFD_HIP_HEAD=0 route
+            line['head_node_ranges_separate'] = line['head_node']['max_ms'] < line['node']['min_ms']
         print(json.dumps(line))
 
 
