@@ -1107,6 +1107,61 @@ LFD_API int lfd_fcos_out_grad_levels_f32(const lfd_fcos_out_level_t* levels, int
                                          const float* dctr, const float* reg, float loss_scale, float* dbias_cls, float* dbias_ctr,
                                          float* dbias_reg, void* workspace, size_t workspace_bytes, lfd_stream_t stream);
 
+/* The glue around LFDHead's output convs with fp32 logits in a training iteration (csrc/lfd_out.hip), all pyramid levels and
+ * both convs of a level in one launch.  Replaces, forward, lfd_head.py:157-185 (the classification conv's output, the regression
+ * conv's output through the level's Scale) and lfd.py:526-542 (permute + reshape + concatenation of the levels along the point
+ * axis), and, backward, what autograd runs for them.  The detector node runs a level's two 1x1 convs as ONE conv (both read the
+ * same activation) or TWO (separate towers) padded to `rows` (64 | 128) output rows with fp32 outputs
+ * (lfd_conv2d_nhwc_f16_acc32): `raw` [n, hw, rows].  A segment is the row range [row0, row0 + channels) of one of the
+ * reference's convs inside a padded conv, kind 0 = classification (channels == cls_channels), 1 = regression (channels == 4); a
+ * level has exactly one of each.
+ *   lfd_lfdhead_out_pack_levels_f32: cls[img, point0 + p, j] = raw[img, p, row0 + j] (a copy) and reg[img, point0 + p, k] =
+ *     raw[img, p, row0 + k] * *scale (one fp32 multiply; a copy when scale is null).  cls [n, points_total, cls_channels], reg
+ *     [n, points_total, 4] fp32; every element of a level's point range is written.
+ *   lfd_lfdhead_out_grad_levels_f32: from dcls / dreg (layouts of cls / reg) writes every conv's dy [n, hw, rows] fp16 =
+ *     dcls * loss_scale and dreg * *scale * loss_scale (the product formed in fp64, rounded to fp32 once, then to fp16 once; rows
+ *     outside the segments ZERO) and ACCUMULATES dbias[j] += sum dcls | sum dreg * *scale -- the sums of consecutive levels whose
+ *     segments name the same dbias (a head shared by the levels) reach it as one rounding of their fp64 total; a head with its own
+ *     convs per level names one target per level -- and, per level with a Scale, *dscale += sum_k sum dreg * raw, through
+ *     per-block fp32 partials in `workspace` (lfd_lfdhead_out_grad_workspace_bytes; lfd_train_workspace_bytes() covers it) and
+ *     one fixed-order fp64 final launch: no atomics, equal bits run after run.  A dbias element belongs to one (conv position, row)
+ *     of the levels that name it.
+ * `levels`: host array.  raw, dy, reg, dreg, workspace: 16-byte aligned (cls / dcls move as float4 where they are).
+ * LFD_ERR_INVALID_ARGUMENT: a null / misaligned pointer (dscale must be given iff scale is), rows not 64 | 128, nconvs / nsegs
+ * outside 1..2, a segment past `rows`, overlapping segments, channels that are not cls_channels / 4, a level without exactly one
+ * segment of each kind, nlevels > LFD_MAX_LEVELS, a point range outside points_total; LFD_ERR_UNSUPPORTED: n * hw * rows >= 2^31
+ * (32-bit indices); LFD_ERR_WORKSPACE_TOO_SMALL.  Nothing is launched when a status code is returned. */
+typedef struct lfd_lfdhead_out_seg {
+  float* dbias;          /* grad: [channels] fp32, += (pack: unused) */
+  int32_t row0;          /* first row of the segment inside the padded conv */
+  int32_t channels;
+  int32_t kind;          /* 0: classification, 1: regression */
+  int32_t reserved;
+} lfd_lfdhead_out_seg_t;
+typedef struct lfd_lfdhead_out_conv {
+  const float* raw;      /* [n, hw, rows] fp32: the padded conv's output (grad: read, and required, only where the conv holds
+                          * the regression rows of a level with a Scale) */
+  void* dy;              /* grad: [n, hw, rows] fp16 (pack: unused) */
+  int32_t nsegs;         /* 1 | 2 */
+  int32_t reserved;
+  lfd_lfdhead_out_seg_t segs[2];
+} lfd_lfdhead_out_conv_t;
+typedef struct lfd_lfdhead_out_level {
+  const float* scale;    /* device scalar: the level's Scale (null: the head has none) */
+  float* dscale;         /* grad: device scalar, += (null iff scale is) */
+  int32_t hw;            /* pixels per image of the level */
+  int32_t nconvs;        /* 1 | 2 */
+  int64_t point0;        /* first point of the level inside an image of the concatenated tensors */
+  lfd_lfdhead_out_conv_t convs[2];
+} lfd_lfdhead_out_level_t;
+LFD_API size_t lfd_lfdhead_out_grad_workspace_bytes(int32_t nlevels, int32_t rows);
+LFD_API int lfd_lfdhead_out_pack_levels_f32(const lfd_lfdhead_out_level_t* levels, int32_t nlevels, int32_t n, int32_t rows,
+                                            int32_t cls_channels, int64_t points_total, float* cls, float* reg,
+                                            lfd_stream_t stream);
+LFD_API int lfd_lfdhead_out_grad_levels_f32(const lfd_lfdhead_out_level_t* levels, int32_t nlevels, int32_t n, int32_t rows,
+                                            int32_t cls_channels, int64_t points_total, const float* dcls, const float* dreg,
+                                            float loss_scale, void* workspace, size_t workspace_bytes, lfd_stream_t stream);
+
 /* first stem conv (3 -> channels, 3x3 stride 2 pad 1, lfd_resnet.py:358,:378) on the NCHW fp32 image batch:
  * forward -> y NHWC fp16 (pre-norm), and its weight gradient (OIHW fp32); channels in {32, 64} */
 LFD_API int lfd_stem_conv0_train_fwd(const float* x_nchw, int32_t n, int32_t h, int32_t w, int32_t channels,

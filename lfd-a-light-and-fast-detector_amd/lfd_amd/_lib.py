@@ -57,6 +57,22 @@ class FcosOutLevel(C.Structure):
                 ('dy_cls', C.c_void_p), ('dy_reg', C.c_void_p), ('hw', C.c_int32), ('reserved', C.c_int32), ('point0', C.c_int64)]
 
 
+class LfdHeadOutSeg(C.Structure):
+    """lfd_lfdhead_out_seg_t"""
+    _fields_ = [('dbias', C.c_void_p), ('row0', C.c_int32), ('channels', C.c_int32), ('kind', C.c_int32), ('reserved', C.c_int32)]
+
+
+class LfdHeadOutConv(C.Structure):
+    """lfd_lfdhead_out_conv_t"""
+    _fields_ = [('raw', C.c_void_p), ('dy', C.c_void_p), ('nsegs', C.c_int32), ('reserved', C.c_int32), ('segs', LfdHeadOutSeg * 2)]
+
+
+class LfdHeadOutLevel(C.Structure):
+    """lfd_lfdhead_out_level_t"""
+    _fields_ = [('scale', C.c_void_p), ('dscale', C.c_void_p), ('hw', C.c_int32), ('nconvs', C.c_int32), ('point0', C.c_int64),
+                ('convs', LfdHeadOutConv * 2)]
+
+
 class BnBwdLevel(C.Structure):
     """lfd_bn_bwd_level_t"""
     _fields_ = [('y', C.c_void_p), ('dy', C.c_void_p), ('stats', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p),
@@ -372,6 +388,10 @@ _SIGNATURES = {
     'lfd_fcos_out_pack_levels_f32': (C.c_int, [C.POINTER(FcosOutLevel), _I32, _I32, _I32, _I32, _I64, _P, _P, _P, _P]),
     'lfd_fcos_out_grad_levels_f32': (C.c_int, [C.POINTER(FcosOutLevel), _I32, _I32, _I32, _I32, _I64, _P, _P, _P, _P, _F, _P, _P, _P,
                                                _P, _SZ, _P]),
+    # the glue around LFDHead's fp32-logit output convs, all levels and both convs in one launch (csrc/lfd_out.hip)
+    'lfd_lfdhead_out_grad_workspace_bytes': (_SZ, [_I32, _I32]),
+    'lfd_lfdhead_out_pack_levels_f32': (C.c_int, [C.POINTER(LfdHeadOutLevel), _I32, _I32, _I32, _I32, _I64, _P, _P, _P]),
+    'lfd_lfdhead_out_grad_levels_f32': (C.c_int, [C.POINTER(LfdHeadOutLevel), _I32, _I32, _I32, _I32, _I64, _P, _P, _F, _P, _SZ, _P]),
     'lfd_stem_conv0_train_fwd_bn_stats': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _F, _F, _P, _P, _P, _SZ, _P, _P]),
     'lfd_stem_conv0_wgrad': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _F, _I32, _P, _SZ, _P, _P]),
     'lfd_stem_conv0_bn_bwd_wgrad': (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _I32, _P, _SZ, _P, _P, _P, _P]),

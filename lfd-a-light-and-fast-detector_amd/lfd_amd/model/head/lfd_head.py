@@ -5,6 +5,10 @@ then cls conv1x1 -> C (C+1 for CrossEntropyLoss :138-141) and reg conv1x1 -> 4, 
 per-level Scale on reg for IoU-type losses (:64-65,179-180); weights optionally shared
 across levels by aliasing head0's Sequentials (:67-82).  Child names, creation order and the
 N(0, 0.01) init (:151-162) follow the reference so checkpoints and seeds line up.
+
+Execution in training mode: behind a SimpleNeck inside the whole-network node (train_engine.network_supported); a GroupNorm
+head behind an FPN / SimpleFPN inside the detector node (train_engine.lfd_head_supported / LFDDetectorTrainFunction), which
+reads these modules' parameters; every other head: its children as PyTorch-ROCm modules under autograd (LFD._forward_train).
 """
 import torch
 import torch.nn as nn

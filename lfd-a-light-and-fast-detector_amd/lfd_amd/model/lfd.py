@@ -254,7 +254,9 @@ class LFD(nn.Module):
         configurations the WHOLE network -- backbone, neck, head towers, output convs -- runs forward and backward on the
         hand-written kernels as one autograd node (train_engine.NetworkTrainFunction); a supported backbone under an
         unsupported neck / head runs as its own node with PyTorch-ROCm modules behind it -- together with an FPN / SimpleFPN
-        neck that train_engine.pyramid_supported admits (PyramidTrainFunction; LFD_HIP_NECK=0: the backbone alone).  LFD_HIP_TRAIN=0 or an
+        neck that train_engine.pyramid_supported admits (PyramidTrainFunction; LFD_HIP_NECK=0: the backbone alone), and with a
+        GroupNorm LFDHead behind that neck that train_engine.lfd_head_supported admits as ONE node again
+        (LFDDetectorTrainFunction; LFD_HIP_HEAD=0: the pyramid node with the head under autograd).  LFD_HIP_TRAIN=0 or an
         unsupported backbone: everything through PyTorch-ROCm autograd (same parameters, same semantics)."""
         neck, head = self._neck, self._head
         hip = x.is_cuda and os.environ.get('LFD_HIP_TRAIN', '1') != '0'
@@ -263,7 +265,14 @@ class LFD(nn.Module):
             for i, sz in enumerate(sizes):
                 self._head_indexes_to_feature_map_sizes[i] = sz
             return cls, reg
-        if hip and train_engine.switches().hip_neck and train_engine.pyramid_supported(self._backbone, neck):
+        sw = train_engine.switches()
+        if hip and sw.hip_neck and sw.hip_head and train_engine.lfd_head_supported(self._backbone, neck, head):
+            # FPN / SimpleFPN + a GroupNorm LFDHead: backbone + neck + head as one node (LFD_HIP_HEAD=0: the route below)
+            cls, reg, sizes = train_engine.lfd_detector_train_forward(self._backbone, neck, head, x)
+            for i, sz in enumerate(sizes):
+                self._head_indexes_to_feature_map_sizes[i] = sz
+            return cls, reg
+        if hip and sw.hip_neck and train_engine.pyramid_supported(self._backbone, neck):
             # FPN / SimpleFPN: backbone + neck as one node (the taps stay NHWC fp16, the neck runs on the hand-written kernels)
             feats = train_engine.backbone_neck_train_forward(self._backbone, neck, x)
         else:

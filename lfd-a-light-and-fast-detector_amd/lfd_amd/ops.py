@@ -1699,6 +1699,77 @@ def fcos_out_grad_levels(levels, dcls, dreg, dctr, reg, loss_scale, dbias_cls, d
                                                  ws.numel(), stream_ptr()), 'lfd_fcos_out_grad_levels_f32')
 
 
+def _lfdhead_out_levels(levels, n, backward, what):
+    """levels: [dict(point0, scale (fp32 scalar tensor or None), convs=[dict(raw [n, h, w, rows] fp32, segs=[dict(kind 'cls' |
+    'reg', row0, channels (+ dbias))] (+ dy [n, h, w, rows] fp16))] (+ dscale))] -> (lfd_lfdhead_out_level_t array, rows)"""
+    arr = (_lib.LfdHeadOutLevel * len(levels))()
+    shaped = 'dy' if backward else 'raw'          # (the backward needs raw only where a Scale gradient reads it)
+    rows = levels[0]['convs'][0][shaped].size(-1)
+    for a, lv in zip(arr, levels):
+        convs = lv['convs']
+        if not 1 <= len(convs) <= 2:
+            raise RuntimeError('%s: one or two output convs per level' % what)
+        raw0 = convs[0][shaped]
+        if raw0.dim() != 4:
+            raise RuntimeError('%s: [n, h, w, rows] tensors expected' % what)
+        a.hw, a.nconvs, a.point0 = raw0.size(1) * raw0.size(2), len(convs), int(lv['point0'])
+        scale = lv.get('scale')
+        if scale is not None:
+            a.scale = _f32c(scale, what).data_ptr()
+            if backward:
+                a.dscale = _f32c(lv['dscale'], what).data_ptr()
+        for c, cv in zip(a.convs, convs):
+            raw = cv.get('raw')
+            shape = (n,) + tuple(raw0.shape[1:3]) + (rows,)
+            if raw is not None:
+                if tuple(_f32c(raw, what).shape) != shape:
+                    raise RuntimeError('%s: raw must be [n, h, w, %d] with one (h, w) per level' % (what, rows))
+                c.raw = raw.data_ptr()
+            c.nsegs = len(cv['segs'])
+            if not 1 <= len(cv['segs']) <= 2:
+                raise RuntimeError('%s: one or two segments per conv' % what)
+            if backward:
+                dy = cv['dy']
+                if dy.dtype != torch.float16 or not dy.is_contiguous() or tuple(dy.shape) != shape:
+                    raise RuntimeError('%s: dy must be contiguous fp16 %s' % (what, shape))
+                c.dy = dy.data_ptr()
+            for s, sg in zip(c.segs, cv['segs']):
+                s.row0, s.channels, s.kind = int(sg['row0']), int(sg['channels']), {'cls': 0, 'reg': 1}[sg['kind']]
+                if backward:
+                    if _f32c(sg['dbias'], what).numel() != s.channels:
+                        raise RuntimeError('%s: dbias of %d elements expected' % (what, s.channels))
+                    s.dbias = sg['dbias'].data_ptr()
+    return arr, rows
+
+
+def lfdhead_out_pack_levels(levels, cls, reg):
+    """LFDHead's outputs of ALL levels in one launch (lfd_lfdhead_out_pack_levels_f32): from the levels' padded fp32 conv outputs
+    into the level-concatenated cls [n, P, C'] (a copy of the classification rows) and reg [n, P, 4] = raw * scale_i (a copy
+    without a Scale).  levels: see _lfdhead_out_levels."""
+    require_cuda(cls, 'lfdhead_out_pack_levels')
+    what = 'lfdhead_out_pack_levels'
+    n, p, c = cls.shape
+    _f32c(cls, what), _f32c(reg, what, (n, p, 4))
+    arr, rows = _lfdhead_out_levels(levels, n, False, what)
+    with torch.cuda.device(cls.device):
+        check(lib().lfd_lfdhead_out_pack_levels_f32(arr, len(levels), n, rows, c, p, ptr(cls), ptr(reg), stream_ptr()),
+              'lfd_lfdhead_out_pack_levels_f32')
+
+
+def lfdhead_out_grad_levels(levels, dcls, dreg, loss_scale):
+    """the backward of lfdhead_out_pack_levels in one launch + one final (lfd_lfdhead_out_grad_levels_f32): writes every conv's dy
+    (fp16, times loss_scale, padded rows zero) and accumulates the segments' dbias and the levels' dscale in place."""
+    require_cuda(dcls, 'lfdhead_out_grad_levels')
+    what = 'lfdhead_out_grad_levels'
+    n, p, c = dcls.shape
+    _f32c(dcls, what), _f32c(dreg, what, (n, p, 4))
+    arr, rows = _lfdhead_out_levels(levels, n, True, what)
+    ws = train_workspace(dcls.device)
+    with torch.cuda.device(dcls.device):
+        check(lib().lfd_lfdhead_out_grad_levels_f32(arr, len(levels), n, rows, c, p, ptr(dcls), ptr(dreg), float(loss_scale), ptr(ws),
+                                                    ws.numel(), stream_ptr()), 'lfd_lfdhead_out_grad_levels_f32')
+
+
 def _stem_conv0_cin(x_nchw, weight, what):
     """input channels of a first-stem-conv call: 3 (RGB, csrc/train.hip) or 1 (gray, csrc/stem_gray_train.hip); anything else,
     or a weight whose in_channels disagree with the batch, raises before any launch"""

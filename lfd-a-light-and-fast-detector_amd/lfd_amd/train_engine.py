@@ -54,8 +54,8 @@ def switches():
     environment at every call: the public entries call this once per pass and hand the record down.  `.hip_neck`
     (LFD_HIP_NECK, default on): FPN / SimpleFPN necks run inside the backbone's autograd node (PyramidTrainFunction); '0'
     restores the backbone node with the neck as PyTorch-ROCm modules under autograd.  `.hip_head` (LFD_HIP_HEAD, default on): an
-    FCOSHead behind such a neck runs inside the same node (DetectorTrainFunction); '0' keeps the pyramid node with the head
-    under autograd.  The head node sits on the pyramid node: LFD_HIP_NECK=0 turns both off."""
+    FCOSHead or an LFDHead behind such a neck runs inside the same node (DetectorTrainFunction / LFDDetectorTrainFunction); '0'
+    keeps the pyramid node with the head under autograd.  The head node sits on the pyramid node: LFD_HIP_NECK=0 turns both off."""
     sw = _Switches(
         conv_bn_stats=os.environ.get('LFD_CONV_BN_STATS', '1') == '1',           # conv, then a statistics pass over y
         dgrad_s2=os.environ.get('LFD_DGRAD_S2', '1') == '1',                     # zero_insert2 + stride-1 conv (3x3 stride-2 dgrad)
@@ -817,23 +817,24 @@ def _sched(plan_owner, dev):
     return sc
 
 
-def _out_packs(sc, outs):
+def _out_packs(sc, outs, rows=None):
     """{ids of a level's output convs: (padded weight [rows, C, k, k], padded bias [rows], forward pack, data-gradient pack), rows
     64 or 128; k = 1 for LFDHead, 3 for FCOSHead}: the
     rows of the convs are gathered into persistent zero-padded buffers by ONE launch (lfd_rows_sum_batched_f32 with one source
-    row = a batched copy), then packed; shared heads: once for all levels"""
+    row = a batched copy), then packed; shared heads: once for all levels.  rows: one row count for every conv (the LFD detector
+    node, whose glue takes both convs of a level in one launch) instead of each conv's own"""
     cache, jobs = {}, []
     for o in outs:
         key = tuple(id(cv) for _, cv in o.convs)
         if key in cache:
             continue
         c = o.convs[0][1].in_channels
-        rows = -(-sum(cv.out_channels for _, cv in o.convs) // 64) * 64
+        nrows = rows or -(-sum(cv.out_channels for _, cv in o.convs) // 64) * 64
         wp = sc.bufs.get(('outw', key))
         if wp is None:
-            wp = torch.zeros((rows,) + tuple(o.convs[0][1].weight.shape[1:]), dtype=torch.float32, device=sc.dev)
+            wp = torch.zeros((nrows,) + tuple(o.convs[0][1].weight.shape[1:]), dtype=torch.float32, device=sc.dev)
             sc.bufs[('outw', key)] = wp
-            sc.bufs[('outb', key)] = torch.zeros(rows, dtype=torch.float32, device=sc.dev)
+            sc.bufs[('outb', key)] = torch.zeros(nrows, dtype=torch.float32, device=sc.dev)
         bp = sc.bufs[('outb', key)]
         r0 = 0
         for _, cv in o.convs:
@@ -1572,8 +1573,8 @@ def fcos_head_supported(backbone, neck, head):
     channels -> ReLU, 64 or 128 input and head channels, every parameter taking a gradient, and
     num_classes + 1 <= FCOS_OUT_ROWS (classification and centerness share one padded conv).  NOT admitted -- these keep the
     pyramid node with the head under PyTorch-ROCm autograd: norm_cfg=None, BatchNorm towers (a BatchNorm shared by the levels
-    updates its running statistics level after level: its own piece of work), num_layers == 0, more classes, and
-    LFDHead / LFDHeadV1 behind an FPN."""
+    updates its running statistics level after level: its own piece of work), num_layers == 0 and more classes.  (An LFDHead
+    behind such a neck has its own node: lfd_head_supported; LFDHeadV1 has none.)"""
     if type(head).__name__ != 'FCOSHead' or not head.training:
         return False
     if not pyramid_supported(backbone, neck) or len(head._scales) != neck._num_outputs:
@@ -1667,6 +1668,43 @@ def detector_forward(plan, x):
     return cls, reg, ctr, sizes, ((acts, tape), htape, opk, raw_reg, starts)
 
 
+def _head_tail_backward(plan, saved, htape, opk, dys, ks, store, sc, packs, zeros, dead, scale, sw):
+    """what the backward of both detector nodes does behind the output-conv glue: from dys[j], the fp16 output gradient of
+    plan.outs[j]'s padded ks x ks conv, that conv's weight gradient (partial sums into its own buffer, its rows routed to the
+    parameters they belong to by ONE final launch: a padded buffer never reaches a parameter gradient) and data gradient (chains
+    ending in the same activation take the earlier gradient as the conv kernel's residual), the head's units last to first, then
+    pyramid_backward with the gradients collected at the neck's outputs"""
+    pp = plan.pyramid
+    acts, tape = saved
+    inv = 1.0 / scale
+    fin = sc.finals
+    grads = {}
+    for j, o in enumerate(plan.outs):
+        wp = _out_pack(o, opk)
+        xin, dy = acts[o.src], dys[j]
+        floats, nwg, nblk = ops.conv_wgrad_partial_floats(xin, dy, ks, 1)
+        part = sc.buf(('wg', j), floats)
+        ops.conv_wgrad_partials(xin, dy, ks, 1, part)
+        fin.add_wgrad(part, nwg, nblk, xin.size(3), dy.size(3), ks * ks, inv,
+                      [(store.target(cv.weight), lo, hi) for cv, lo, hi in out_row_ranges(o)])
+        c = xin.size(3)
+        grads[o.src] = ops.conv2d_nhwc(dy, wp[3], zeros(c), wp[0].size(0), c, ks, 1, False, residual=grads.get(o.src))
+    fin.launch()
+
+    def wgrad(xin, dy, ks_, st, targets, producer=None):
+        ops.conv_wgrad(xin, dy, ks_, st, inv, out=targets[0][0], accumulate=True)
+
+    for ui in range(len(plan.units) - 1, -1, -1):
+        u = plan.units[ui]
+        dz = grads.pop(u.dst, None)
+        if dz is None:
+            continue
+        for p_ in (u.norm.weight, u.norm.bias, u.conv.weight):
+            store.target(p_)
+        _unit_backward(ui, u, dz, plan.units, (acts, htape), grads, dead, store, packs, zeros, inv, sw, wgrad)
+    pyramid_backward(pp, (acts, tape), {o: grads[o] for o in pp.out_ids if o in grads}, scale=scale, store=store)
+
+
 def detector_backward(plan, saved, reg, dcls, dreg, dctr, scale):
     """the backward of detector_forward: output-conv glue (+ the bias / Scale finals), the output convs' weight and data
     gradients, the tower units last to first, then pyramid_backward with the gradients collected at the neck's outputs.
@@ -1675,11 +1713,9 @@ def detector_backward(plan, saved, reg, dcls, dreg, dctr, scale):
     pp, head = plan.pyramid, plan.head
     (acts, tape), htape, opk, raw_reg, starts = saved
     dev = dcls.device
-    inv = 1.0 / scale
     store = _GradStore(in_place=True)
     sc = _sched(head, dev)
-    fin = sc.finals
-    fin.reset()
+    sc.finals.reset()
     zeros = _Zeros(dev)
     packs = _Packs(plan.units, True)
     dead = dead_activations(pp.units)
@@ -1694,33 +1730,8 @@ def detector_backward(plan, saved, reg, dcls, dreg, dctr, scale):
     ops.fcos_out_grad_levels(levels, dcls.contiguous(), dreg.contiguous(), dctr.contiguous(), reg, scale,
                              store.target(head._classification.bias), store.target(head._centerness.bias),
                              store.target(head._regression.bias))
-    grads = {}
-    for j, o in enumerate(plan.outs):
-        # the padded conv's weight gradient: partial sums into this conv's own buffer, its rows routed to the parameters they
-        # belong to by the one final launch below (a padded buffer never reaches a parameter gradient)
-        wp = _out_pack(o, opk)
-        xin, dy = acts[o.src], dys[(o.level, o.convs[0][0])]
-        floats, nwg, nblk = ops.conv_wgrad_partial_floats(xin, dy, 3, 1)
-        part = sc.buf(('wg', j), floats)
-        ops.conv_wgrad_partials(xin, dy, 3, 1, part)
-        fin.add_wgrad(part, nwg, nblk, xin.size(3), dy.size(3), 9, inv, [(store.target(cv.weight), lo, hi) for cv, lo, hi in out_row_ranges(o)])
-        c = xin.size(3)
-        # both towers' chains end in the same neck output: the second data gradient takes the first as its residual
-        grads[o.src] = ops.conv2d_nhwc(dy, wp[3], zeros(c), wp[0].size(0), c, 3, 1, False, residual=grads.get(o.src))
-    fin.launch()
-
-    def wgrad(xin, dy, ks, st, targets, producer=None):
-        ops.conv_wgrad(xin, dy, ks, st, inv, out=targets[0][0], accumulate=True)
-
-    for ui in range(len(plan.units) - 1, -1, -1):
-        u = plan.units[ui]
-        dz = grads.pop(u.dst, None)
-        if dz is None:
-            continue
-        for p_ in (u.norm.weight, u.norm.bias, u.conv.weight):
-            store.target(p_)
-        _unit_backward(ui, u, dz, plan.units, (acts, htape), grads, dead, store, packs, zeros, inv, sw, wgrad)
-    pyramid_backward(pp, (acts, tape), {o: grads[o] for o in pp.out_ids if o in grads}, scale=scale, store=store)
+    _head_tail_backward(plan, (acts, tape), htape, opk, [dys[(o.level, o.convs[0][0])] for o in plan.outs], 3, store, sc, packs,
+                        zeros, dead, scale, sw)
 
 
 class DetectorTrainFunction(torch.autograd.Function):
@@ -1757,3 +1768,201 @@ def detector_train_forward(backbone, neck, head, x):
         head.__dict__['_lfd_detector_plan'] = plan
     cls, reg, ctr = DetectorTrainFunction.apply(plan, x, *plan.params)
     return cls, reg, ctr, DetectorTrainFunction.last_sizes
+
+
+# ---------------------------------------------------------------------------------------------- backbone + pyramid neck + LFDHead
+# LFDHead (lfd/model/head/lfd_head.py:30-185) behind the pyramid node, in the SAME autograd node, level by level: the merge path's
+# units, then the classification and regression towers' units (1x1 or 3x3 conv -> GroupNorm -> ReLU through _unit_forward /
+# _unit_backward; modules shared by the levels are packed once and their gradients accumulate over the levels), then the level's
+# output convs as build_network forms them -- ONE 1x1 conv with the rows of both when they read the same activation, else two --
+# padded to 64 or 128 rows with fp32 outputs (ops.conv2d_nhwc_f32out), and csrc/lfd_out.hip on both sides of them.  The node
+# returns what LFD.forward returns in train mode: (cls [N,P,C'], reg [N,P,4]) fp32, level-concatenated; reg = raw * Scale_i (the
+# loss applies `exp` where distance_to_bbox_mode asks for it).  A 3x3 head runs here although the level-concatenated schedule
+# of network_forward cannot take it: every level keeps its own map.
+def lfd_head_supported(backbone, neck, head):
+    """backbone + neck + head as one node (LFDDetectorTrainFunction): pyramid_supported(backbone, neck) and a training-mode LFDHead
+    with one head per neck output, 64 or 128 input (= the neck's output) and head channels, 1x1 or 3x3 tower convs, any number of
+    tower layers (0: the output convs read the neck's outputs), ReLU, affine GroupNorm in groups of 8 channels, every parameter
+    taking a gradient, a Scale per level exactly when the regression loss is of the IoU family, shared or per-level towers, merged
+    or separate, and output rows that fit the padded conv (_out_weight): num_cls_channels + 4 <= 128 where both convs read the
+    same activation, num_cls_channels <= 128 with separate towers.  NOT admitted -- these keep the pyramid node with the head
+    under PyTorch-ROCm autograd: LFDHeadV1, BatchNorm towers, norm_cfg=None, a frozen head parameter, other GroupNorm group
+    sizes, an eval-mode head."""
+    if type(head).__name__ != 'LFDHead' or not head.training:
+        return False
+    if not pyramid_supported(backbone, neck) or head._num_heads != neck._num_outputs:
+        return False
+    if head._num_input_channels != neck._num_output_channels or head._num_input_channels not in (64, 128):
+        return False
+    if head._num_head_channels not in (64, 128) or head._conv_kernel_size not in (1, 3) or head._num_conv_layers < 0:
+        return False
+    if head._num_conv_layers == 0 and head._num_head_channels != head._num_input_channels:
+        return False          # (the output convs are built on num_head_channels: lfd_head.py:107-111)
+    if head._activation_cfg.get('type') != 'ReLU':
+        return False
+    cfg = head._norm_cfg
+    if cfg is None or cfg.get('type') != 'GroupNorm' or head._num_head_channels != 8 * cfg.get('num_groups', 0):
+        return False
+    if any(isinstance(m, nn.GroupNorm) and not m.affine for m in head.modules()):
+        return False
+    if not all(p.requires_grad for p in head.parameters()):
+        return False
+    union = head._regression_loss_type in ('IoULoss', 'GIoULoss', 'DIoULoss', 'CIoULoss')
+    if hasattr(head, '_scales') != union or (union and len(head._scales) != head._num_heads):
+        return False
+    one_conv = head._merge_path_flag or head._num_conv_layers == 0
+    return head.num_cls_channels + (4 if one_conv else 0) <= 128
+
+
+class _LFDDetectorPlan(object):
+    """pyramid: the _PyramidPlan; units: the head's units of all levels (their own list: tape indices are positions in it,
+    activation indices go on from the pyramid's); outs: per level one _Out record (cls + reg on the same activation) or two;
+    rows: the row count every output conv is padded to"""
+    __slots__ = ('pyramid', 'units', 'outs', 'rows', 'cls_channels', 'params', 'head')
+
+
+def build_lfd_detector(backbone, neck, head):
+    """-> _LFDDetectorPlan: the pyramid plan, then per level, in LFD._forward_train's order (lfd.py:526-542), the merge path's
+    units, the two towers' units and the output records exactly as build_network forms them"""
+    pp = _pyramid_plan(backbone, neck)
+    b = _Builder()
+    b.n_act = pp.n_act
+    d = _LFDDetectorPlan()
+    d.pyramid, d.outs, d.cls_channels, d.head = pp, [], head.num_cls_channels, head
+
+    def tower(path, cur):
+        mods = list(path)
+        n3 = len(mods) - (1 if mods and isinstance(mods[-1], nn.Conv2d) else 0)
+        for i in range(0, n3, 3):          # (conv, norm, ReLU) triples; the path's last module is its output conv
+            cur = b.add(mods[i], mods[i + 1], True, cur)
+        return cur
+
+    for i, src in enumerate(pp.out_ids):
+        b.level = i
+        cur = tower(getattr(head, 'head%d_merge_path' % i), src)
+        cpath, rpath = getattr(head, 'head%d_classification_path' % i), getattr(head, 'head%d_regression_path' % i)
+        csrc, rsrc = tower(cpath, cur), tower(rpath, cur)
+        scale = head._scales[i] if hasattr(head, '_scales') else None
+        if csrc == rsrc:
+            o = _Out()
+            o.level, o.convs, o.src, o.scale = i, [('cls', cpath[-1]), ('reg', rpath[-1])], csrc, scale
+            d.outs.append(o)
+        else:
+            for kind, conv, s in (('cls', cpath[-1], csrc), ('reg', rpath[-1], rsrc)):
+                o = _Out()
+                o.level, o.convs, o.src, o.scale = i, [(kind, conv)], s, scale
+                d.outs.append(o)
+    d.units = b.units
+    d.rows = max(-(-sum(cv.out_channels for _, cv in o.convs) // 64) * 64 for o in d.outs)
+    ps = list(pp.params)
+    for u in d.units:
+        ps += [u.conv.weight, u.norm.weight, u.norm.bias]
+    for o in d.outs:
+        for _, conv in o.convs:
+            ps += [conv.weight, conv.bias]
+        if o.scale is not None:
+            ps.append(o.scale._scale)
+    d.params = _unique(ps)
+    return d
+
+
+def _lfd_out_levels(plan, nlev, starts, raws, dys=None, store=None):
+    """the level records of ops.lfdhead_out_pack_levels (raws: {index into plan.outs: the conv's fp32 output}) and, with dys (per
+    plan.outs record) and the gradient store, of ops.lfdhead_out_grad_levels"""
+    levels = [dict(point0=starts[l], convs=[], scale=None) for l in range(nlev)]
+    for j, o in enumerate(plan.outs):
+        lv = levels[o.level]
+        cv = dict(raw=raws.get(j), segs=[dict(kind=sg['kind'], row0=sg['row0'], channels=sg['channels']) for sg in _out_segs(o)])
+        if dys is not None:
+            cv['dy'] = dys[j]
+            for d, sg in zip(cv['segs'], _out_segs(o)):
+                d['dbias'] = store.target(sg['conv'].bias)
+        lv['convs'].append(cv)
+        if o.scale is not None and lv['scale'] is None:
+            lv['scale'] = o.scale._scale.detach()
+            if dys is not None:
+                lv['dscale'] = store.target(o.scale._scale)
+    return levels
+
+
+def lfd_detector_forward(plan, x):
+    """-> (cls [N,P,C'], reg [N,P,4] fp32, [(h, w)] per level, saved)"""
+    sw = switches()
+    pp = plan.pyramid
+    feats, (acts, tape) = pyramid_forward(pp, x)
+    dev = x.device
+    n = x.size(0)
+    zeros = _Zeros(dev)
+    packs = _Packs(plan.units, False)
+    htape = [_unit_forward(ui, u, acts, packs, zeros, sw) for ui, u in enumerate(plan.units)]
+    sizes = [tuple(f.shape[1:3]) for f in feats]
+    starts, p = _level_starts(sizes)
+    opk = _out_packs(_sched(plan.head, dev), plan.outs, plan.rows)
+    raws = {}
+    for j, o in enumerate(plan.outs):
+        wp, bp, wpk, _ = _out_pack(o, opk)
+        xin = acts[o.src]
+        raws[j] = ops.conv2d_nhwc_f32out(xin, wpk, bp, xin.size(3), wp.size(0), 1, 1)
+    cls = torch.empty((n, p, plan.cls_channels), dtype=torch.float32, device=dev)
+    reg = torch.empty((n, p, 4), dtype=torch.float32, device=dev)
+    ops.lfdhead_out_pack_levels(_lfd_out_levels(plan, len(sizes), starts, raws), cls, reg)
+    # the backward reads a raw output for the Scale gradient alone: the conv that holds a Scale'd level's regression rows
+    keep = {j: raws[j] for j, o in enumerate(plan.outs) if o.scale is not None and any(k == 'reg' for k, _ in o.convs)}
+    return cls, reg, sizes, ((acts, tape), htape, opk, keep, starts, sizes)
+
+
+def lfd_detector_backward(plan, saved, dcls, dreg, scale):
+    """the backward of lfd_detector_forward: output-conv glue (+ the bias / Scale finals), the output convs' weight and data
+    gradients (chains ending in the same activation take the earlier gradient as residual), the units last to first, then
+    pyramid_backward with the gradients collected at the neck's outputs.  Parameter gradients accumulate into `.grad` (created
+    zeroed when missing)."""
+    sw = switches()
+    pp, head = plan.pyramid, plan.head
+    (acts, tape), htape, opk, raws, starts, sizes = saved
+    dev = dcls.device
+    n = dcls.size(0)
+    store = _GradStore(in_place=True)
+    sc = _sched(head, dev)
+    sc.finals.reset()
+    zeros = _Zeros(dev)
+    packs = _Packs(plan.units, True)
+    dead = dead_activations(pp.units)
+    dys = [torch.empty((n,) + sizes[o.level] + (plan.rows,), dtype=torch.float16, device=dev) for o in plan.outs]
+    ops.lfdhead_out_grad_levels(_lfd_out_levels(plan, len(sizes), starts, raws, dys, store), dcls.contiguous(), dreg.contiguous(), scale)
+    _head_tail_backward(plan, (acts, tape), htape, opk, dys, 1, store, sc, packs, zeros, dead, scale, sw)
+
+
+class LFDDetectorTrainFunction(torch.autograd.Function):
+    """(cls [N,P,C'], reg [N,P,4]) = LFD.forward(x) in train mode as ONE autograd node: backbone, pyramid neck and LFDHead forward
+    and backward on the hand-written kernels (lfd_detector_forward / lfd_detector_backward)."""
+
+    @staticmethod
+    def forward(ctx, plan, x, *params):
+        cls, reg, sizes, saved = lfd_detector_forward(plan, x)
+        ctx.plan, ctx.saved = plan, saved
+        LFDDetectorTrainFunction.last_sizes = sizes
+        return cls, reg
+
+    @staticmethod
+    def backward(ctx, dcls, dreg):
+        plan, saved = ctx.plan, ctx.saved
+        starts, sizes = saved[4], saved[5]
+        p = starts[-1] + sizes[-1][0] * sizes[-1][1]
+        ref = saved[0][0][plan.pyramid.out_ids[0]]
+        zero = lambda c: torch.zeros((ref.size(0), p, c), dtype=torch.float32, device=ref.device)         # noqa: E731
+        dcls = zero(plan.cls_channels) if dcls is None else dcls
+        dreg = zero(4) if dreg is None else dreg
+        lfd_detector_backward(plan, saved, dcls, dreg, loss_scale())
+        ctx.saved = None
+        return (None, None) + (None,) * len(plan.params)     # gradients were accumulated into .grad directly
+
+
+def lfd_detector_train_forward(backbone, neck, head, x):
+    """-> (cls, reg, [(h, w)] per level)"""
+    check_train_input(backbone, x)
+    plan = head.__dict__.get('_lfd_detector_plan')
+    if plan is None or plan.pyramid is not neck.__dict__.get('_lfd_pyramid_plan') or plan.pyramid.owner is not backbone:
+        plan = build_lfd_detector(backbone, neck, head)
+        head.__dict__['_lfd_detector_plan'] = plan
+    cls, reg = LFDDetectorTrainFunction.apply(plan, x, *plan.params)
+    return cls, reg, LFDDetectorTrainFunction.last_sizes

@@ -1,7 +1,8 @@
 """tools/bench_sibling_train.py -- one training iteration of the pyramid siblings: forward, device targets, fused loss, backward
 (no optimizer) of FCOS_FPN and LFDV2_SFPN at 640x640, batch 32, 2-6 boxes per image (seeded; the shape of
 tools/bench_sibling_loss.py), on the routes a model has:
-    head_node      (FCOS_FPN) LFD_HIP_HEAD=1: backbone + neck + FCOSHead as one autograd node (train_engine.DetectorTrainFunction)
+    head_node      LFD_HIP_HEAD=1: backbone + neck + head as one autograd node (FCOS_FPN: train_engine.DetectorTrainFunction;
+                   LFDV2_SFPN: train_engine.LFDDetectorTrainFunction)
     node           LFD_HIP_HEAD=0: the backbone + neck node (train_engine.PyramidTrainFunction), the head under autograd
     autograd_neck  LFD_HIP_NECK=0: the backbone node, neck and head as PyTorch-ROCm modules under autograd, where that route
                    exists -- autograd refuses LFDV2_SFPN's neck (an in-place op on a tensor ReluBackward saved), reported as such.
@@ -27,7 +28,8 @@ MODELS = ('FCOS_FPN', 'LFDV2_SFPN')
 # route -> the environment that selects it (the head switch only moves a model whose head the detector node admits)
 ROUTES = {'FCOS_FPN': (('head_node', dict(LFD_HIP_NECK='1', LFD_HIP_HEAD='1')), ('node', dict(LFD_HIP_NECK='1', LFD_HIP_HEAD='0')),
                        ('autograd_neck', dict(LFD_HIP_NECK='0', LFD_HIP_HEAD='0'))),
-          'LFDV2_SFPN': (('node', dict(LFD_HIP_NECK='1', LFD_HIP_HEAD='0')), ('autograd_neck', dict(LFD_HIP_NECK='0', LFD_HIP_HEAD='0')))}
+          'LFDV2_SFPN': (('head_node', dict(LFD_HIP_NECK='1', LFD_HIP_HEAD='1')), ('node', dict(LFD_HIP_NECK='1', LFD_HIP_HEAD='0')),
+                         ('autograd_neck', dict(LFD_HIP_NECK='0', LFD_HIP_HEAD='0')))}
 
 
 def worker(args):
