@@ -341,6 +341,42 @@ LFD_API int lfd_get_loss_bwd_f32(const lfd_loss_desc_t* d, const float* pred_cls
                          const float* cls_targets, const float* reg_targets, const float* finalized,
                          const float* grad_out, float* grad_cls, float* grad_reg, lfd_stream_t stream);
 
+/* Fused get_loss for every pair of loss modules LFD / LFDv2 accept (csrc/getloss_ex.hip): the three stages, the sums[8] and
+ * out[8] layouts, the row classification and the normalisers of lfd_get_loss_* above, with
+ *   cls_loss 0 FocalLoss (sigmoid), 1 CrossEntropyLoss (num_classes + 1 channels), 2 QualityFocalLoss
+ *            (gfocal_loss.py:11-51: per class B(x, t) |t - sigmoid(x)|^qfl_beta, t = the row's maximum score at the label's
+ *            channel of a positive row and 0 elsewhere, a constant of the backward), 3 BCEWithLogitsLoss (lfd.py:342-347:
+ *            B(x_c, target_c) against the row's whole soft target vector, summed);
+ *   reg_loss 0 IoULoss, 1 GIoULoss, 2 DIoULoss, 3 CIoULoss (iou_loss.py:105-283) on distance2bbox of the decoded
+ *            prediction and of the target, times the row's score when reg_weighted; 4 SmoothL1Loss(smooth_l1_beta),
+ *            5 MSELoss (lfd.py:354-358, 'independent'): elementwise on the raw four outputs against the raw targets,
+ *            summed over the four components, no decode; reg_weighted is LFD_ERR_UNSUPPORTED with these two.
+ * Reduction 'mean' only.  lfd_get_loss_* keeps the Focal / CrossEntropy + IoU pair with its own kernels. */
+typedef struct lfd_loss_ex_desc {
+  int32_t n, num_levels;
+  int32_t level_h[LFD_MAX_LEVELS], level_w[LFD_MAX_LEVELS], stride[LFD_MAX_LEVELS];
+  float range_max[LFD_MAX_LEVELS];  /* max(regression_ranges[i]) ('sigmoid' decode, lfd.py:368-373) */
+  int32_t total_points, num_classes;
+  int32_t cls_loss;                 /* 0..3, see above */
+  int32_t reg_loss;                 /* 0..5, see above */
+  int32_t decode_mode;              /* 0 sigmoid * range_max, 1 exp (lfd.py:366-374); unused by reg_loss 4, 5 */
+  float gamma, alpha;               /* FocalLoss */
+  float qfl_beta;                   /* QualityFocalLoss */
+  float smooth_l1_beta;             /* SmoothL1Loss (> 0) */
+  float box_eps;                    /* eps of the IoU-family module */
+  float cls_loss_weight, reg_loss_weight;   /* loss_weight of the two loss modules */
+  int32_t cls_weighted, reg_weighted;       /* enable_classification_weight / enable_regression_weight */
+} lfd_loss_ex_desc_t;
+LFD_API size_t lfd_get_loss_ex_workspace_bytes(void);
+LFD_API int lfd_get_loss_ex_sums_f32(const lfd_loss_ex_desc_t* d, const float* pred_cls, const float* pred_reg,
+                             const float* cls_targets, const float* reg_targets, void* workspace, size_t workspace_bytes,
+                             double* sums, lfd_stream_t stream);
+LFD_API int lfd_get_loss_ex_finalize_f32(const lfd_loss_ex_desc_t* d, const double* local_sums, const double* global_sums,
+                                 float rank_scale, float* out, lfd_stream_t stream);
+LFD_API int lfd_get_loss_ex_bwd_f32(const lfd_loss_ex_desc_t* d, const float* pred_cls, const float* pred_reg,
+                            const float* cls_targets, const float* reg_targets, const float* finalized,
+                            const float* grad_out, float* grad_cls, float* grad_reg, lfd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Sibling meta-architectures: target assignment and fused get_loss on the device (csrc/assign_sibling.hip,
  * csrc/getloss_fcos.hip).  Conventions of lfd_assign_targets_f32: whole batch in one launch, one thread per (image,

@@ -27,26 +27,15 @@ __global__ __launch_bounds__(kThreads) void k_box_loss(const float4* __restrict_
 
 // Elementwise regression losses of LFD's "independent" family (lfd.py:61-66): smooth-L1 (smooth_l1_loss.py:11-22:
 // 0.5 d^2 / beta below beta, d - 0.5 beta above), L1 (:25-30) and MSE (mse_loss.py:11-13), loss and d loss / d pred
-// in one pass.  kind: 1 smooth-L1, 2 L1, 3 MSE.  |x| has derivative sign(x) with sign(0) = 0, like torch.abs.
+// in one pass.  kind: 1 smooth-L1, 2 L1, 3 MSE (pointwise_loss_elem, loss_elems.h: shared with the fused get_loss).
 __global__ __launch_bounds__(kThreads) void k_pointwise_loss(const float* __restrict__ pred,
                                                             const float* __restrict__ target, int64_t n, int kind,
                                                             float beta, float* __restrict__ loss,
                                                             float* __restrict__ dpred) {
   for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
-    const float x = pred[i] - target[i];
-    const float d = fabsf(x);
-    const float sg = x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);
-    float l, g;
-    if (kind == 1) {
-      if (d < beta) { l = 0.5f * d * d / beta; g = sg * (d / beta); }
-      else { l = d - 0.5f * beta; g = sg; }
-    } else if (kind == 2) {
-      l = d; g = sg;
-    } else {
-      l = x * x; g = 2.f * x;
-    }
-    loss[i] = l;
-    if (dpred) dpred[i] = g;
+    const LossGrad e = pointwise_loss_elem(pred[i] - target[i], kind, beta);
+    loss[i] = e.l;
+    if (dpred) dpred[i] = e.g;
   }
 }
 
@@ -76,15 +65,9 @@ __global__ __launch_bounds__(kThreads) void k_qfl(const float* __restrict__ x, c
     for (int j = 0; j < c; ++j) {
       const float xv = x[r * c + j];
       const float t = (lab == j) ? sc : 0.f;            // labels outside [0, c) are background: no positive class
-      const float s = 1.f / (1.f + expf(-xv));
-      const float u = t - s, m = fabsf(u);
-      const float b = bce_logits(xv, t);
-      const float mb = powf(m, beta);
-      sum += b * mb;
-      if (dx) {
-        const float sg = u > 0.f ? 1.f : (u < 0.f ? -1.f : 0.f);
-        dx[r * c + j] = (s - t) * mb - b * beta * powf(m, beta - 1.f) * sg * s * (1.f - s);
-      }
+      const LossGrad e = qfl_elem(xv, t, beta);          // loss_elems.h: shared with the fused get_loss
+      sum += e.l;
+      if (dx) dx[r * c + j] = e.g;
     }
     loss[r] = sum;
   }

@@ -1,5 +1,6 @@
-// csrc/loss_elems.h -- per-element device functions shared by the stand-alone loss kernels (losses.hip,
-// targets.hip) and the fused get_loss kernels (getloss.hip), so both paths produce the same values.
+// csrc/loss_elems.h -- per-element device functions shared by the stand-alone loss kernels (losses.hip, boxloss.hip,
+// targets.hip) and the fused get_loss kernels (getloss.hip, getloss_ex.hip, getloss_fcos.hip), so both paths produce the
+// same values.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -162,4 +163,42 @@ static __device__ __forceinline__ Dual box_loss(float4 p, float4 t, int kind, fl
 // B(x, t) = max(x, 0) - x t + log(1 + exp(-|x|))  (F.binary_cross_entropy_with_logits), dB/dx = sigmoid(x) - t
 static __device__ __forceinline__ float bce_logits(float x, float t) {
   return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+}
+
+// one (row, class) element of Quality Focal Loss (gfocal_loss.py:11-52) against the quality target t (the score at the
+// label's channel, 0 elsewhere): l = B(x, t) |t - s|^beta, s = sigmoid(x);
+//   dl/dx = (s - t) |t - s|^beta - B beta |t - s|^(beta-1) sign(t - s) s (1 - s)   (t is a constant)
+struct LossGrad {
+  float l, g;
+};
+static __device__ __forceinline__ LossGrad qfl_elem(float xv, float t, float beta) {
+  const float s = 1.f / (1.f + expf(-xv));
+  const float u = t - s, m = fabsf(u);
+  const float b = bce_logits(xv, t);
+  const float mb = powf(m, beta);
+  const float sg = u > 0.f ? 1.f : (u < 0.f ? -1.f : 0.f);
+  LossGrad r;
+  r.l = b * mb;
+  r.g = (s - t) * mb - b * beta * powf(m, beta - 1.f) * sg * s * (1.f - s);
+  return r;
+}
+static __device__ __forceinline__ float qfl_fwd_elem(float xv, float t, float beta) { return qfl_elem(xv, t, beta).l; }
+static __device__ __forceinline__ float qfl_bwd_elem(float xv, float t, float beta) { return qfl_elem(xv, t, beta).g; }
+
+// one element of LFD's "independent" regression losses on x = pred - target: kind 1 smooth-L1 (smooth_l1_loss.py:11-22:
+// 0.5 d^2 / beta below beta, d - 0.5 beta above), 2 L1 (:25-30), 3 MSE (mse_loss.py:11-13), with d loss / d pred.
+// |x| has derivative sign(x) with sign(0) = 0, like torch.abs.
+static __device__ __forceinline__ LossGrad pointwise_loss_elem(float x, int kind, float beta) {
+  const float d = fabsf(x);
+  const float sg = x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);
+  LossGrad r;
+  if (kind == 1) {
+    if (d < beta) { r.l = 0.5f * d * d / beta; r.g = sg * (d / beta); }
+    else { r.l = d - 0.5f * beta; r.g = sg; }
+  } else if (kind == 2) {
+    r.l = d; r.g = sg;
+  } else {
+    r.l = x * x; r.g = 2.f * x;
+  }
+  return r;
 }

@@ -168,6 +168,19 @@ class LossDesc(C.Structure):
                 ('cls_weighted', C.c_int32), ('reg_weighted', C.c_int32)]
 
 
+class LossDescEx(C.Structure):
+    """lfd_loss_ex_desc_t"""
+    _fields_ = [('n', C.c_int32), ('num_levels', C.c_int32),
+                ('level_h', C.c_int32 * MAX_LEVELS), ('level_w', C.c_int32 * MAX_LEVELS), ('stride', C.c_int32 * MAX_LEVELS),
+                ('range_max', C.c_float * MAX_LEVELS),
+                ('total_points', C.c_int32), ('num_classes', C.c_int32),
+                ('cls_loss', C.c_int32), ('reg_loss', C.c_int32), ('decode_mode', C.c_int32),
+                ('gamma', C.c_float), ('alpha', C.c_float), ('qfl_beta', C.c_float), ('smooth_l1_beta', C.c_float),
+                ('box_eps', C.c_float),
+                ('cls_loss_weight', C.c_float), ('reg_loss_weight', C.c_float),
+                ('cls_weighted', C.c_int32), ('reg_weighted', C.c_int32)]
+
+
 class AssignFcosDesc(C.Structure):
     """lfd_assign_fcos_desc_t"""
     _fields_ = [('n', C.c_int32), ('num_levels', C.c_int32),
@@ -332,6 +345,10 @@ _SIGNATURES = {
     'lfd_get_loss_sums_f32': (C.c_int, [C.POINTER(LossDesc), _P, _P, _P, _P, _P, _SZ, _P, _P]),
     'lfd_get_loss_finalize_f32': (C.c_int, [C.POINTER(LossDesc), _P, _P, _F, _P, _P]),
     'lfd_get_loss_bwd_f32': (C.c_int, [C.POINTER(LossDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'lfd_get_loss_ex_workspace_bytes': (_SZ, []),
+    'lfd_get_loss_ex_sums_f32': (C.c_int, [C.POINTER(LossDescEx), _P, _P, _P, _P, _P, _SZ, _P, _P]),
+    'lfd_get_loss_ex_finalize_f32': (C.c_int, [C.POINTER(LossDescEx), _P, _P, _F, _P, _P]),
+    'lfd_get_loss_ex_bwd_f32': (C.c_int, [C.POINTER(LossDescEx), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'lfd_assign_targets_fcos_f32': (C.c_int, [C.POINTER(AssignFcosDesc), _P, _P, _I64, _P, _P, _P, _P, _P]),
     'lfd_assign_targets_v2_f32': (C.c_int, [C.POINTER(AssignDesc), _P, _P, _I64, _P, _P, _P, _P, _P]),
     'lfd_fcos_loss_workspace_bytes': (_SZ, []),

@@ -9,7 +9,9 @@ fp32, `head_indexes_to_feature_map_sizes`, `get_results`, `predict_for_single_im
                             per-image Python loop with ~20 tiny ATen kernels per level and a
                             blocking D2H of the NMS mask per image (lfd.py:412-431, nms_kernel.cu:105-111)
   get_loss               -> device target assignment (csrc/targets.hip) + the three-launch fused loss
-                            (csrc/getloss.hip); other loss modules take the op-by-op path on the HIP loss kernels
+                            (csrc/getloss.hip; csrc/getloss_ex.hip for the other pairs of loss modules the constructor
+                            accepts, 'mean' reduction: see LFD._fused_loss_route for its switch); what is not admitted takes
+                            the op-by-op path on the HIP loss kernels
 
 Train-mode forward (`self.training`): for the shipped configurations the whole network runs forward and
 backward on the hand-written kernels as one autograd node (train_engine.NetworkTrainFunction, csrc/train.hip;
@@ -28,14 +30,34 @@ from .. import engine, engine_p32, engine_sibling, ops, parallel, train_engine
 from ..data import DeviceAnnotations
 from .utils import multiclass_nms  # noqa: F401  (kept importable like the reference module)
 
-__all__ = ['LFD']
+__all__ = ['LFD', 'fused_loss_route']
 
 _UNION = ('IoULoss', 'GIoULoss', 'DIoULoss', 'CIoULoss')
 
 
+def fused_loss_route(classification_loss_func, regression_loss_func, enable_classification_weight=False,
+                     enable_regression_weight=False):
+    """Which fused get_loss kernels cover a pair of loss modules: 'base' (csrc/getloss.hip: FocalLoss or CrossEntropyLoss +
+    IoULoss), 'ex' (csrc/getloss_ex.hip: every other pair of FocalLoss / CrossEntropyLoss / QualityFocalLoss /
+    BCEWithLogitsLoss with IoULoss / GIoULoss / DIoULoss / CIoULoss / SmoothL1Loss / MSELoss) or None (the op-by-op route:
+    a softmax FocalLoss, a reduction other than 'mean', an independent regression loss with enable_regression_weight --
+    the reference multiplies a [K] weight into a [K,4] loss there)."""
+    cn, rn = type(classification_loss_func).__name__, type(regression_loss_func).__name__
+    if cn not in ops.CLS_LOSSES or rn not in ops.REG_LOSSES:
+        return None
+    if cn == 'FocalLoss' and not getattr(classification_loss_func, 'use_sigmoid', True):
+        return None
+    if any(getattr(f, 'reduction', None) != 'mean' for f in (classification_loss_func, regression_loss_func)):
+        return None
+    if rn in ('SmoothL1Loss', 'MSELoss') and enable_regression_weight:
+        return None
+    return 'base' if cn in ('FocalLoss', 'CrossEntropyLoss') and rn == 'IoULoss' else 'ex'
+
+
 class _FusedLossFunction(torch.autograd.Function):
-    """get_loss as lfd_get_loss_{sums,finalize,bwd}_f32 (csrc/getloss.hip): -> [classification_loss,
-    regression_loss, loss]; backward writes the dense prediction gradients in one launch."""
+    """get_loss as lfd_get_loss_{sums,finalize,bwd}_f32 (csrc/getloss.hip) or, for a lfd_loss_ex_desc_t, their
+    lfd_get_loss_ex_* twins (csrc/getloss_ex.hip): -> [classification_loss, regression_loss, loss]; backward writes the
+    dense prediction gradients in one launch."""
 
     @staticmethod
     def forward(ctx, pred_cls, pred_reg, cls_t, reg_t, desc, reduce_sums, rank_scale):
@@ -463,6 +485,7 @@ class LFD(nn.Module):
     def _loss_from_targets(self, pred_cls, pred_reg, cls_t, reg_t, pts_list):
         """lfd.py:300-395 from the flattening on: op by op on the HIP loss kernels (any loss module combination)"""
         dev = pred_cls.device
+        self.__dict__['_last_loss_route'] = 'op_by_op'
         N = pred_cls.size(0)
         C = self._num_classes
         ce = self._is_ce()
@@ -518,23 +541,42 @@ class LFD(nn.Module):
         return dict(loss=loss, loss_values=dict(loss=loss.item(), classification_loss=cls_loss.item(),
                                                 regression_loss=reg_loss.item()))
 
+    def _fused_loss_route(self):
+        """fused_loss_route of this model's loss modules under the two switches.  LFD_FUSED_LOSS=0: the op-by-op route for every
+        pair.  LFD_FUSED_LOSS_EX: 0 = only the pairs of csrc/getloss.hip are fused (the admission before csrc/getloss_ex.hip;
+        A/B timing and parity), 1 = every pair fused_loss_route admits; unset = the 'ex' pairs whose regression module is
+        IoULoss (QualityFocalLoss / BCEWithLogitsLoss + IoULoss: the shipped TrafficLight configurations) -- the other
+        regression modules occur in no shipped configuration and keep the op-by-op route until the switch asks for the
+        fused one"""
+        if os.environ.get('LFD_FUSED_LOSS', '1') == '0':
+            return None
+        route = fused_loss_route(self._classification_loss_func, self._regression_loss_func,
+                                 self._enable_classification_weight, self._enable_regression_weight)
+        if route == 'ex':
+            ex = os.environ.get('LFD_FUSED_LOSS_EX')
+            if ex == '0' or (ex != '1' and type(self._regression_loss_func).__name__ != 'IoULoss'):
+                return None
+        return route
+
     def _fused_loss_supported(self, pred_cls):
-        """The three-launch device path (csrc/getloss.hip) covers what the shipped configs use: FocalLoss or
-        CrossEntropyLoss + IoULoss, 'mean' reduction; other loss modules take the op-by-op path above."""
-        if pred_cls.device.type != 'cuda' or os.environ.get('LFD_FUSED_LOSS', '1') == '0':
-            return False
-        cf, rf = self._classification_loss_func, self._regression_loss_func
-        if type(cf).__name__ == 'FocalLoss':
-            if not getattr(cf, 'use_sigmoid', True):
-                return False
-        elif type(cf).__name__ != 'CrossEntropyLoss':
-            return False
-        return type(rf).__name__ == 'IoULoss' and cf.reduction == 'mean' and rf.reduction == 'mean'
+        """The three-launch device path: csrc/getloss.hip for FocalLoss or CrossEntropyLoss + IoULoss, csrc/getloss_ex.hip for
+        the other pairs the constructor accepts ('mean' reduction); what fused_loss_route refuses takes the op-by-op path"""
+        return pred_cls.device.type == 'cuda' and self._fused_loss_route() is not None
 
     def _loss_desc(self, n):
-        """lfd_loss_desc_t of the fused get_loss kernels for a batch of n images at the recorded feature-map sizes"""
+        """descriptor of the fused get_loss kernels for a batch of n images at the recorded feature-map sizes:
+        lfd_loss_desc_t for the 'base' pairs, lfd_loss_ex_desc_t otherwise (ops.get_loss_* dispatch on its type)"""
         cf, rf = self._classification_loss_func, self._regression_loss_func
         sizes = [self._head_indexes_to_feature_map_sizes[i] for i in range(self._num_heads)]
+        if self._fused_loss_route() == 'ex':
+            return ops.make_loss_desc_ex(n, sizes, self._point_strides, self._regression_ranges, self._num_classes,
+                                         type(cf).__name__, type(rf).__name__, self._distance_to_bbox_mode,
+                                         gamma=getattr(cf, 'gamma', 2.0), alpha=getattr(cf, 'alpha', 0.25),
+                                         qfl_beta=getattr(cf, 'beta', 2.0), smooth_l1_beta=getattr(rf, 'beta', 1.0),
+                                         box_eps=getattr(rf, 'eps', 1e-6),
+                                         cls_loss_weight=cf.loss_weight, reg_loss_weight=rf.loss_weight,
+                                         cls_weighted=self._enable_classification_weight,
+                                         reg_weighted=self._enable_regression_weight)
         return ops.make_loss_desc(n, sizes, self._point_strides, self._regression_ranges,
                                   self._num_classes, self._is_ce(), self._distance_to_bbox_mode,
                                   gamma=getattr(cf, 'gamma', 2.0), alpha=getattr(cf, 'alpha', 0.25), iou_eps=rf.eps,
@@ -553,7 +595,14 @@ class LFD(nn.Module):
                                         parallel.global_count if dist_on else None,
                                         float(parallel.world_size()) if dist_on else 1.0)
 
+    @property
+    def last_loss_route(self):
+        """the route the last get_loss took: 'base' (csrc/getloss.hip), 'ex' (csrc/getloss_ex.hip), 'op_by_op', or None
+        before the first call"""
+        return self.__dict__.get('_last_loss_route')
+
     def _get_loss_fused(self, pred_cls, pred_reg, cls_t, reg_t):
+        self.__dict__['_last_loss_route'] = self._fused_loss_route()
         vals = self._fused_loss_tensor(pred_cls, pred_reg, cls_t, reg_t)
         c, r, t = vals.tolist()      # the one host sync of the step (the reference does three .item())
         return dict(loss=vals[2], loss_values=dict(loss=t, classification_loss=c, regression_loss=r))

@@ -10,13 +10,15 @@ modes, predict_for_single_image :704-815 == LFD's) is inherited from ..lfd.LFD.
 Where the arithmetic runs: forward on the fused LFD plan when neck / head are what that plan covers (SimpleNeck + 1x1
 LFDHead), otherwise layer by layer on the same kernels (engine_sibling: FPN / SimpleFPN necks, 3x3 head convs);
 get_results as one lfd_detect_batched_ex pass per batch; get_loss on a CUDA prediction: targets by
-lfd_assign_targets_v2_f32 (csrc/assign_sibling.hip), then LFD's fused get_loss when the loss modules are what it covers,
-else the op-by-op HIP loss kernels; `device_targets = False` builds the targets with the reference's tensor algebra on the
-host (annotation_to_target, the public mirror) and takes the op-by-op losses.
+lfd_assign_targets_v2_f32 (csrc/assign_sibling.hip; from the device buffers of a DeviceAnnotations batch as they are), then
+LFD's fused get_loss when the loss modules are what it admits (LFD._fused_loss_route), else the op-by-op HIP loss kernels;
+`device_targets = False` builds the targets with the reference's tensor algebra on the host (annotation_to_target, the public
+mirror) and takes the op-by-op losses.
 """
 import torch
 
 from .. import ops
+from ..data import DeviceAnnotations
 from .lfd import LFD
 from .fcos import _results_from_detect
 
@@ -127,12 +129,24 @@ class LFDv2(LFD):
         return cls_t, reg_t
 
     def _fused_loss_supported(self, pred_cls):
-        """LFD's rule (Focal or CE + IoULoss, 'mean'): the fused get_loss reads targets, whoever assigned them"""
+        """LFD's rule (LFD._fused_loss_route): the fused get_loss reads targets, whoever assigned them"""
         return self.device_targets and super()._fused_loss_supported(pred_cls)
 
     def get_loss(self, predict_outputs, annotation_batch, *args):
         """lfdv2.py:443-554: same reduction as LFD.get_loss over LFDv2's targets"""
         pred_cls, pred_reg = predict_outputs
+        if isinstance(annotation_batch, DeviceAnnotations):
+            # annotations planned on the device (lfd_amd.data.ResidentDataLoader): the device-target route only
+            if not (pred_cls.device.type == 'cuda' and self._fused_loss_supported(pred_cls)):
+                raise RuntimeError('LFDv2.get_loss: DeviceAnnotations need the device target route (a CUDA prediction and the '
+                                   'fused loss); pass annotation_batch.to_host() on the host route')
+            sizes = [self._head_indexes_to_feature_map_sizes[i] for i in range(self._num_heads)]
+            a = annotation_batch
+            cls_t, reg_t = ops.assign_targets_v2_device(sizes, self._point_strides, self._regression_ranges, self._gray_ranges,
+                                                        self._num_classes, self._range_assign_mode,
+                                                        self._regression_loss_type == 'independent', a.boxes, a.labels,
+                                                        a.offsets)
+            return self._get_loss_fused(pred_cls, pred_reg, cls_t, reg_t)
         if pred_cls.device.type == 'cuda' and self.device_targets:
             sizes = [self._head_indexes_to_feature_map_sizes[i] for i in range(self._num_heads)]
             # annotation_to_target builds the ranges with points.new_tensor(...) on the int64 point grid (lfdv2.py:232-276)

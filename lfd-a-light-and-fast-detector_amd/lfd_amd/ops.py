@@ -457,9 +457,40 @@ def make_loss_desc(n, sizes, strides, reg_ranges, num_classes, cross_entropy, de
     return d
 
 
+CLS_LOSSES = {'FocalLoss': 0, 'CrossEntropyLoss': 1, 'QualityFocalLoss': 2, 'BCEWithLogitsLoss': 3}
+REG_LOSSES = {'IoULoss': 0, 'GIoULoss': 1, 'DIoULoss': 2, 'CIoULoss': 3, 'SmoothL1Loss': 4, 'MSELoss': 5}
+
+
+def make_loss_desc_ex(n, sizes, strides, reg_ranges, num_classes, cls_loss, reg_loss, decode_mode, gamma=2.0, alpha=0.25,
+                      qfl_beta=2.0, smooth_l1_beta=1.0, box_eps=1e-6, cls_loss_weight=1.0, reg_loss_weight=1.0,
+                      cls_weighted=False, reg_weighted=False):
+    """lfd_loss_ex_desc_t for the fused get_loss kernels of every loss pair (csrc/getloss_ex.hip).  cls_loss / reg_loss: a
+    key of CLS_LOSSES / REG_LOSSES (the loss module's class name) or its number; decode_mode: 'sigmoid' | 'exp'."""
+    d = _lib.LossDescEx()
+    d.n, d.num_levels = int(n), len(sizes)
+    total = 0
+    for i, (h, w) in enumerate(sizes):
+        d.level_h[i], d.level_w[i], d.stride[i] = int(h), int(w), int(strides[i])
+        d.range_max[i] = float(max(reg_ranges[i]))
+        total += int(h) * int(w)
+    d.total_points, d.num_classes = total, int(num_classes)
+    d.cls_loss = CLS_LOSSES[cls_loss] if isinstance(cls_loss, str) else int(cls_loss)
+    d.reg_loss = REG_LOSSES[reg_loss] if isinstance(reg_loss, str) else int(reg_loss)
+    d.decode_mode = {'sigmoid': 0, 'exp': 1}[decode_mode]
+    d.gamma, d.alpha, d.qfl_beta = float(gamma), float(alpha), float(qfl_beta)
+    d.smooth_l1_beta, d.box_eps = float(smooth_l1_beta), float(box_eps)
+    d.cls_loss_weight, d.reg_loss_weight = float(cls_loss_weight), float(reg_loss_weight)
+    d.cls_weighted, d.reg_weighted = int(bool(cls_weighted)), int(bool(reg_weighted))
+    return d
+
+
+def _is_ex(desc):
+    return isinstance(desc, _lib.LossDescEx)
+
+
 def _loss_inputs(desc, pred_cls, pred_reg, cls_t, reg_t):
     require_cuda(pred_cls, 'get_loss')
-    ch = desc.num_classes + (1 if desc.cls_loss else 0)
+    ch = desc.num_classes + (1 if desc.cls_loss == 1 else 0)
     rows = desc.n * desc.total_points
     ts = [pred_cls.detach().contiguous().float(), pred_reg.detach().contiguous().float(),
           cls_t.contiguous().float(), reg_t.contiguous().float()]
@@ -471,7 +502,11 @@ def _loss_inputs(desc, pred_cls, pred_reg, cls_t, reg_t):
 
 def get_loss_sums(desc, pred_cls, pred_reg, cls_t, reg_t):
     """First half of the fused get_loss forward: this rank's float64[8] sums (lfd_get_loss_sums_f32).  Under image-parallel
-    training they are all-reduced before `get_loss_finalize` (lfd.py:340,383: `n_pos + 1` / `n_pos` are global-batch counts)."""
+    training they are all-reduced before `get_loss_finalize` (lfd.py:340,383: `n_pos + 1` / `n_pos` are global-batch counts).
+    get_loss_sums / _finalize / _forward / _backward dispatch on the descriptor: a lfd_loss_ex_desc_t (make_loss_desc_ex)
+    runs the get_loss_ex_* twin."""
+    if _is_ex(desc):
+        return get_loss_ex_sums(desc, pred_cls, pred_reg, cls_t, reg_t)
     pc, pr, ct, rt = _loss_inputs(desc, pred_cls, pred_reg, cls_t, reg_t)
     dev = pc.device
     nbytes = lib().lfd_get_loss_workspace_bytes()
@@ -486,6 +521,8 @@ def get_loss_sums(desc, pred_cls, pred_reg, cls_t, reg_t):
 def get_loss_finalize(desc, sums, gsums, rank_scale=1.0):
     """Second half: local + global sums -> float32[8] {classification_loss, regression_loss, loss, n_pos, avg_cls, avg_reg,
     n_green, rank_scale} (lfd_get_loss_finalize_f32)"""
+    if _is_ex(desc):
+        return get_loss_ex_finalize(desc, sums, gsums, rank_scale)
     out = torch.empty(8, dtype=torch.float32, device=sums.device)
     with torch.cuda.device(sums.device):
         check(lib().lfd_get_loss_finalize_f32(C.byref(desc), ptr(sums), ptr(gsums), float(rank_scale), ptr(out),
@@ -505,12 +542,54 @@ def get_loss_forward(desc, pred_cls, pred_reg, cls_t, reg_t, reduce_sums=None, r
 
 def get_loss_backward(desc, pred_cls, pred_reg, cls_t, reg_t, finalized, grad_out):
     """-> (d pred_cls, d pred_reg), dense, for grad_out[3] = d/d{classification_loss, regression_loss, loss}."""
+    if _is_ex(desc):
+        return get_loss_ex_backward(desc, pred_cls, pred_reg, cls_t, reg_t, finalized, grad_out)
     pc, pr, ct, rt = _loss_inputs(desc, pred_cls, pred_reg, cls_t, reg_t)
     g = grad_out.contiguous().float()
     gc, gr = torch.empty_like(pc), torch.empty_like(pr)
     with torch.cuda.device(pc.device):
         check(lib().lfd_get_loss_bwd_f32(C.byref(desc), ptr(pc), ptr(pr), ptr(ct), ptr(rt), ptr(finalized), ptr(g),
                                          ptr(gc), ptr(gr), stream_ptr()), 'lfd_get_loss_bwd_f32')
+    return gc, gr
+
+
+def get_loss_ex_sums(desc, pred_cls, pred_reg, cls_t, reg_t):
+    """get_loss_sums for a lfd_loss_ex_desc_t (lfd_get_loss_ex_sums_f32): this rank's float64[8] sums"""
+    pc, pr, ct, rt = _loss_inputs(desc, pred_cls, pred_reg, cls_t, reg_t)
+    dev = pc.device
+    nbytes = lib().lfd_get_loss_ex_workspace_bytes()
+    ws = _workspace(nbytes, dev)
+    sums = torch.empty(8, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().lfd_get_loss_ex_sums_f32(C.byref(desc), ptr(pc), ptr(pr), ptr(ct), ptr(rt), ptr(ws), nbytes, ptr(sums),
+                                             stream_ptr()), 'lfd_get_loss_ex_sums_f32')
+    return sums
+
+
+def get_loss_ex_finalize(desc, sums, gsums, rank_scale=1.0):
+    """get_loss_finalize for a lfd_loss_ex_desc_t (lfd_get_loss_ex_finalize_f32), same float32[8] layout"""
+    out = torch.empty(8, dtype=torch.float32, device=sums.device)
+    with torch.cuda.device(sums.device):
+        check(lib().lfd_get_loss_ex_finalize_f32(C.byref(desc), ptr(sums), ptr(gsums), float(rank_scale), ptr(out),
+                                                 stream_ptr()), 'lfd_get_loss_ex_finalize_f32')
+    return out
+
+
+def get_loss_ex_forward(desc, pred_cls, pred_reg, cls_t, reg_t, reduce_sums=None, rank_scale=1.0):
+    """get_loss_forward for a lfd_loss_ex_desc_t: sums, the optional all-reduce over image-parallel ranks, finalize"""
+    sums = get_loss_ex_sums(desc, pred_cls, pred_reg, cls_t, reg_t)
+    gsums = reduce_sums(sums) if reduce_sums is not None else sums
+    return get_loss_ex_finalize(desc, sums, gsums, rank_scale)
+
+
+def get_loss_ex_backward(desc, pred_cls, pred_reg, cls_t, reg_t, finalized, grad_out):
+    """get_loss_backward for a lfd_loss_ex_desc_t (lfd_get_loss_ex_bwd_f32): -> dense (d pred_cls, d pred_reg)"""
+    pc, pr, ct, rt = _loss_inputs(desc, pred_cls, pred_reg, cls_t, reg_t)
+    g = grad_out.contiguous().float()
+    gc, gr = torch.empty_like(pc), torch.empty_like(pr)
+    with torch.cuda.device(pc.device):
+        check(lib().lfd_get_loss_ex_bwd_f32(C.byref(desc), ptr(pc), ptr(pr), ptr(ct), ptr(rt), ptr(finalized), ptr(g),
+                                            ptr(gc), ptr(gr), stream_ptr()), 'lfd_get_loss_ex_bwd_f32')
     return gc, gr
 
 
@@ -613,6 +692,23 @@ def assign_targets_v2_from_host(sizes, strides, reg_ranges, gray_ranges, num_cla
     d, total = make_assign_desc(len(annotation_batch), sizes, strides, reg_ranges, gray_ranges, num_classes, assign_mode,
                                 independent)
     return _assign_v2_launch(d, total, _concat_gt_host(annotation_batch, device), torch.device(device))
+
+
+def assign_targets_v2_device(sizes, strides, reg_ranges, gray_ranges, num_classes, assign_mode, independent, boxes, labels,
+                             offs):
+    """assign_targets_v2 from device-resident annotations in GraphedTrainStep's layout (lfd_amd.data.DeviceAnnotations):
+    boxes [K,4] fp32 xywh, labels [K] int64, offs [N+1] int32; K is the capacity of the buffer (the kernel reads no row
+    outside [0, K)), no host copy of the offsets and no sync"""
+    require_cuda(boxes, 'assign_targets_v2')
+    n = int(offs.numel()) - 1
+    d, total = make_assign_desc(n, sizes, strides, reg_ranges, gray_ranges, num_classes, assign_mode, independent)
+    dev = boxes.device
+    cls_t = torch.empty((n, total, d.num_classes), dtype=torch.float32, device=dev)
+    reg_t = torch.empty((n, total, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().lfd_assign_targets_v2_f32(C.byref(d), ptr(boxes), ptr(labels), int(boxes.size(0)), ptr(offs), None,
+                                              ptr(cls_t), ptr(reg_t), stream_ptr()), 'lfd_assign_targets_v2_f32')
+    return cls_t, reg_t
 
 
 FCOS_BOX_LOSSES = {'IoULoss': 0, 'GIoULoss': 1, 'DIoULoss': 2, 'CIoULoss': 3}
