@@ -1882,6 +1882,9 @@ static int wgrad_geometry(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t 
   } else if (ks == 3) {
     nwg = 256;
     if (stride == 2) { nwg = tiles / 6; if (nwg < 256) nwg = 256; if (nwg > 512) nwg = 512; }
+    // rows x blocks x 9 taps must fit the training workspace (lfd_train_workspace_bytes: 256 rows x 4 blocks): 128 -> 128
+    // channels at stride 2 on a map of more than 1541 tiles asked for up to twice that and wrote past its end
+    if (nwg * nblk > kWgradMaxWg * 4) nwg = kWgradMaxWg * 4 / nblk;
   } else {
     const int target = operand_bytes >= (128 << 20) ? 1024 : (operand_bytes >= (32 << 20) ? 512 : 256);
     nwg = target / nblk;
@@ -1922,6 +1925,7 @@ int lfd_conv_wgrad_nhwc_f16(const void* x, const void* dy, int32_t n, int32_t h,
   int rc = wgrad_geometry(n, h, w, cin, cout, ks, stride, &nwg, &nblk, &ho, &wo, &ts);
   if (rc != LFD_OK) return rc;
   if (workspace_bytes < lfd_train_workspace_bytes()) return LFD_ERR_WORKSPACE_TOO_SMALL;
+  if (workspace_bytes < (size_t)nwg * nblk * ks * ks * 64 * 64 * sizeof(float)) return LFD_ERR_WORKSPACE_TOO_SMALL;
   float* partials = reinterpret_cast<float*>(workspace);
   rc = wgrad_launch(x, dy, n, h, w, cin, cout, ks, stride, partials, nwg, nblk, ho, wo, ts, st);
   if (rc != LFD_OK) return rc;
