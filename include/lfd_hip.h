@@ -484,7 +484,8 @@ LFD_API int lfd_sgd_step_f32(float* params, float* grads, float* momentum_buf, i
  */
 typedef struct lfd_conv_desc {
   int32_t n, h, w;      /* input dims (NHWC) */
-  int32_t cin, cout;    /* cin in {32,64,128}; cout multiple of 32 */
+  int32_t cin, cout;    /* cin in {32,64,128} with the cout values csrc/conv.hip lists; or, when either side is above 128
+                         * (csrc/conv_wide.hip): cin a multiple of 64, cout a multiple of 32, both <= 512, no chained 1x1 */
   int32_t ks, stride;   /* 1|3 (pad = ks/2), 1|2 */
   int32_t relu;
   int32_t tail_cout;    /* 0: no chained 1x1; else must equal cout */
@@ -499,6 +500,10 @@ LFD_API int lfd_conv2d_downsample_nhwc_f16(const lfd_conv_desc_t* desc, const vo
                                            const void* w_packed, const float* bias,
                                            const void* ds_w_packed, const float* ds_bias, void* ds_out,
                                            const void* zeros, lfd_stream_t stream);
+
+/* The checks and the dispatch of lfd_conv2d_nhwc_f16 on a descriptor alone (no residual): 0 if the call would reach a kernel,
+ * else LFD_ERR_UNSUPPORTED (LFD_ERR_INVALID_ARGUMENT for a malformed descriptor).  Launches nothing, needs no device. */
+LFD_API int lfd_conv2d_nhwc_f16_supported(const lfd_conv_desc_t* desc);
 
 LFD_API int lfd_conv2d_nhwc_f16(const lfd_conv_desc_t* desc, const void* in, void* out,
                                 const void* w_packed, const float* bias, const void* residual,

@@ -49,6 +49,7 @@ struct ConvArgs {
   int cout2;   // tail output channels (TAIL only)
   int relu, relu2;
   int tiles_x, tiles_y, ntiles;
+  int dry;               // lfd_conv2d_nhwc_f16_supported: the dispatch reached an instance -- answer LFD_OK, launch nothing
   float* stat_partials;  // STATS kernels: [gridDim.x][2][cout] per-workgroup sums of the stored outputs and of their squares
   // PRO kernels (1x1 stride 1): `in` is the PRE-normalisation output y of the producing train-mode BatchNorm unit; the
   // activation fragments are normalised + ReLU'd on their way from LDS into the MFMA (the unit's z tensor never exists)
@@ -838,6 +839,7 @@ __global__ __launch_bounds__(256, 2) void k_conv(ConvArgs a) {
 template <int CIN, int KS, int S, int NCT, bool WREG, bool TAIL, bool RES, bool DS, bool ACC32 = false, bool STATS = false, bool PRO = false, bool BSUM = false>
 int launch_conv_(const ConvArgs& a0, hipStream_t st, int* blocks_out = nullptr) {
   using C = Cfg<CIN, KS, S, NCT, WREG, TAIL>;
+  if (a0.dry) return LFD_OK;
   ConvArgs a = a0;
   a.tiles_x = (a.OW + C::TW - 1) / C::TW;
   a.tiles_y = (a.OH + C::TH - 1) / C::TH;

@@ -434,6 +434,7 @@ _SIGNATURES = {
     'lfd_groupnorm_finalize_fold': (C.c_int, [C.POINTER(HeadDesc), _P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _F, _P,
                                               C.POINTER(HeadLevelPtrs), _I32, _P]),
     'lfd_conv_packed_weight_halfs': (_SZ, [_I32, _I32, _I32]),
+    'lfd_conv2d_nhwc_f16_supported': (C.c_int, [C.POINTER(ConvDesc)]),
     'lfd_conv2d_nhwc_f16': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'lfd_fasterblock_fused_f16': (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
     'lfd_fasterblock128_fused_f16': (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),

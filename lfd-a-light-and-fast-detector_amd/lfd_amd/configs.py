@@ -54,6 +54,37 @@ ARCHS = {
 }
 
 
+# ------------------------------------------------------------------ LFDResNet's own presets (lfd_resnet.py:222-231)
+# No shipped config uses them: block_mode / stem_mode / body_mode are the constructor's defaults ('fast' x 3) and their
+# siblings.  The 'fast' body ends in 256 and 512 channels, the 'faster' body in 256: the layers of csrc/conv_wide.hip.
+# out_indices: the last block of every stage (the constructor's default taps (0, 3) only exist in the 'fast' body).
+PRESET_BODY_ARCHITECTURES = {'fast': [4, 2, 2, 1, 1], 'faster': [2, 1, 1, 1, 1], 'fastest': [2, 1, 1, 1, 1]}
+PRESET_BODY_CHANNELS = {'fast': [64, 64, 128, 256, 512], 'faster': [64, 64, 128, 128, 256], 'fastest': [32, 32, 64, 64, 128]}
+
+
+def preset_arch(block_mode, stem_mode, body_mode, body_architecture=None, body_channels=None):
+    """the `arch` dict (build_modules / build_model) of LFDResNet(block_mode, stem_mode, body_mode) under SimpleNeck(128) + the
+    WIDERFACE head; body_mode=None takes body_architecture / body_channels instead"""
+    ba = PRESET_BODY_ARCHITECTURES[body_mode] if body_mode is not None else list(body_architecture)
+    arch = _wf(stem_mode, 64, None if body_mode is not None else ba, None if body_mode is not None and body_channels is None else body_channels,
+               tuple((i, n - 1) for i, n in enumerate(ba)))
+    arch.update(block_mode=block_mode, body_mode=body_mode)
+    return arch
+
+
+# the (block, stem, body) combinations with fixtures (tests/golden/make_golden_presets.py); the two body_mode=None cases put two
+# blocks into the 256- and 512-channel stages, so that the C -> C, residual and C -> C/2 layers occur
+PRESETS = {
+    'fast_fast_fast': preset_arch('fast', 'fast', 'fast'),
+    'faster_faster_faster': preset_arch('faster', 'faster', 'faster'),
+    'fastest_fastest_fastest': preset_arch('fastest', 'fastest', 'fastest'),
+    'fast_faster_faster': preset_arch('fast', 'faster', 'faster'),
+    'fastest_fast_fast': preset_arch('fastest', 'fast', 'fast'),
+    'faster_fast_11122': preset_arch('faster', 'fast', None, [1, 1, 1, 2, 2], PRESET_BODY_CHANNELS['fast']),
+    'fastest_fast_11122': preset_arch('fastest', 'fast', None, [1, 1, 1, 2, 2], PRESET_BODY_CHANNELS['fast']),
+}
+
+
 def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, iou_cls, ce_cls, seed=666, qfl_cls=None,
                   input_channels=3, frozen_stages=-1, norm_eval=False):
     """Instantiates (backbone, neck, head, LFD) from `arch` with the given classes (this package's
@@ -68,9 +99,12 @@ def build_modules(arch, backbone_cls, neck_cls, head_cls, lfd_cls, focal_cls, io
     else:
         cls_loss = focal_cls(use_sigmoid=True, gamma=2.0, alpha=0.25, reduction='mean', loss_weight=1.0)
     reg_loss = iou_cls(eps=1e-6, reduction='mean', loss_weight=1.0)
-    bb = backbone_cls(block_mode=arch['block_mode'], stem_mode=arch['stem_mode'], body_mode=None, input_channels=input_channels,
-                      stem_channels=arch['stem_channels'], body_architecture=list(arch['body_architecture']),
-                      body_channels=list(arch['body_channels']), out_indices=arch['out_indices'], frozen_stages=frozen_stages,
+    # (body_mode: only the PRESETS name one of the class's own body presets; the task scripts spell their bodies out)
+    bb = backbone_cls(block_mode=arch['block_mode'], stem_mode=arch['stem_mode'], body_mode=arch.get('body_mode'), input_channels=input_channels,
+                      stem_channels=arch['stem_channels'],
+                      body_architecture=None if arch.get('body_architecture') is None else list(arch['body_architecture']),
+                      body_channels=None if arch.get('body_channels') is None else list(arch['body_channels']),
+                      out_indices=arch['out_indices'], frozen_stages=frozen_stages,
                       activation_cfg=dict(type='ReLU', inplace=True), norm_cfg=dict(type='BatchNorm2d'),
                       init_with_weight_file=None, norm_eval=norm_eval)
     neck = neck_cls(num_neck_channels=arch['num_neck_channels'], num_input_channels_list=bb.num_output_channels_list,

@@ -40,13 +40,37 @@ def pad_channels(c):
     """The MFMA kernels are instantiated for 32 / 64 / 128 channels.  Any other width (TL_LFD_S: a 48-channel stem and first
     stage, TrafficLight_train/TL_LFD_S.py) runs zero-padded to the next one: padded output channels have zero weights and a
     zero bias, so they stay exactly 0 through ReLU / residual adds and meet zero weights in every consumer -- the real
-    channels are bit-identical to an unpadded evaluation.  3 and 1 (an RGB / a grayscale image) are left alone."""
+    channels are bit-identical to an unpadded evaluation.  3 and 1 (an RGB / a grayscale image) are left alone.
+    256 and 512 (the last stages of LFDResNet's own 'fast' / 'faster' body presets, lfd_resnet.py:222-231) are the widths of
+    csrc/conv_wide.hip: backbone convs of the 'fp16' mode only (require_narrow guards the fp32_storage plans; necks and
+    heads stay at 128)."""
     if c in (1, 3):
         return c
-    for a in (32, 64, 128):
+    for a in (32, 64, 128, 256, 512):
         if c <= a:
             return a
-    _unsupported('more than 128 channels')
+    _unsupported('more than 512 channels')
+
+
+def wide_conv(cin, cout, ks, stride):
+    """the (padded) layers conv_dispatch sends to csrc/conv_wide.hip -- everything above 128 channels and the four <= 128 layers
+    of FastBlock / FastestBlock bodies without an instance of conv_impl.h -- which has neither the chained-1x1 nor the
+    downsample-pair form: the plan launches those layers one by one"""
+    return cin > 128 or cout > 128 or (cin, cout, ks, stride) in ((64, 32, 3, 2), (64, 32, 1, 2), (32, 64, 3, 1), (32, 32, 1, 2))
+
+
+# (cin, cout) of the 3x3 stride-2 convs that carry their block's 1x1 stride-2 identity branch in the same launch
+# (lfd_conv2d_downsample_nhwc_f16): the pairs every shipped configuration has.  Other first blocks -- the wide ones, 64 -> 32 and
+# 32 -> 32 of a 'fastest' body -- launch the branch on its own.
+_DS_PAIRS = ((64, 64), (64, 128), (128, 128), (32, 64))
+
+
+def require_narrow(backbone, what):
+    """the plans without kernels above 128 channels (precision='fp32_storage') say so instead of running untested widths"""
+    for m in backbone.modules():
+        if isinstance(m, nn.Conv2d) and max(m.in_channels, m.out_channels) > 128:
+            _unsupported("more than 128 channels (conv %d -> %d) in %s: the 256 / 512-channel layers run in the 'fp16' mode only"
+                         % (m.in_channels, m.out_channels, what))
 
 
 def _pad_wb(w, b):
@@ -273,7 +297,8 @@ class EnginePlan(object):
                     c1 = blk._conv1
                     P = pad_channels
                     if (c1.kernel_size[0] == 3 and c1.stride[0] == 2 and c1.out_channels == dconv.out_channels and
-                            c1.in_channels == dconv.in_channels and blk.num_convs == 2):
+                            c1.in_channels == dconv.in_channels and blk.num_convs == 2 and
+                            (P(c1.in_channels), P(c1.out_channels)) in _DS_PAIRS):
                         # identity branch rides on the block's 3x3 stride-2 conv (one launch, one input read)
                         ident = new_buf()
                         self.buf_channels[ident] = P(dconv.out_channels)

@@ -255,6 +255,8 @@ class PlanesPlan(object):
             raise Unsupported('SimpleNeck + LFDHead')
         if bb._input_channels not in (1, 3) or (bb._norm_cfg is not None and bb._norm_cfg['type'] != 'BatchNorm2d'):
             raise Unsupported('backbone')
+        if any(isinstance(m, nn.Conv2d) and max(m.in_channels, m.out_channels) > 128 for m in bb.modules()):
+            raise Unsupported("more than 128 channels: the 256 / 512-channel layers run in the 'fp16' mode only")
         # the consumer kernels hard-wire ReLU (lfd_resnet.py / simple_neck.py / lfd_head.py build their activation from
         # activation_cfg): any other leaf module than conv / norm / ReLU / Scale falls back to the fp32-tensor plan's checks
         for part in (bb, neck, head):

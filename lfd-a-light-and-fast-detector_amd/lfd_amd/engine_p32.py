@@ -119,6 +119,7 @@ class PrecisePlan(object):
             engine._unsupported('input_channels not in (1, 3)')
         if bb._norm_cfg is not None and bb._norm_cfg['type'] != 'BatchNorm2d':
             engine._unsupported('backbone norm must be BatchNorm2d (or None)')
+        engine.require_narrow(bb, "precision='fp32_storage'")
         has_norm = bb._norm_cfg is not None
         step = 3 if has_norm else 2
         cur = 'input'

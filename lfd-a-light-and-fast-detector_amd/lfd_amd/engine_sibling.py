@@ -13,8 +13,8 @@ kernels).  The siblings are not used by any shipped config; they get the same ke
   extra levels         lfd_relu_inplace_f16, conv 3x3 s2 | lfd_maxpool3x3s2_nhwc_f16
   output convs         lfd_conv2d_nhwc_f16_acc32 (fp32 logits) + lfd_pack_level_outputs_f32 (Scale, exp, [N,P,C] concat)
 
-Inter-layer storage is NHWC fp16 like the LFD plan.  Widths: 32 / 64 / 128 channels (others zero-padded up, > 128
-rejected); GroupNorm with 8 channels per group (the kernels' group size: 128/16, 64/8).  No PyTorch fallback: an
+Inter-layer storage is NHWC fp16 like the LFD plan.  Widths: 32 / 64 / 128 channels (others zero-padded up); a backbone tap
+may have 256 or 512 channels (csrc/conv_wide.hip reads it), neck and head convs with more than 128 outputs are rejected; GroupNorm with 8 channels per group (the kernels' group size: 128/16, 64/8).  No PyTorch fallback: an
 unsupported module raises.
 """
 import torch
@@ -47,6 +47,8 @@ class _Conv(object):
         w, b = engine._fold_conv_norm(conv, bn)
         self.cout_real = w.shape[0]
         cout = engine.pad_channels(max(self.cout_real, 32))        # output convs have 1 .. 6 filters: one 32-wide MFMA tile
+        if cout > 128:          # the 256 / 512-channel kernels are the backbone's; a lateral conv READS such a tap (cin_have)
+            _unsupported('neck / head convs with more than 128 output channels (%d)' % self.cout_real)
         if f32out and cin_have == 128 and cout == 32:
             cout = 64                     # the 128-channel fp32-output kernels are instantiated for >= 64 outputs
         if self.gn is not None:

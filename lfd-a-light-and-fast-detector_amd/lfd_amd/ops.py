@@ -809,6 +809,13 @@ def zero_line(device):
     return z
 
 
+def conv2d_supported(cin, cout, ks, stride, tail=False):
+    """does lfd_conv2d_nhwc_f16 have a kernel for this layer (channels as the engine pads them)?  The dispatch of the real
+    call, nothing launched -- works without a device."""
+    d = _lib.ConvDesc(1, 8, 8, cin, cout, ks, stride, 1, cout if tail else 0, 1 if tail else 0)
+    return lib().lfd_conv2d_nhwc_f16_supported(C.byref(d)) == 0
+
+
 def conv2d_nhwc(x, w_packed, bias, cin, cout, ks, stride, relu, residual=None, tail=None, out=None):
     """x [N,H,W,cin] fp16 -> [N,OH,OW,cout] fp16.  tail = (w2_packed, bias2, relu2) chains a 1x1."""
     require_cuda(x, 'conv2d')
