@@ -7,7 +7,7 @@ across levels by aliasing head0's Sequentials (:67-82).  Child names, creation o
 N(0, 0.01) init (:151-162) follow the reference so checkpoints and seeds line up.
 
 Execution in training mode: behind a SimpleNeck inside the whole-network node (train_engine.network_supported); a GroupNorm
-head behind an FPN / SimpleFPN inside the detector node (train_engine.lfd_head_supported / LFDDetectorTrainFunction), which
+head behind an FPN / SimpleFPN inside the detector node (train_engine.lfd_head_supported / DetectorTrainFunction), which
 reads these modules' parameters; every other head: its children as PyTorch-ROCm modules under autograd (LFD._forward_train).
 """
 import torch

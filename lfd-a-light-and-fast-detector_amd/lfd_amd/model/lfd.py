@@ -278,7 +278,7 @@ class LFD(nn.Module):
         unsupported neck / head runs as its own node with PyTorch-ROCm modules behind it -- together with an FPN / SimpleFPN
         neck that train_engine.pyramid_supported admits (PyramidTrainFunction; LFD_HIP_NECK=0: the backbone alone), and with a
         GroupNorm LFDHead behind that neck that train_engine.lfd_head_supported admits as ONE node again
-        (LFDDetectorTrainFunction; LFD_HIP_HEAD=0: the pyramid node with the head under autograd).  LFD_HIP_TRAIN=0 or an
+        (DetectorTrainFunction; LFD_HIP_HEAD=0: the pyramid node with the head under autograd).  LFD_HIP_TRAIN=0 or an
         unsupported backbone: everything through PyTorch-ROCm autograd (same parameters, same semantics)."""
         neck, head = self._neck, self._head
         hip = x.is_cuda and os.environ.get('LFD_HIP_TRAIN', '1') != '0'

@@ -1,8 +1,17 @@
-"""Training-mode forward / backward of the LFDResNet backbone on the hand-written gfx950 kernels (SURVEY 8a
-row 18; csrc/train.hip + the MFMA conv of csrc/conv.hip), bridged into autograd as ONE node so that the torch
-modules after it (neck / head, not yet hand-written in training mode) and the loss drive it.
+"""Training-mode forward / backward on the hand-written gfx950 kernels (csrc/train.hip + the MFMA conv of
+csrc/conv.hip), bridged into autograd as ONE node per model that the loss (and whatever torch modules are left behind it) drives.
+Four nodes, each the widest one its model admits:
+    BackboneTrainFunction   the LFDResNet backbone alone (`supported`); neck and head stay PyTorch-ROCm modules under autograd
+    NetworkTrainFunction    backbone + SimpleNeck + LFDHead, the whole network (`network_supported`; level-concatenated head)
+    PyramidTrainFunction    backbone + FPN / SimpleFPN (`pyramid_supported`)
+    DetectorTrainFunction   that pyramid + FCOSHead or LFDHead (`fcos_head_supported` / `lfd_head_supported`): ONE plan class,
+                            forward, backward and Function for both heads; what is head-specific is the builder of the plan and a
+                            glue adapter around the output convs (_FCOSGlue: csrc/fcos_out.hip, _LFDGlue: csrc/lfd_out.hip)
+All of them run the same unit step (_unit_forward / _unit_backward), the same units-last-to-first loop (_units_backward) and the
+same two weight-gradient forms (_wgrad_accumulate: straight into the parameter's gradient; _wgrad_partials: partial sums into a
+persistent buffer, summed with all others of the iteration by one launch).
 
-Reference semantics: LFDResNet.forward in train mode (lfd/model/backbone/lfd_resnet.py:488-501) over
+Reference semantics of the backbone: LFDResNet.forward in train mode (lfd/model/backbone/lfd_resnet.py:488-501) over
 nn.Conv2d(bias=False) -> nn.BatchNorm2d (batch statistics, running statistics updated) -> ReLU units, residual
 blocks `relu(norm(conv(..)) + identity)` (:96-154), identity = norm(conv1x1 s2(x)) for the first block of a stage
 (:458-468).  Numerics here: NHWC fp16 activations / activation gradients (gradients carry a power-of-two loss
@@ -12,6 +21,7 @@ The backward is a hand-written schedule over the recorded units (no autograd ins
     g, dy = bn_bwd(dz)  ->  dW = wgrad(x, dy)  ->  dx = conv(dy, W^T flipped) (+ gradient already collected for x)
 """
 import collections
+import itertools
 import os
 
 import torch
@@ -54,7 +64,7 @@ def switches():
     environment at every call: the public entries call this once per pass and hand the record down.  `.hip_neck`
     (LFD_HIP_NECK, default on): FPN / SimpleFPN necks run inside the backbone's autograd node (PyramidTrainFunction); '0'
     restores the backbone node with the neck as PyTorch-ROCm modules under autograd.  `.hip_head` (LFD_HIP_HEAD, default on): an
-    FCOSHead or an LFDHead behind such a neck runs inside the same node (DetectorTrainFunction / LFDDetectorTrainFunction); '0'
+    FCOSHead or an LFDHead behind such a neck runs inside the same node (DetectorTrainFunction); '0'
     keeps the pyramid node with the head under autograd.  The head node sits on the pyramid node: LFD_HIP_NECK=0 turns both off."""
     sw = _Switches(
         conv_bn_stats=os.environ.get('LFD_CONV_BN_STATS', '1') == '1',           # conv, then a statistics pass over y
@@ -216,41 +226,48 @@ def build_units(backbone):
     return b.units, taps
 
 
+def _tower(b, path, cur):
+    """the (conv, norm, ReLU) triples of a head path as units from activation `cur` on -> the last activation (LFDHead's
+    classification / regression paths end in their output conv, which is no unit: it goes into an _Out record)"""
+    mods = list(path)
+    n3 = len(mods) - (1 if mods and isinstance(mods[-1], nn.Conv2d) else 0)
+    for i in range(0, n3, 3):
+        cur = b.add(mods[i], mods[i + 1], True, cur)
+    return cur
+
+
+def _out(level, convs, src, scale):
+    o = _Out()
+    o.level, o.convs, o.src, o.scale = level, convs, src, scale
+    return o
+
+
+def _lfd_head_level(b, head, i, src):
+    """LFDHead's level i on activation `src` (lfd_head.py:164-185): the merge path's units, the two towers' units -> the level's
+    _Out records: ONE (rows of both output convs) when they read the same activation, else two"""
+    cur = _tower(b, getattr(head, 'head%d_merge_path' % i), src)
+    cpath, rpath = getattr(head, 'head%d_classification_path' % i), getattr(head, 'head%d_regression_path' % i)
+    csrc, rsrc = _tower(b, cpath, cur), _tower(b, rpath, cur)
+    scale = head._scales[i] if hasattr(head, '_scales') else None
+    if csrc == rsrc:
+        return [_out(i, [('cls', cpath[-1]), ('reg', rpath[-1])], csrc, scale)]
+    return [_out(i, [('cls', cpath[-1])], csrc, scale), _out(i, [('reg', rpath[-1])], rsrc, scale)]
+
+
 def build_network(model):
     """-> (units, outs): backbone + neck + head towers as conv/norm/ReLU units, and the per-level output convs."""
     b = _Builder()
     taps = _build_backbone(b, model._backbone)
-    neck, head = model._neck, model._head
     outs = []
-
-    def tower(path, cur):
-        mods = list(path)
-        n3 = len(mods) - (1 if mods and isinstance(mods[-1], nn.Conv2d) else 0)
-        for i in range(0, n3, 3):
-            cur = b.add(mods[i], mods[i + 1], True, cur)
-        return cur
-
     for i, tap in enumerate(taps):
         b.level = i
-        nk = getattr(neck, 'neck%d' % i)
-        cur = b.add(nk[0], nk[1], True, tap)
-        cur = tower(getattr(head, 'head%d_merge_path' % i), cur)
-        cpath, rpath = getattr(head, 'head%d_classification_path' % i), getattr(head, 'head%d_regression_path' % i)
-        csrc, rsrc = tower(cpath, cur), tower(rpath, cur)
-        scale = head._scales[i] if hasattr(head, '_scales') else None
-        if csrc == rsrc:
-            o = _Out()
-            o.level, o.convs, o.src, o.scale = i, [('cls', cpath[-1]), ('reg', rpath[-1])], csrc, scale
-            outs.append(o)
-        else:
-            for kind, conv, src in (('cls', cpath[-1], csrc), ('reg', rpath[-1], rsrc)):
-                o = _Out()
-                o.level, o.convs, o.src, o.scale = i, [(kind, conv)], src, scale
-                outs.append(o)
+        nk = getattr(model._neck, 'neck%d' % i)
+        outs += _lfd_head_level(b, model._head, i, b.add(nk[0], nk[1], True, tap))
     return b.units, outs
 
 
 def _unique(params):
+    """the parameters (or modules) in their order, each object once"""
     seen, out = set(), []
     for p in params:
         if id(p) not in seen:
@@ -274,14 +291,20 @@ def dead_activations(units):
     return {0} | {u.dst for u in units if u.frozen}
 
 
-def network_params(units, outs):
-    ps = backbone_params(units)
+def _plan_params(base, units, outs):
+    """the parameters of a plan in the order its Function receives them: `base` (what the plan is built on), then the units'
+    that are not frozen, then per output record its convs' weight and bias and its Scale; every parameter once"""
+    ps = list(base) + backbone_params(units)
     for o in outs:
         for _, conv in o.convs:
             ps += [conv.weight, conv.bias]
         if o.scale is not None:
             ps.append(o.scale._scale)
     return _unique(ps)
+
+
+def network_params(units, outs):
+    return _plan_params((), units, outs)
 
 
 def _dgrad_weight(w):
@@ -336,7 +359,7 @@ class _EvalNorms(object):
 
     def run(self, units):
         self.rows, self.folded = {}, {}
-        norms = _unique_mods([u.norm for u in units if u.eval_norm])
+        norms = _unique([u.norm for u in units if u.eval_norm])
         if not norms:
             return self
         if self.rows_batch is None or not self.rows_batch.matches(norms):
@@ -352,15 +375,6 @@ class _EvalNorms(object):
             packed, biases = self.fold_batch.run(fresh)
             self.folded = {ui: (wp, b) for (ui, _), wp, b in zip(fz, packed, biases)}
         return self
-
-
-def _unique_mods(mods):
-    seen, out = set(), []
-    for m in mods:
-        if id(m) not in seen:
-            seen.add(id(m))
-            out.append(m)
-    return out
 
 
 def _eval_norms(owner, units):
@@ -508,7 +522,8 @@ _Fusions = collections.namedtuple('_Fusions', 'fed sum_rows')
 def _unit_backward(ui, u, dz, units, saved, grads, dead, store, packs, zeros, inv, sw, wgrad, fus=None, trace=None):
     """The backward of unit ui from dz = dL/d(its activation): norm backward, residual hand-off, weight gradient, data gradient
     (added to what `grads` holds for the unit's input; none for an input in `dead`).  The one unit backward of both schedules:
-    wgrad(xin, dy, ks, st, targets, producer) forms the conv's weight gradient (targets as ops.WgradFinals.add_wgrad);
+    wgrad(xin, dy, ks, st, inv, targets, producer) forms the conv's weight gradient (_wgrad_accumulate, or the whole-network
+    schedule's partial sums; targets as ops.WgradFinals.add_wgrad);
     fus: the _Fusions of the whole-network schedule, which also takes the first unit's one-launch shortcut and re-forms inputs
     that were never stored; trace: optional list that receives this unit's tensors."""
     acts, tape = saved
@@ -550,7 +565,7 @@ def _unit_backward(ui, u, dz, units, saved, grads, dead, store, packs, zeros, in
             pi = [i for i, p_ in enumerate(units) if p_.dst == u.src][0]
             producer = (units[pi], tape[pi])
             xin = tape[pi][0]
-        wgrad(xin, dy, conv.kernel_size[0], conv.stride[0], [(dw, 0, conv.out_channels)], producer)
+        wgrad(xin, dy, conv.kernel_size[0], conv.stride[0], inv, [(dw, 0, conv.out_channels)], producer)
         if u.src in dead:          # the input is a frozen activation: no data gradient
             pass
         elif fus is not None and ui in fus.fed and u.src not in grads:       # (a 1x1 stride-1 conv)
@@ -566,6 +581,25 @@ def _unit_backward(ui, u, dz, units, saved, grads, dead, store, packs, zeros, in
         trace.append(rec)
 
 
+def _wgrad_accumulate(xin, dy, ks, st, inv, targets, producer=None):
+    """the conv's weight gradient, formed now and added into its target (the parameter's gradient buffer)"""
+    ops.conv_wgrad(xin, dy, ks, st, inv, out=targets[0][0], accumulate=True)
+
+
+def _units_backward(units, order, saved, grads, dead, store, packs, zeros, inv, sw, trace=None):
+    """the backward of the units `order` (indices into `units`, last to first) whose activation has a gradient in `grads`: the
+    serial path of the backbone, of the pyramid neck's units and of the detector heads.  A missing gradient buffer is zero-filled
+    before the unit's first kernel (the whole-network schedule fills it where it is used)."""
+    for ui in order:
+        u = units[ui]
+        dz = grads.pop(u.dst, None)
+        if dz is None or u.frozen:
+            continue
+        for p in (u.norm.weight, u.norm.bias, u.conv.weight):
+            store.target(p)
+        _unit_backward(ui, u, dz, units, saved, grads, dead, store, packs, zeros, inv, sw, _wgrad_accumulate, trace=trace)
+
+
 def backward(units, saved, grads, scale=None, store=None, trace=None):
     """grads: {activation index: dL/dact NHWC fp16 multiplied by `scale`} for the activations consumed outside the units
     (taps for the backbone alone, tower outputs for the whole network).  -> _GradStore of fp32 parameter gradients.
@@ -578,19 +612,7 @@ def backward(units, saved, grads, scale=None, store=None, trace=None):
     store = store if store is not None else _GradStore()
     zeros = _Zeros(saved[0][0].device)
     packs = _Packs(units, True)
-    dead = dead_activations(units)
-
-    def wgrad(xin, dy, ks, st, targets, producer=None):
-        ops.conv_wgrad(xin, dy, ks, st, inv, out=targets[0][0], accumulate=True)
-
-    for ui in range(len(units) - 1, -1, -1):
-        u = units[ui]
-        dz = grads.pop(u.dst, None)
-        if dz is None or u.frozen:
-            continue
-        for p in (u.norm.weight, u.norm.bias, u.conv.weight):      # (this path zero-fills a missing gradient buffer before the
-            store.target(p)                                         #  unit's first kernel, the whole-network one where it is used)
-        _unit_backward(ui, u, dz, units, saved, grads, dead, store, packs, zeros, inv, sw, wgrad, trace=trace)
+    _units_backward(units, reversed(range(len(units))), saved, grads, dead_activations(units), store, packs, zeros, inv, sw, trace)
     return store
 
 
@@ -620,6 +642,17 @@ def _out_segs(o):
                          scale=o.scale._scale.detach() if (kind == 'reg' and o.scale is not None) else None))
         r0 += conv.out_channels
     return segs
+
+
+def out_row_ranges(o):
+    """[(conv, first row, end row)] of an output record's convs inside its padded conv"""
+    return [(sg['conv'], sg['row0'], sg['row0'] + sg['channels']) for sg in _out_segs(o)]
+
+
+def _out_targets(o, store):
+    """where the rows of the padded conv's weight gradient go (as ops.WgradFinals.add_wgrad takes them): a padded buffer never
+    reaches a parameter gradient"""
+    return [(store.target(cv.weight), lo, hi) for cv, lo, hi in out_row_ranges(o)]
 
 
 def _level_starts(sizes):
@@ -817,6 +850,21 @@ def _sched(plan_owner, dev):
     return sc
 
 
+def _wgrad_partials(sc, key, xin, dy, ks, st, inv, targets, producer=None):
+    """the per-workgroup partial sums of a conv's weight gradient into the conv's own persistent buffer sc.buf(key, ..); ONE
+    launch sums the partials of all convs registered this way (sc.finals.launch()) and routes their rows to `targets` (as
+    ops.WgradFinals.add_wgrad).  producer = (unit, (y, stats)): xin is that unit's pre-normalisation output, its activation was
+    never stored (_deferred_units)"""
+    floats, nwg, nblk = ops.conv_wgrad_partial_floats(xin, dy, ks, st)
+    part = sc.buf(key, floats)
+    if producer is not None:
+        pu, (_, pstats) = producer
+        ops.conv1x1_wgrad_partials_of_bn_relu(xin, pstats, pu.norm.weight.detach(), pu.norm.bias.detach(), dy, part)
+    else:
+        ops.conv_wgrad_partials(xin, dy, ks, st, part)
+    sc.finals.add_wgrad(part, nwg, nblk, xin.size(3), dy.size(3), ks * ks, inv, targets)
+
+
 def _out_packs(sc, outs, rows=None):
     """{ids of a level's output convs: (padded weight [rows, C, k, k], padded bias [rows], forward pack, data-gradient pack), rows
     64 or 128; k = 1 for LFDHead, 3 for FCOSHead}: the
@@ -1002,12 +1050,8 @@ def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, sw, full, sta
         else:
             for hw_, p0_, segs, grads_ in lv:
                 ops.head_out_grad_concat(y, hw_, segs, grads_, p0_, scale, dyo)
-        r0, targets = 0, []
-        for _, cv in o0.convs:
-            targets.append((store.target(cv.weight), r0, r0 + cv.out_channels))
-            r0 += cv.out_channels
         xin, dy4 = _as_image(A[sp]), _as_image(dyo)
-        wgrad(xin, dy4, 1, 1, targets)
+        wgrad(xin, dy4, 1, 1, inv, _out_targets(o0, store))
         c = xin.size(3)
         res = _as_image(dA[sp]) if dA[sp] is not None else None
         dA[sp] = ops.conv2d_nhwc(dy4, _out_pack(o0, opk)[3], zeros(c), wp.size(0), c, 1, 1, False, residual=res).view(n, ptot, c)
@@ -1022,7 +1066,7 @@ def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, sw, full, sta
         dA[p_] = None
         sp = cl['src_pos'][p_]
         xin, dy4 = _as_image(A[sp]), _as_image(dy)
-        wgrad(xin, dy4, 1, 1, [(store.target(conv.weight), 0, conv.out_channels)])
+        wgrad(xin, dy4, 1, 1, inv, [(store.target(conv.weight), 0, conv.out_channels)])
         cin = conv.in_channels
         res = _as_image(dA[sp]) if dA[sp] is not None else None
         dA[sp] = ops.conv2d_nhwc(dy4, packs(conv.weight, True), zeros(cin), conv.out_channels, cin, 1, 1, False,
@@ -1048,7 +1092,7 @@ def _concat_backward(cl, cs, units, acts, tape, packs, opk, zeros, sw, full, sta
             dA[0], starts[l], y, stats, norm.weight.detach(), norm.bias.detach(), inv, store.target(norm.weight),
             store.target(norm.bias), relu=True, accumulate=True)
         xin = acts[u.src]
-        wgrad(xin, dy, 1, 1, [(store.target(conv.weight), 0, conv.out_channels)])
+        wgrad(xin, dy, 1, 1, inv, [(store.target(conv.weight), 0, conv.out_channels)])
         cin = conv.in_channels
         if u.src in dead:
             continue
@@ -1168,27 +1212,13 @@ def network_backward(model, plan, saved, sizes, dcls, dreg, scale):
     dcls, dreg = dcls.contiguous(), dreg.contiguous()
     full = {'cls': dcls, 'reg': dreg}
     starts, _ = _level_starts(sizes)
-    nj = [0]
+    nj = itertools.count()
 
-    def wgrad(xin, dy, ks, st, targets, producer=None):
-        """the partial sums of dW into this conv's own buffer; `targets` as ops.WgradFinals.add_wgrad.  producer = (unit, (y,
-        stats)): xin is that unit's pre-normalisation output, its activation was never stored (_deferred_units)"""
-        floats, nwg, nblk = ops.conv_wgrad_partial_floats(xin, dy, ks, st)
-        part = sc.buf(('wg', nj[0]), floats)
-        nj[0] += 1
-        if producer is not None:
-            pu, (_, pstats) = producer
-            ops.conv1x1_wgrad_partials_of_bn_relu(xin, pstats, pu.norm.weight.detach(), pu.norm.bias.detach(), dy, part)
-        else:
-            ops.conv_wgrad_partials(xin, dy, ks, st, part)
-        fin.add_wgrad(part, nwg, nblk, xin.size(3), dy.size(3), ks * ks, inv, targets)
+    def wgrad(xin, dy, ks, st, inv, targets, producer=None):      # the schedule's j-th weight gradient: buffer ('wg', j)
+        _wgrad_partials(sc, ('wg', next(nj)), xin, dy, ks, st, inv, targets, producer)
 
     def out_wgrad(o, wp, xo, dy):
-        r0, targets = 0, []
-        for _, cv in o.convs:
-            targets.append((store.target(cv.weight), r0, r0 + cv.out_channels))
-            r0 += cv.out_channels
-        wgrad(xo, dy, 1, 1, targets)
+        wgrad(xo, dy, 1, 1, inv, _out_targets(o, store))
 
     grads = {}
     # stem pairs (_stem_pairs, adjacent units only: nothing else may touch the training workspace in between): the 1x1 conv's
@@ -1243,14 +1273,15 @@ class BackboneTrainFunction(torch.autograd.Function):
 
 class NetworkTrainFunction(torch.autograd.Function):
     """(cls [N,P,C'], reg [N,P,4]) = LFD.forward(x) in train mode as ONE autograd node: every conv / norm / ReLU of
-    backbone, neck and head runs forward and backward on the hand-written kernels (network_forward / network_backward)."""
+    backbone, neck and head runs forward and backward on the hand-written kernels (network_forward / network_backward).
+    sizes_out: the caller's list, which receives [(h, w)] per level."""
 
     @staticmethod
-    def forward(ctx, model, plan, x, *params):
+    def forward(ctx, model, plan, x, sizes_out, *params):
         cls, reg, sizes, saved = network_forward(model, plan, x)
         ctx.model, ctx.plan, ctx.saved, ctx.sizes = model, plan, saved, sizes
         ctx.shapes = (cls.shape, reg.shape)
-        NetworkTrainFunction.last_sizes = sizes
+        sizes_out.extend(sizes)
         return cls, reg
 
     @staticmethod
@@ -1263,7 +1294,7 @@ class NetworkTrainFunction(torch.autograd.Function):
             dreg = torch.zeros(ctx.shapes[1], dtype=torch.float32, device=dev)
         network_backward(ctx.model, ctx.plan, ctx.saved, ctx.sizes, dcls, dreg, loss_scale())
         ctx.saved = None
-        return (None, None, None) + (None,) * len(network_params(units, outs))   # accumulated into .grad directly
+        return (None,) * (4 + len(network_params(units, outs)))   # accumulated into .grad directly
 
 
 def backbone_train_forward(backbone, x):
@@ -1283,8 +1314,9 @@ def network_train_forward(model, x):
         units, outs = build_network(model)
         plan = (units, outs, model._num_heads)
         model.__dict__['_lfd_train_plan'] = plan
-    cls, reg = NetworkTrainFunction.apply(model, plan, x, *network_params(plan[0], plan[1]))
-    return cls, reg, NetworkTrainFunction.last_sizes
+    sizes = []
+    cls, reg = NetworkTrainFunction.apply(model, plan, x, sizes, *network_params(plan[0], plan[1]))
+    return cls, reg, sizes
 
 
 # ---------------------------------------------------------------------------------------------- backbone + pyramid neck
@@ -1461,18 +1493,9 @@ def pyramid_backward(plan, saved, grads, scale=None, store=None):
     dead = dead_activations(plan.units)
     relu_made = {a[1] for kind, *a in plan.steps if kind == 'relu'}
     side = {}          # {ReLU'd activation: the gradient of the extra level behind it}: joined with the head's by the ReLU backward
-
-    def wgrad(xin, dy, ks, st, targets, producer=None):
-        ops.conv_wgrad(xin, dy, ks, st, inv, out=targets[0][0], accumulate=True)
-
     for kind, *a in reversed(plan.steps):
         if kind == 'unit':
-            ui, u = a[0], plan.units[a[0]]
-            dz = grads.pop(u.dst, None)
-            if dz is not None:
-                for p_ in (u.norm.weight, u.norm.bias, u.conv.weight):
-                    store.target(p_)
-                _unit_backward(ui, u, dz, plan.units, saved, grads, dead, store, packs, zeros, inv, sw, wgrad)
+            _units_backward(plan.units, a, saved, grads, dead, store, packs, zeros, inv, sw)       # (a: [the unit's index])
         elif kind == 'conv':
             nc, cv = a[0], a[0].conv
             dz = grads.pop(nc.dst, None)
@@ -1482,7 +1505,7 @@ def pyramid_backward(plan, saved, grads, scale=None, store=None):
                 dz = ops.relu_backward_add(acts[nc.dst], dz)
             xin = acts[nc.src]
             ops.bias_grad_(dz, inv, store.target(cv.bias))
-            wgrad(xin, dz, cv.kernel_size[0], cv.stride[0], [(store.target(cv.weight), 0, cv.out_channels)])
+            _wgrad_accumulate(xin, dz, cv.kernel_size[0], cv.stride[0], inv, [(store.target(cv.weight), 0, cv.out_channels)])
             if nc.src in dead:
                 continue
             prev = None if nc.src in relu_made else grads.get(nc.src)
@@ -1556,8 +1579,38 @@ def _pyramid_plan(backbone, neck):
     return plan
 
 
-# ---------------------------------------------------------------------------------------------- backbone + pyramid neck + FCOSHead
-# FCOSHead (lfd/model/head/fcos_head.py:20-154) behind the pyramid node, in the SAME autograd node: two towers of 3x3 conv ->
+# ---------------------------------------------------------------------------------------------- backbone + pyramid neck + head
+# The detector node: an FCOSHead or an LFDHead behind the pyramid node, in the SAME autograd node.  One plan class, one forward,
+# one backward, one Function (at the end of this file); a head brings its `*_head_supported`, the builder of its plan and its
+# glue adapter: pack(plan, starts, raws, full) from the output convs' fp32 outputs into the node's level-concatenated outputs
+# (-> what its backward keeps), grad(plan, starts, kept, read, dfull, dys, store, scale) back from the outputs' gradients to the
+# convs' fp16 output gradients, the bias and the Scale gradients.
+class _DetectorPlan(object):
+    """The plan of the detector node, for both heads.  pyramid: the _PyramidPlan; units: the head's units of all levels (their own
+    list: tape indices are positions in it, activation indices go on from the pyramid's); outs: the levels' _Out records in
+    forward order; rows: the row count every output conv is padded to; ks: the output convs' kernel size; widths: {kind: channels}
+    of the node's output tensors, in the order it returns them; glue: the adapter around the output convs (_FCOSGlue / _LFDGlue)"""
+    __slots__ = ('pyramid', 'units', 'outs', 'rows', 'ks', 'widths', 'params', 'head', 'glue')
+
+
+def _build_detector(backbone, neck, head, glue, ks, widths, level):
+    """-> _DetectorPlan on the pyramid plan; level(b, i, src) adds the head's units of level i on the neck's output `src` to the
+    builder and -> the level's _Out records"""
+    pp = _pyramid_plan(backbone, neck)
+    b = _Builder()
+    b.n_act = pp.n_act
+    d = _DetectorPlan()
+    d.pyramid, d.outs, d.head, d.glue, d.ks, d.widths = pp, [], head, glue, ks, widths
+    for i, src in enumerate(pp.out_ids):
+        b.level = i
+        d.outs += level(b, i, src)
+    d.units = b.units
+    d.rows = max(-(-sum(cv.out_channels for _, cv in o.convs) // 64) * 64 for o in d.outs)
+    d.params = _plan_params(pp.params, d.units, d.outs)
+    return d
+
+
+# ---- FCOSHead (lfd/model/head/fcos_head.py:20-154): two towers of 3x3 conv ->
 # GroupNorm -> ReLU units shared by all levels (through _unit_forward / _unit_backward: shared weights are packed once, every
 # parameter gradient accumulates over the levels), then per level two output convs padded to FCOS_OUT_ROWS rows with fp32
 # outputs (ops.conv2d_nhwc_f32out) -- rows [0, C) `_classification` and row C `_centerness` on the classification tower, rows
@@ -1574,7 +1627,7 @@ def fcos_head_supported(backbone, neck, head):
     num_classes + 1 <= FCOS_OUT_ROWS (classification and centerness share one padded conv).  NOT admitted -- these keep the
     pyramid node with the head under PyTorch-ROCm autograd: norm_cfg=None, BatchNorm towers (a BatchNorm shared by the levels
     updates its running statistics level after level: its own piece of work), num_layers == 0 and more classes.  (An LFDHead
-    behind such a neck has its own node: lfd_head_supported; LFDHeadV1 has none.)"""
+    behind such a neck enters the same node through lfd_head_supported; LFDHeadV1 has none.)"""
     if type(head).__name__ != 'FCOSHead' or not head.training:
         return False
     if not pyramid_supported(backbone, neck) or len(head._scales) != neck._num_outputs:
@@ -1593,185 +1646,46 @@ def fcos_head_supported(backbone, neck, head):
     return head._num_classes + 1 <= FCOS_OUT_ROWS
 
 
-class _DetectorPlan(object):
-    """pyramid: the _PyramidPlan; units: the head's tower units (their own list: tape indices are positions in it, activation
-    indices go on from the pyramid's); outs: per level two _Out records, (cls + ctr) then (reg, with the level's Scale)"""
-    __slots__ = ('pyramid', 'units', 'outs', 'rows', 'num_classes', 'params', 'head')
-
-
-def out_row_ranges(o):
-    """[(conv, first row, end row)] of an output record's convs inside its padded conv"""
-    return [(sg['conv'], sg['row0'], sg['row0'] + sg['channels']) for sg in _out_segs(o)]
-
-
 def build_detector(backbone, neck, head):
-    """-> _DetectorPlan: the pyramid plan, then per level, in FCOSHead.forward's order (fcos_head.py:129-150), the classification
-    tower's units, the regression tower's units and the two output records"""
-    pp = _pyramid_plan(backbone, neck)
-    b = _Builder()
-    b.n_act = pp.n_act
-    d = _DetectorPlan()
-    d.pyramid, d.outs, d.rows, d.num_classes, d.head = pp, [], FCOS_OUT_ROWS, head._num_classes, head
+    """-> _DetectorPlan of an FCOSHead: per level, in FCOSHead.forward's order (fcos_head.py:129-150), the classification tower's
+    units, the regression tower's units and two output records, (cls + ctr) then (reg, with the level's Scale); 3x3 output convs
+    of FCOS_OUT_ROWS rows (what fcos_head_supported admits fits them)"""
+    def level(b, i, src):
+        csrc, rsrc = _tower(b, head._classification_path, src), _tower(b, head._regression_path, src)
+        return [_out(i, [('cls', head._classification), ('ctr', head._centerness)], csrc, None),
+                _out(i, [('reg', head._regression)], rsrc, head._scales[i])]
 
-    def tower(path, cur):
-        mods = list(path)
-        for i in range(0, len(mods), 3):          # (conv, norm, ReLU) triples
-            cur = b.add(mods[i], mods[i + 1], True, cur)
-        return cur
-
-    for i, src in enumerate(pp.out_ids):
-        b.level = i
-        csrc, rsrc = tower(head._classification_path, src), tower(head._regression_path, src)
-        for convs, s, scale in (([('cls', head._classification), ('ctr', head._centerness)], csrc, None),
-                                ([('reg', head._regression)], rsrc, head._scales[i])):
-            o = _Out()
-            o.level, o.convs, o.src, o.scale = i, convs, s, scale
-            d.outs.append(o)
-    d.units = b.units
-    ps = list(pp.params)
-    for u in d.units:
-        ps += [u.conv.weight, u.norm.weight, u.norm.bias]
-    for o in d.outs:
-        for _, conv in o.convs:
-            ps += [conv.weight, conv.bias]
-        if o.scale is not None:
-            ps.append(o.scale._scale)
-    d.params = _unique(ps)
-    return d
+    return _build_detector(backbone, neck, head, _FCOSGlue, 3, dict(cls=head._num_classes, reg=4, ctr=1), level)
 
 
-def detector_forward(plan, x):
-    """-> (cls [N,P,C], reg [N,P,4], ctr [N,P,1] fp32, [(h, w)] per level, saved)"""
-    sw = switches()
-    pp = plan.pyramid
-    feats, (acts, tape) = pyramid_forward(pp, x)
-    dev = x.device
-    n = x.size(0)
-    zeros = _Zeros(dev)
-    packs = _Packs(plan.units, False)
-    htape = [_unit_forward(ui, u, acts, packs, zeros, sw) for ui, u in enumerate(plan.units)]
-    sizes = [tuple(f.shape[1:3]) for f in feats]
-    starts, p = _level_starts(sizes)
-    opk = _out_packs(_sched(plan.head, dev), plan.outs)
-    raws = {}
-    for o in plan.outs:
-        wp, bp, wpk, _ = _out_pack(o, opk)
-        xin = acts[o.src]
-        raws[(o.level, o.convs[0][0])] = ops.conv2d_nhwc_f32out(xin, wpk, bp, xin.size(3), wp.size(0), 3, 1)
-    cls = torch.empty((n, p, plan.num_classes), dtype=torch.float32, device=dev)
-    reg = torch.empty((n, p, 4), dtype=torch.float32, device=dev)
-    ctr = torch.empty((n, p, 1), dtype=torch.float32, device=dev)
-    scales = {o.level: o.scale._scale.detach() for o in plan.outs if o.scale is not None}
-    ops.fcos_out_pack_levels([dict(raw_cls=raws[(l, 'cls')], raw_reg=raws[(l, 'reg')], scale=scales[l], point0=starts[l])
-                              for l in range(len(sizes))], cls, reg, ctr)
-    raw_reg = [raws[(l, 'reg')] for l in range(len(sizes))]
-    return cls, reg, ctr, sizes, ((acts, tape), htape, opk, raw_reg, starts)
-
-
-def _head_tail_backward(plan, saved, htape, opk, dys, ks, store, sc, packs, zeros, dead, scale, sw):
-    """what the backward of both detector nodes does behind the output-conv glue: from dys[j], the fp16 output gradient of
-    plan.outs[j]'s padded ks x ks conv, that conv's weight gradient (partial sums into its own buffer, its rows routed to the
-    parameters they belong to by ONE final launch: a padded buffer never reaches a parameter gradient) and data gradient (chains
-    ending in the same activation take the earlier gradient as the conv kernel's residual), the head's units last to first, then
-    pyramid_backward with the gradients collected at the neck's outputs"""
-    pp = plan.pyramid
-    acts, tape = saved
-    inv = 1.0 / scale
-    fin = sc.finals
-    grads = {}
-    for j, o in enumerate(plan.outs):
-        wp = _out_pack(o, opk)
-        xin, dy = acts[o.src], dys[j]
-        floats, nwg, nblk = ops.conv_wgrad_partial_floats(xin, dy, ks, 1)
-        part = sc.buf(('wg', j), floats)
-        ops.conv_wgrad_partials(xin, dy, ks, 1, part)
-        fin.add_wgrad(part, nwg, nblk, xin.size(3), dy.size(3), ks * ks, inv,
-                      [(store.target(cv.weight), lo, hi) for cv, lo, hi in out_row_ranges(o)])
-        c = xin.size(3)
-        grads[o.src] = ops.conv2d_nhwc(dy, wp[3], zeros(c), wp[0].size(0), c, ks, 1, False, residual=grads.get(o.src))
-    fin.launch()
-
-    def wgrad(xin, dy, ks_, st, targets, producer=None):
-        ops.conv_wgrad(xin, dy, ks_, st, inv, out=targets[0][0], accumulate=True)
-
-    for ui in range(len(plan.units) - 1, -1, -1):
-        u = plan.units[ui]
-        dz = grads.pop(u.dst, None)
-        if dz is None:
-            continue
-        for p_ in (u.norm.weight, u.norm.bias, u.conv.weight):
-            store.target(p_)
-        _unit_backward(ui, u, dz, plan.units, (acts, htape), grads, dead, store, packs, zeros, inv, sw, wgrad)
-    pyramid_backward(pp, (acts, tape), {o: grads[o] for o in pp.out_ids if o in grads}, scale=scale, store=store)
-
-
-def detector_backward(plan, saved, reg, dcls, dreg, dctr, scale):
-    """the backward of detector_forward: output-conv glue (+ the bias / Scale finals), the output convs' weight and data
-    gradients, the tower units last to first, then pyramid_backward with the gradients collected at the neck's outputs.
-    Parameter gradients accumulate into `.grad` (created zeroed when missing)."""
-    sw = switches()
-    pp, head = plan.pyramid, plan.head
-    (acts, tape), htape, opk, raw_reg, starts = saved
-    dev = dcls.device
-    store = _GradStore(in_place=True)
-    sc = _sched(head, dev)
-    sc.finals.reset()
-    zeros = _Zeros(dev)
-    packs = _Packs(plan.units, True)
-    dead = dead_activations(pp.units)
-    dys, levels = {}, []
-    for o in plan.outs:
-        if o.scale is None:
-            continue
-        l = o.level
-        dys[(l, 'cls')], dys[(l, 'reg')] = (torch.empty(raw_reg[l].shape, dtype=torch.float16, device=dev) for _ in range(2))
-        levels.append(dict(raw_reg=raw_reg[l], scale=o.scale._scale.detach(), point0=starts[l], dscale=store.target(o.scale._scale),
-                           dy_cls=dys[(l, 'cls')], dy_reg=dys[(l, 'reg')]))
-    ops.fcos_out_grad_levels(levels, dcls.contiguous(), dreg.contiguous(), dctr.contiguous(), reg, scale,
-                             store.target(head._classification.bias), store.target(head._centerness.bias),
-                             store.target(head._regression.bias))
-    _head_tail_backward(plan, (acts, tape), htape, opk, [dys[(o.level, o.convs[0][0])] for o in plan.outs], 3, store, sc, packs,
-                        zeros, dead, scale, sw)
-
-
-class DetectorTrainFunction(torch.autograd.Function):
-    """(cls [N,P,C], reg [N,P,4], ctr [N,P,1]) = FCOS.forward(x) in train mode as ONE autograd node: backbone, pyramid neck and
-    FCOSHead forward and backward on the hand-written kernels (detector_forward / detector_backward)."""
+class _FCOSGlue(object):
+    """csrc/fcos_out.hip on both sides of FCOSHead's output convs: rows [0, C) `_classification` and row C `_centerness` of the
+    classification tower's conv, rows [0, 4) `_regression` of the regression tower's; reg = expf(raw * Scale_i)"""
+    reads = ('reg',)         # the node's outputs the backward reads
 
     @staticmethod
-    def forward(ctx, plan, x, *params):
-        cls, reg, ctr, sizes, saved = detector_forward(plan, x)
-        ctx.plan, ctx.saved = plan, saved
-        ctx.save_for_backward(reg)
-        DetectorTrainFunction.last_sizes = sizes
-        return cls, reg, ctr
+    def pack(plan, starts, raws, full):
+        """raws[j]: the fp32 output of plan.outs[j]'s conv -> what the backward keeps: the levels' raw regression outputs"""
+        raw_cls, raw_reg = raws[0::2], raws[1::2]
+        ops.fcos_out_pack_levels([dict(raw_cls=raw_cls[l], raw_reg=raw_reg[l], scale=plan.outs[2 * l + 1].scale._scale.detach(),
+                                       point0=starts[l]) for l in range(len(starts))], full['cls'], full['reg'], full['ctr'])
+        return raw_reg
 
     @staticmethod
-    def backward(ctx, dcls, dreg, dctr):
-        reg, = ctx.saved_tensors
-        n, p = reg.shape[:2]
-        zero = lambda c: torch.zeros((n, p, c), dtype=torch.float32, device=reg.device)         # noqa: E731
-        dcls = zero(ctx.plan.num_classes) if dcls is None else dcls
-        dreg = zero(4) if dreg is None else dreg
-        dctr = zero(1) if dctr is None else dctr
-        detector_backward(ctx.plan, ctx.saved, reg.detach(), dcls, dreg, dctr, loss_scale())
-        ctx.saved = None
-        return (None, None) + (None,) * len(ctx.plan.params)     # gradients were accumulated into .grad directly
+    def grad(plan, starts, raw_reg, read, dfull, dys, store, scale):
+        """dfull: the gradients of the node's outputs; writes dys[j], the fp16 output gradient of plan.outs[j]'s conv, and
+        accumulates the bias and Scale gradients; read: {kind: the node's output} for the kinds in `reads`"""
+        head = plan.head
+        levels = []
+        for l, o in enumerate(plan.outs[1::2]):
+            levels.append(dict(raw_reg=raw_reg[l], scale=o.scale._scale.detach(), point0=starts[l], dscale=store.target(o.scale._scale),
+                               dy_cls=dys[2 * l], dy_reg=dys[2 * l + 1]))
+        ops.fcos_out_grad_levels(levels, dfull['cls'].contiguous(), dfull['reg'].contiguous(), dfull['ctr'].contiguous(), read['reg'],
+                                 scale, store.target(head._classification.bias), store.target(head._centerness.bias),
+                                 store.target(head._regression.bias))
 
 
-def detector_train_forward(backbone, neck, head, x):
-    """-> (cls, reg, ctr, [(h, w)] per level)"""
-    check_train_input(backbone, x)
-    plan = head.__dict__.get('_lfd_detector_plan')
-    if plan is None or plan.pyramid is not neck.__dict__.get('_lfd_pyramid_plan') or plan.pyramid.owner is not backbone:
-        plan = build_detector(backbone, neck, head)
-        head.__dict__['_lfd_detector_plan'] = plan
-    cls, reg, ctr = DetectorTrainFunction.apply(plan, x, *plan.params)
-    return cls, reg, ctr, DetectorTrainFunction.last_sizes
-
-
-# ---------------------------------------------------------------------------------------------- backbone + pyramid neck + LFDHead
-# LFDHead (lfd/model/head/lfd_head.py:30-185) behind the pyramid node, in the SAME autograd node, level by level: the merge path's
+# ---- LFDHead (lfd/model/head/lfd_head.py:30-185), level by level: the merge path's
 # units, then the classification and regression towers' units (1x1 or 3x3 conv -> GroupNorm -> ReLU through _unit_forward /
 # _unit_backward; modules shared by the levels are packed once and their gradients accumulate over the levels), then the level's
 # output convs as build_network forms them -- ONE 1x1 conv with the rows of both when they read the same activation, else two --
@@ -1780,7 +1694,7 @@ def detector_train_forward(backbone, neck, head, x):
 # loss applies `exp` where distance_to_bbox_mode asks for it).  A 3x3 head runs here although the level-concatenated schedule
 # of network_forward cannot take it: every level keeps its own map.
 def lfd_head_supported(backbone, neck, head):
-    """backbone + neck + head as one node (LFDDetectorTrainFunction): pyramid_supported(backbone, neck) and a training-mode LFDHead
+    """backbone + neck + head as one node (DetectorTrainFunction): pyramid_supported(backbone, neck) and a training-mode LFDHead
     with one head per neck output, 64 or 128 input (= the neck's output) and head channels, 1x1 or 3x3 tower convs, any number of
     tower layers (0: the output convs read the neck's outputs), ReLU, affine GroupNorm in groups of 8 channels, every parameter
     taking a gradient, a Scale per level exactly when the regression loss is of the IoU family, shared or per-level towers, merged
@@ -1814,62 +1728,17 @@ def lfd_head_supported(backbone, neck, head):
     return head.num_cls_channels + (4 if one_conv else 0) <= 128
 
 
-class _LFDDetectorPlan(object):
-    """pyramid: the _PyramidPlan; units: the head's units of all levels (their own list: tape indices are positions in it,
-    activation indices go on from the pyramid's); outs: per level one _Out record (cls + reg on the same activation) or two;
-    rows: the row count every output conv is padded to"""
-    __slots__ = ('pyramid', 'units', 'outs', 'rows', 'cls_channels', 'params', 'head')
-
-
 def build_lfd_detector(backbone, neck, head):
-    """-> _LFDDetectorPlan: the pyramid plan, then per level, in LFD._forward_train's order (lfd.py:526-542), the merge path's
-    units, the two towers' units and the output records exactly as build_network forms them"""
-    pp = _pyramid_plan(backbone, neck)
-    b = _Builder()
-    b.n_act = pp.n_act
-    d = _LFDDetectorPlan()
-    d.pyramid, d.outs, d.cls_channels, d.head = pp, [], head.num_cls_channels, head
-
-    def tower(path, cur):
-        mods = list(path)
-        n3 = len(mods) - (1 if mods and isinstance(mods[-1], nn.Conv2d) else 0)
-        for i in range(0, n3, 3):          # (conv, norm, ReLU) triples; the path's last module is its output conv
-            cur = b.add(mods[i], mods[i + 1], True, cur)
-        return cur
-
-    for i, src in enumerate(pp.out_ids):
-        b.level = i
-        cur = tower(getattr(head, 'head%d_merge_path' % i), src)
-        cpath, rpath = getattr(head, 'head%d_classification_path' % i), getattr(head, 'head%d_regression_path' % i)
-        csrc, rsrc = tower(cpath, cur), tower(rpath, cur)
-        scale = head._scales[i] if hasattr(head, '_scales') else None
-        if csrc == rsrc:
-            o = _Out()
-            o.level, o.convs, o.src, o.scale = i, [('cls', cpath[-1]), ('reg', rpath[-1])], csrc, scale
-            d.outs.append(o)
-        else:
-            for kind, conv, s in (('cls', cpath[-1], csrc), ('reg', rpath[-1], rsrc)):
-                o = _Out()
-                o.level, o.convs, o.src, o.scale = i, [(kind, conv)], s, scale
-                d.outs.append(o)
-    d.units = b.units
-    d.rows = max(-(-sum(cv.out_channels for _, cv in o.convs) // 64) * 64 for o in d.outs)
-    ps = list(pp.params)
-    for u in d.units:
-        ps += [u.conv.weight, u.norm.weight, u.norm.bias]
-    for o in d.outs:
-        for _, conv in o.convs:
-            ps += [conv.weight, conv.bias]
-        if o.scale is not None:
-            ps.append(o.scale._scale)
-    d.params = _unique(ps)
-    return d
+    """-> _DetectorPlan of an LFDHead: per level, in LFD._forward_train's order (lfd.py:526-542), the merge path's units, the two
+    towers' units and the output records exactly as build_network forms them; 1x1 output convs of 64 or 128 rows"""
+    return _build_detector(backbone, neck, head, _LFDGlue, 1, dict(cls=head.num_cls_channels, reg=4),
+                           lambda b, i, src: _lfd_head_level(b, head, i, src))
 
 
-def _lfd_out_levels(plan, nlev, starts, raws, dys=None, store=None):
+def _lfd_out_levels(plan, starts, raws, dys=None, store=None):
     """the level records of ops.lfdhead_out_pack_levels (raws: {index into plan.outs: the conv's fp32 output}) and, with dys (per
     plan.outs record) and the gradient store, of ops.lfdhead_out_grad_levels"""
-    levels = [dict(point0=starts[l], convs=[], scale=None) for l in range(nlev)]
+    levels = [dict(point0=p0, convs=[], scale=None) for p0 in starts]
     for j, o in enumerate(plan.outs):
         lv = levels[o.level]
         cv = dict(raw=raws.get(j), segs=[dict(kind=sg['kind'], row0=sg['row0'], channels=sg['channels']) for sg in _out_segs(o)])
@@ -1885,84 +1754,111 @@ def _lfd_out_levels(plan, nlev, starts, raws, dys=None, store=None):
     return levels
 
 
-def lfd_detector_forward(plan, x):
-    """-> (cls [N,P,C'], reg [N,P,4] fp32, [(h, w)] per level, saved)"""
+class _LFDGlue(object):
+    """csrc/lfd_out.hip on both sides of LFDHead's output convs (one conv per level with the rows of both, or two): cls a copy of
+    the classification rows, reg = raw * Scale_i (a copy without a Scale)"""
+    reads = ()
+
+    @staticmethod
+    def pack(plan, starts, raws, full):
+        ops.lfdhead_out_pack_levels(_lfd_out_levels(plan, starts, dict(enumerate(raws))), full['cls'], full['reg'])
+        # the backward reads a raw output for the Scale gradient alone: the conv that holds a Scale'd level's regression rows
+        return {j: raws[j] for j, o in enumerate(plan.outs) if o.scale is not None and any(k == 'reg' for k, _ in o.convs)}
+
+    @staticmethod
+    def grad(plan, starts, keep, read, dfull, dys, store, scale):
+        ops.lfdhead_out_grad_levels(_lfd_out_levels(plan, starts, keep, dys, store), dfull['cls'].contiguous(), dfull['reg'].contiguous(),
+                                    scale)
+
+
+# ---- the node of both heads
+def detector_forward(plan, x):
+    """-> ({kind: [N,P,width] fp32} in plan.widths' order, [(h, w)] per level, saved): FCOS.forward / LFD.forward in train mode"""
     sw = switches()
-    pp = plan.pyramid
-    feats, (acts, tape) = pyramid_forward(pp, x)
+    feats, (acts, tape) = pyramid_forward(plan.pyramid, x)
     dev = x.device
-    n = x.size(0)
     zeros = _Zeros(dev)
     packs = _Packs(plan.units, False)
     htape = [_unit_forward(ui, u, acts, packs, zeros, sw) for ui, u in enumerate(plan.units)]
     sizes = [tuple(f.shape[1:3]) for f in feats]
     starts, p = _level_starts(sizes)
     opk = _out_packs(_sched(plan.head, dev), plan.outs, plan.rows)
-    raws = {}
-    for j, o in enumerate(plan.outs):
+    raws = []
+    for o in plan.outs:
         wp, bp, wpk, _ = _out_pack(o, opk)
         xin = acts[o.src]
-        raws[j] = ops.conv2d_nhwc_f32out(xin, wpk, bp, xin.size(3), wp.size(0), 1, 1)
-    cls = torch.empty((n, p, plan.cls_channels), dtype=torch.float32, device=dev)
-    reg = torch.empty((n, p, 4), dtype=torch.float32, device=dev)
-    ops.lfdhead_out_pack_levels(_lfd_out_levels(plan, len(sizes), starts, raws), cls, reg)
-    # the backward reads a raw output for the Scale gradient alone: the conv that holds a Scale'd level's regression rows
-    keep = {j: raws[j] for j, o in enumerate(plan.outs) if o.scale is not None and any(k == 'reg' for k, _ in o.convs)}
-    return cls, reg, sizes, ((acts, tape), htape, opk, keep, starts, sizes)
+        raws.append(ops.conv2d_nhwc_f32out(xin, wpk, bp, xin.size(3), wp.size(0), plan.ks, 1))
+    full = {k: torch.empty((x.size(0), p, c), dtype=torch.float32, device=dev) for k, c in plan.widths.items()}
+    kept = plan.glue.pack(plan, starts, raws, full)
+    return full, sizes, ((acts, tape), htape, opk, kept, starts, sizes)
 
 
-def lfd_detector_backward(plan, saved, dcls, dreg, scale):
-    """the backward of lfd_detector_forward: output-conv glue (+ the bias / Scale finals), the output convs' weight and data
-    gradients (chains ending in the same activation take the earlier gradient as residual), the units last to first, then
-    pyramid_backward with the gradients collected at the neck's outputs.  Parameter gradients accumulate into `.grad` (created
-    zeroed when missing)."""
+def detector_backward(plan, saved, read, dfull, scale):
+    """the backward of detector_forward from dfull = {kind: gradient of that output}: the output-conv glue (+ the bias / Scale
+    finals), the output convs' weight gradients (partial sums, their rows routed to the parameters by ONE final launch) and data
+    gradients (chains ending in the same activation take the earlier gradient as the conv kernel's residual), the head's units
+    last to first, then pyramid_backward with the gradients collected at the neck's outputs.  Parameter gradients accumulate into
+    `.grad` (created zeroed when missing)."""
     sw = switches()
-    pp, head = plan.pyramid, plan.head
-    (acts, tape), htape, opk, raws, starts, sizes = saved
-    dev = dcls.device
-    n = dcls.size(0)
+    pp, ks = plan.pyramid, plan.ks
+    (acts, tape), htape, opk, kept, starts, sizes = saved
+    dev = acts[0].device
+    inv = 1.0 / scale
     store = _GradStore(in_place=True)
-    sc = _sched(head, dev)
+    sc = _sched(plan.head, dev)
     sc.finals.reset()
     zeros = _Zeros(dev)
     packs = _Packs(plan.units, True)
     dead = dead_activations(pp.units)
-    dys = [torch.empty((n,) + sizes[o.level] + (plan.rows,), dtype=torch.float16, device=dev) for o in plan.outs]
-    ops.lfdhead_out_grad_levels(_lfd_out_levels(plan, len(sizes), starts, raws, dys, store), dcls.contiguous(), dreg.contiguous(), scale)
-    _head_tail_backward(plan, (acts, tape), htape, opk, dys, 1, store, sc, packs, zeros, dead, scale, sw)
+    dys = [torch.empty((acts[0].size(0),) + sizes[o.level] + (plan.rows,), dtype=torch.float16, device=dev) for o in plan.outs]
+    plan.glue.grad(plan, starts, kept, read, dfull, dys, store, scale)
+    grads = {}
+    for j, o in enumerate(plan.outs):
+        wp = _out_pack(o, opk)
+        xin, dy = acts[o.src], dys[j]
+        _wgrad_partials(sc, ('wg', j), xin, dy, ks, 1, inv, _out_targets(o, store))
+        c = xin.size(3)
+        grads[o.src] = ops.conv2d_nhwc(dy, wp[3], zeros(c), wp[0].size(0), c, ks, 1, False, residual=grads.get(o.src))
+    sc.finals.launch()
+    _units_backward(plan.units, reversed(range(len(plan.units))), (acts, htape), grads, dead, store, packs, zeros, inv, sw)
+    pyramid_backward(pp, (acts, tape), {o: grads[o] for o in pp.out_ids if o in grads}, scale=scale, store=store)
 
 
-class LFDDetectorTrainFunction(torch.autograd.Function):
-    """(cls [N,P,C'], reg [N,P,4]) = LFD.forward(x) in train mode as ONE autograd node: backbone, pyramid neck and LFDHead forward
-    and backward on the hand-written kernels (lfd_detector_forward / lfd_detector_backward)."""
+class DetectorTrainFunction(torch.autograd.Function):
+    """FCOS.forward(x) = (cls [N,P,C], reg [N,P,4], ctr [N,P,1]) or, with an LFDHead, LFD.forward(x) = (cls [N,P,C'], reg [N,P,4])
+    in train mode as ONE autograd node: backbone, pyramid neck and head forward and backward on the hand-written kernels
+    (detector_forward / detector_backward).  sizes_out: the caller's list, which receives [(h, w)] per level."""
 
     @staticmethod
-    def forward(ctx, plan, x, *params):
-        cls, reg, sizes, saved = lfd_detector_forward(plan, x)
+    def forward(ctx, plan, x, sizes_out, *params):
+        full, sizes, saved = detector_forward(plan, x)
         ctx.plan, ctx.saved = plan, saved
-        LFDDetectorTrainFunction.last_sizes = sizes
-        return cls, reg
+        ctx.shapes = [t.shape for t in full.values()]
+        ctx.save_for_backward(*(full[k] for k in plan.glue.reads))
+        sizes_out.extend(sizes)
+        return tuple(full.values())
 
     @staticmethod
-    def backward(ctx, dcls, dreg):
-        plan, saved = ctx.plan, ctx.saved
-        starts, sizes = saved[4], saved[5]
-        p = starts[-1] + sizes[-1][0] * sizes[-1][1]
-        ref = saved[0][0][plan.pyramid.out_ids[0]]
-        zero = lambda c: torch.zeros((ref.size(0), p, c), dtype=torch.float32, device=ref.device)         # noqa: E731
-        dcls = zero(plan.cls_channels) if dcls is None else dcls
-        dreg = zero(4) if dreg is None else dreg
-        lfd_detector_backward(plan, saved, dcls, dreg, loss_scale())
+    def backward(ctx, *douts):
+        plan = ctx.plan
+        dev = ctx.saved[0][0][0].device
+        dfull = {k: torch.zeros(s, dtype=torch.float32, device=dev) if g is None else g
+                 for k, s, g in zip(plan.widths, ctx.shapes, douts)}
+        read = {k: t.detach() for k, t in zip(plan.glue.reads, ctx.saved_tensors)}
+        detector_backward(plan, ctx.saved, read, dfull, loss_scale())
         ctx.saved = None
-        return (None, None) + (None,) * len(plan.params)     # gradients were accumulated into .grad directly
+        return (None,) * (3 + len(plan.params))     # gradients were accumulated into .grad directly
 
 
-def lfd_detector_train_forward(backbone, neck, head, x):
-    """-> (cls, reg, [(h, w)] per level)"""
+def detector_train_forward(backbone, neck, head, x):
+    """-> (cls, reg, ctr, [(h, w)] per level) for an FCOSHead, (cls, reg, [(h, w)] per level) for an LFDHead"""
     check_train_input(backbone, x)
     plan = head.__dict__.get('_lfd_detector_plan')
     if plan is None or plan.pyramid is not neck.__dict__.get('_lfd_pyramid_plan') or plan.pyramid.owner is not backbone:
-        plan = build_lfd_detector(backbone, neck, head)
+        plan = (build_detector if type(head).__name__ == 'FCOSHead' else build_lfd_detector)(backbone, neck, head)
         head.__dict__['_lfd_detector_plan'] = plan
-    cls, reg = LFDDetectorTrainFunction.apply(plan, x, *plan.params)
-    return cls, reg, LFDDetectorTrainFunction.last_sizes
+    sizes = []
+    return DetectorTrainFunction.apply(plan, x, sizes, *plan.params) + (sizes,)
+
+
+lfd_detector_train_forward = detector_train_forward

@@ -1,4 +1,4 @@
-"""GPU tests of the LFDHead training node (train_engine.LFDDetectorTrainFunction): the glue kernels of csrc/lfd_out.hip per
+"""GPU tests of the LFDHead training node (train_engine.DetectorTrainFunction): the glue kernels of csrc/lfd_out.hip per
 element against float64 on the CPU, the argument checks, the node against the package's own route with the head under autograd
 (LFD_HIP_HEAD=0) from identical state, and whole LFDV2_SFPN iterations.
 

@@ -63,7 +63,7 @@ def test_plan_of_lfdv2_sfpn_and_of_its_merged_twin():
     head = m._head
     plan = te.build_lfd_detector(m._backbone, m._neck, head)
     L, nlev = head._num_conv_layers, m._neck._num_outputs
-    assert nlev == 4 and plan.pyramid is m._neck.__dict__['_lfd_pyramid_plan'] and plan.rows == 64 and plan.cls_channels == 4
+    assert nlev == 4 and plan.pyramid is m._neck.__dict__['_lfd_pyramid_plan'] and plan.rows == 64 and plan.widths['cls'] == 4
     assert len(plan.units) == nlev * 2 * L and len({id(u.conv) for u in plan.units}) == 2 * L       # shared: packed once
     assert all(isinstance(u.norm, nn.GroupNorm) and u.relu and u.res is None and not u.first and not u.frozen for u in plan.units)
     assert all(u.conv.kernel_size == (3, 3) for u in plan.units)

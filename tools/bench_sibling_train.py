@@ -1,8 +1,8 @@
 """tools/bench_sibling_train.py -- one training iteration of the pyramid siblings: forward, device targets, fused loss, backward
 (no optimizer) of FCOS_FPN and LFDV2_SFPN at 640x640, batch 32, 2-6 boxes per image (seeded; the shape of
 tools/bench_sibling_loss.py), on the routes a model has:
-    head_node      LFD_HIP_HEAD=1: backbone + neck + head as one autograd node (FCOS_FPN: train_engine.DetectorTrainFunction;
-                   LFDV2_SFPN: train_engine.LFDDetectorTrainFunction)
+    head_node      LFD_HIP_HEAD=1: backbone + neck + head as one autograd node (train_engine.DetectorTrainFunction; FCOS_FPN
+                   with the FCOSHead glue, LFDV2_SFPN with the LFDHead glue)
     node           LFD_HIP_HEAD=0: the backbone + neck node (train_engine.PyramidTrainFunction), the head under autograd
     autograd_neck  LFD_HIP_NECK=0: the backbone node, neck and head as PyTorch-ROCm modules under autograd, where that route
                    exists -- autograd refuses LFDV2_SFPN's neck (an in-place op on a tensor ReluBackward saved), reported as such.
