@@ -645,6 +645,41 @@ LFD_API int lfd_p32_groupnorm_relu_f32(float* x, int32_t n, int64_t hw, int32_t 
                                        lfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same mode for the pyramid necks and FCOSHead (FCOS / LFDv2 / LFD over FPN, SimpleFPN, LFDHeadV1:
+ * lfd_amd/engine_sibling_p32.py; csrc/precise.hip, csrc/precise_pyramid.hip).  Dense fp32 NHWC tensors, 16-byte aligned,
+ * channels a multiple of 4; nothing is launched when a status code is returned.
+ *   lfd_p32_conv2d_merge_nhwc_f32      replaces a lateral 1x1 conv (+ folded BatchNorm, + ReLU) AND the top-down merge that
+ *                                      follows it, `lateral[i-1] += nn.Upsample(size, mode='nearest')(lateral[i])`
+ *                                      (lfd/model/neck/fpn.py:127-152, simple_fpn.py:141-172), in one launch:
+ *                                      out = relu?(conv + bias) + nearest(up [n, up_h, up_w, cout]) -- the ReLU
+ *                                      (relu_on_lateral) before the add, as the reference orders them.  desc: in_format < 0,
+ *                                      ks 1, stride 1, dense output, cout % 4 == 0; up_h <= h, up_w <= w; `up` is the coarser
+ *                                      level AFTER its own merge (walk the laterals from the coarsest down).  The same bits as
+ *                                      lfd_p32_conv2d_nhwc_f32 followed by lfd_p32_upsample_nearest_add_f32.
+ *   lfd_p32_upsample_nearest_add_f32   the merge step alone (same reference lines): dst[n,H,W,c] += nearest(src[n,h,w,c]),
+ *                                      source index min(floorf(dst_index * float(in)/out), in-1) as ATen computes it (the rule
+ *                                      of lfd_upsample_nearest_add_nhwc_f16); h <= H, w <= W, equal sizes are a plain add.
+ *   lfd_p32_relu_f32                   nn.ReLU(inplace=True) in front of an extra level (fpn.py:127-152 / simple_fpn.py:141-172
+ *                                      run `fpn_out{i}` = Sequential(ReLU(inplace=True), ...) on the previous output, which it
+ *                                      rewrites as well).
+ *   lfd_p32_maxpool3x3s2_f32           extra_type='pooling': nn.MaxPool2d(3, 2, 1) (same lines) -> [n, (h+1)/2, (w+1)/2, c];
+ *                                      F.max_pool2d semantics at the border (the padding never wins).
+ *   lfd_p32_exp_rows_f32               replaces the `.float().exp()` of `scales[i](regression(x)).float().exp()`
+ *                                      (lfd/model/head/fcos_head.py:129-154); conv, bias and Scale are the epilogue of
+ *                                      lfd_p32_conv2d_nhwc_f32 writing rows row0 .. row0+rows of the level-concatenated
+ *                                      out [n, P, c] (image_stride = P * c floats); this entry applies expf (not the fast
+ *                                      intrinsic) to those rows of every image in place and touches nothing else. */
+LFD_API int lfd_p32_conv2d_merge_nhwc_f32(const lfd_p32_conv_desc_t* desc, const void* in, float* out, const void* w_packed,
+                                          const float* bias, const float* up, int32_t up_h, int32_t up_w, lfd_stream_t stream);
+LFD_API int lfd_p32_upsample_nearest_add_f32(float* dst, const float* src, int32_t n, int32_t H, int32_t W, int32_t h,
+                                             int32_t w, int32_t c, lfd_stream_t stream);
+LFD_API int lfd_p32_relu_f32(float* x, int64_t count, lfd_stream_t stream);
+LFD_API int lfd_p32_maxpool3x3s2_f32(const float* in, float* out, int32_t n, int32_t h, int32_t w, int32_t c,
+                                     lfd_stream_t stream);
+LFD_API int lfd_p32_exp_rows_f32(float* out, int32_t n, int64_t image_stride, int64_t row0, int64_t rows, int32_t c,
+                                 lfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The same precision mode on "hi/lo planes" (csrc/planes.hip, csrc/planes_impl.h; lfd_amd/engine_p2.py) -- the fast form of
  * the mode inside north_star's 1e-3 (lfd/model/lfd.py:511-542 to <= 1e-4 on the raw logits).
  * A plane tensor stores an fp32-valued NHWC activation x as two contiguous NHWC fp16 tensors: hi = fp16(x) at the base pointer,

@@ -45,6 +45,9 @@ struct P32Args {
   long out_img_stride;   // floats between images of `out`
   int out_pix_stride;    // floats between pixels of `out`
   int tiles_x, tiles_y;
+  const float* up;       // MERGE: fp32 NHWC [N,uh,uw,cout], the coarser (already merged) level of a pyramid neck
+  int uh, uw;
+  float usy, usx;        // MERGE: float(uh) / OH, float(uw) / OW (ATen's nearest scale)
 };
 
 __device__ __forceinline__ void split8(const float4 a, const float4 b, half8& hi, half8& lo) {
@@ -73,7 +76,10 @@ __device__ __forceinline__ float frame_value(const void* in, int fmt, int n, int
 // straight into LDS -- wave (slab s) fills channel chunk s of its 64 pixels -- and contracted again; the 64-channel fp32
 // intermediate (1.06 GB per 8 x 1080p for the first pair) never reaches HBM.  Needs cout == 64 (one workgroup = both slabs).
 // PCIN: channels of the frame a PATCH conv gathers from (3 = RGB, 1 = gray)
-template <int KS, int S, int NG, bool PATCH, bool TAIL = false, int PCIN = 3>
+// MERGE: the lateral conv of a pyramid neck with the top-down merge in its epilogue (fpn.py:127-135, simple_fpn.py:141-157:
+// `lateral[i-1] += nn.Upsample(size, mode='nearest')(lateral[i])`): out = relu?(conv + bias) + up[n, sy(oy), sx(ox), :], source
+// index as ATen's upsample_nearest2d computes it (csrc/precise_pyramid.hip k_p32_upsample_add: same expression, same add).
+template <int KS, int S, int NG, bool PATCH, bool TAIL = false, int PCIN = 3, bool MERGE = false>
 __global__ __launch_bounds__(256) void k_p32_conv(const P32Args a) {
   constexpr int TW = 16, TH = 4 * NG;
   constexpr int IH = (TH - 1) * S + KS, IW = (TW - 1) * S + KS;
@@ -226,6 +232,13 @@ __global__ __launch_bounds__(256) void k_p32_conv(const P32Args a) {
     const size_t pixi = (size_t)oy * a.OW + ox;
     float* o = a.out + (size_t)n * a.out_img_stride + pixi * a.out_pix_stride;
     const float* r = a.res ? a.res + ((size_t)n * a.OH * a.OW + pixi) * a.cout : nullptr;
+    const float* u = nullptr;
+    if constexpr (MERGE) {
+      int yy = (int)floorf((float)oy * a.usy), xx = (int)floorf((float)ox * a.usx);
+      yy = yy < a.uh - 1 ? yy : a.uh - 1;
+      xx = xx < a.uw - 1 ? xx : a.uw - 1;
+      u = a.up + (((size_t)n * a.uh + yy) * a.uw + xx) * a.cout;
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int c0 = slab * 32 + 8 * q + 4 * kh;
@@ -243,6 +256,10 @@ __global__ __launch_bounds__(256) void k_p32_conv(const P32Args a) {
           v[e] *= sc;
           if (erelu) v[e] = fmaxf(v[e], 0.f);
         }
+        if constexpr (MERGE) {                 // after the ReLU: relu_on_lateral comes before the `+=`
+          const float4 uv = *reinterpret_cast<const float4*>(u + c0);
+          v[0] += uv.x; v[1] += uv.y; v[2] += uv.z; v[3] += uv.w;
+        }
         *reinterpret_cast<float4*>(o + c0) = make_float4(v[0], v[1], v[2], v[3]);
       } else {
 #pragma unroll
@@ -252,6 +269,7 @@ __global__ __launch_bounds__(256) void k_p32_conv(const P32Args a) {
           if (r) x += r[c0 + e];
           x *= sc;
           if (erelu) x = fmaxf(x, 0.f);
+          if constexpr (MERGE) x += u[c0 + e];
           o[c0 + e] = x;
         }
       }
@@ -259,7 +277,7 @@ __global__ __launch_bounds__(256) void k_p32_conv(const P32Args a) {
   }
 }
 
-template <int KS, int S, int NG, bool PATCH, bool TAIL = false, int PCIN = 3>
+template <int KS, int S, int NG, bool PATCH, bool TAIL = false, int PCIN = 3, bool MERGE = false>
 int launch_p32(P32Args a, hipStream_t st) {
   constexpr int TH = 4 * NG, TW = 16;
   constexpr int IH = (TH - 1) * S + KS, IW = (TW - 1) * S + KS;
@@ -269,7 +287,7 @@ int launch_p32(P32Args a, hipStream_t st) {
   a.tiles_y = (a.OH + TH - 1) / TH;
   const long tiles = (long)a.tiles_x * a.tiles_y * a.N;
   if (tiles > 0x7fffffffL) return LFD_ERR_UNSUPPORTED;
-  auto kern = k_p32_conv<KS, S, NG, PATCH, TAIL, PCIN>;
+  auto kern = k_p32_conv<KS, S, NG, PATCH, TAIL, PCIN, MERGE>;
   if (lds > 64 * 1024) {
     static unsigned long long set_mask = 0;   // (idempotent; races only repeat the same call)
     const int set_dev = lfd_device_ordinal();
@@ -393,6 +411,30 @@ int lfd_p32_conv2d_nhwc_f32(const lfd_p32_conv_desc_t* d, const void* in, float*
     case 12: return launch_p32<1, 2, 1, false>(a, st);
     default: return LFD_ERR_UNSUPPORTED;
   }
+}
+
+int lfd_p32_conv2d_merge_nhwc_f32(const lfd_p32_conv_desc_t* d, const void* in, float* out, const void* w_packed,
+                                  const float* bias, const float* up, int32_t up_h, int32_t up_w, lfd_stream_t stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!d || !in || !out || !w_packed || !bias || !up) return LFD_ERR_INVALID_ARGUMENT;
+  if (d->n < 1 || d->h < 1 || d->w < 1 || d->cout < 1 || up_h < 1 || up_w < 1) return LFD_ERR_INVALID_ARGUMENT;
+  if (up_h > d->h || up_w > d->w || up == out || in == out) return LFD_ERR_INVALID_ARGUMENT;
+  // `in`, `up` and `out` move as 16-byte vectors: a misaligned pointer is a status code, not a memory fault
+  if (!lfd_aligned16(in) || !lfd_aligned16(out) || !lfd_aligned16(up)) return LFD_ERR_INVALID_ARGUMENT;
+  // a lateral: 1x1 stride 1 on fp32 NHWC, dense output (`up` has the output's channel count, read 16 bytes at a time)
+  if (d->in_format >= 0 || d->ks != 1 || d->stride != 1 || d->cin < 32 || d->cin % 32 || d->cout % 4) return LFD_ERR_UNSUPPORTED;
+  if (d->out_pixel_stride > 0 || d->out_image_stride > 0) return LFD_ERR_UNSUPPORTED;
+  P32Args a{};
+  a.in = in; a.out = out; a.w = (const half8*)w_packed; a.bias = bias;
+  a.N = d->n; a.H = d->h; a.W = d->w; a.cin = d->cin; a.cout = d->cout; a.nslab = (d->cout + 31) / 32;
+  a.relu = d->relu; a.fmt = -1;
+  a.OH = d->h; a.OW = d->w;
+  a.out_pix_stride = d->cout;
+  a.out_img_stride = (long)a.OH * a.OW * a.out_pix_stride;
+  a.up = up; a.uh = up_h; a.uw = up_w;
+  a.usy = (float)up_h / (float)a.OH;
+  a.usx = (float)up_w / (float)a.OW;
+  return launch_p32<1, 1, 2, false, false, 3, true>(a, st);
 }
 
 int lfd_p32_conv2d_tail_nhwc_f32(const lfd_p32_conv_desc_t* d, const void* in, float* out, const void* w_packed,

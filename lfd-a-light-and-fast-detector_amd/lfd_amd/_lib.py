@@ -443,6 +443,11 @@ _SIGNATURES = {
     'lfd_p32_conv_packed_weight_halfs': (_SZ, [_I32, _I32, _I32]),
     'lfd_p32_conv2d_nhwc_f32': (C.c_int, [C.POINTER(P32ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
     'lfd_p32_conv2d_tail_nhwc_f32': (C.c_int, [C.POINTER(P32ConvDesc), _P, _P, _P, _P, _P, _P, _I32, _P]),
+    'lfd_p32_conv2d_merge_nhwc_f32': (C.c_int, [C.POINTER(P32ConvDesc), _P, _P, _P, _P, _P, _I32, _I32, _P]),
+    'lfd_p32_upsample_nearest_add_f32': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    'lfd_p32_relu_f32': (C.c_int, [_P, _I64, _P]),
+    'lfd_p32_maxpool3x3s2_f32': (C.c_int, [_P, _P, _I32, _I32, _I32, _I32, _P]),
+    'lfd_p32_exp_rows_f32': (C.c_int, [_P, _I32, _I64, _I64, _I64, _I32, _P]),
     'lfd_pl_stem_pair': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P]),
     'lfd_pl_stem2x': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     'lfd_pl_conv2d': (C.c_int, [C.POINTER(PlConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -70,15 +70,22 @@ class PrecisePlan(object):
         with torch.no_grad():
             self._build(model)
 
+    has_ctr = False        # a centerness output [N,P,1] next to cls / reg (FCOSHead: engine_sibling_p32)
+
+    def level_bufs(self):
+        """the buffers whose sizes are the head levels' (a SimpleNeck keeps its taps' sizes)"""
+        return self.taps
+
     def _new_buf(self, channels, scale):
         b = self._nbuf
         self._nbuf += 1
         self.buf_channels[b], self.buf_scale[b] = channels, scale
         return b
 
-    def _conv(self, src, w, b, ks, stride, relu, res=None, patch=False, scale=None, out=None, level=None, tail=None):
+    def _conv(self, src, w, b, ks, stride, relu, res=None, patch=False, scale=None, out=None, level=None, tail=None, packed=None):
         """w: folded fp32 OIHW (channel-padded where engine.fold_conv_norm pads), b: fp32 bias;
-        tail = (w2 [64,64,1,1], b2): a chained 1x1 + ReLU in the same launch (lfd_p32_conv2d_tail_nhwc_f32)"""
+        tail = (w2 [64,64,1,1], b2): a chained 1x1 + ReLU in the same launch (lfd_p32_conv2d_tail_nhwc_f32);
+        packed = (o.w, o.b) of an earlier op on the same (w, b): modules shared between levels keep one device copy"""
         dev = self.device
         o = _Op()
         o.tail = None if tail is None else (pack_weight(tail[0]).to(dev), _pad_bias(tail[1]).to(dev))
@@ -92,8 +99,7 @@ class PrecisePlan(object):
             w = torch.cat([wk, wk.new_zeros((w.shape[0], 32 - 9 * o.cin))], 1).reshape(w.shape[0], 32, 1, 1)
         else:
             o.cin = w.shape[1]
-        o.w = pack_weight(w).to(dev)
-        o.b = _pad_bias(b).to(dev)
+        o.w, o.b = packed if packed is not None else (pack_weight(w).to(dev), _pad_bias(b).to(dev))
         o.out, o.level = out, level
         if out is None:
             sc = (self.buf_scale[src] if src != 'input' else 1) * stride
@@ -103,18 +109,17 @@ class PrecisePlan(object):
         self.ops.append(o)
         return o.dst
 
-    def _gn(self, buf, norm):
+    def _gn(self, buf, norm, relu=True):
         o = _Op()
-        o.kind, o.src = 'gn', buf
+        o.kind, o.src, o.relu = 'gn', buf, int(relu)
         o.gamma = norm.weight.detach().float().contiguous().to(self.device)
         o.beta = norm.bias.detach().float().contiguous().to(self.device)
         o.eps, o.groups = float(norm.eps), int(norm.num_groups)
         self.ops.append(o)
 
-    def _build(self, model):
-        bb, neck, head = model._backbone, model._neck, model._head
-        if type(neck).__name__ != 'SimpleNeck' or type(head).__name__ != 'LFDHead':
-            engine._unsupported("precision='fp32_storage' covers SimpleNeck + LFDHead (every shipped configuration)")
+    def _build_backbone(self, bb):
+        """stem (pairs conv3x3 s2 -> conv1x1 as one launch), residual blocks, taps: the launches of an LFDResNet, shared with
+        the plan of the pyramid necks / other heads (engine_sibling_p32.SiblingPrecisePlan) -> self.taps (buffer ids)"""
         if bb._input_channels not in (1, 3):
             engine._unsupported('input_channels not in (1, 3)')
         if bb._norm_cfg is not None and bb._norm_cfg['type'] != 'BatchNorm2d':
@@ -163,6 +168,12 @@ class PrecisePlan(object):
                 cur = y
                 if (i, j) in taps:
                     self.taps.append(cur)
+
+    def _build(self, model):
+        bb, neck, head = model._backbone, model._neck, model._head
+        if type(neck).__name__ != 'SimpleNeck' or type(head).__name__ != 'LFDHead':
+            engine._unsupported("precision='fp32_storage' covers SimpleNeck + LFDHead (every shipped configuration)")
+        self._build_backbone(bb)
         # ---- neck + head (simple_neck.py:67-74, lfd_head.py:164-185)
         ncfg = head._norm_cfg
         has_hn = ncfg is not None
@@ -214,32 +225,35 @@ class PrecisePlan(object):
     def run(self, x, fmt, st):
         l, sp = lib(), stream_ptr()
         for o in self.ops:
-            if o.kind == 'gn':
-                t = st.bufs[o.src]
-                check(l.lfd_p32_groupnorm_relu_f32(ptr(t), st.n, t.shape[1] * t.shape[2], t.shape[3], o.groups, ptr(o.gamma),
-                                                   ptr(o.beta), o.eps, 1, ptr(st.gn_ws), st.gn_ws.numel(), sp),
-                      'lfd_p32_groupnorm_relu_f32')
-                continue
-            if o.patch:
-                src, hh, ww, infmt = x, st.h, st.w, fmt
-            else:
-                src = st.bufs[o.src]
-                hh, ww, infmt = src.shape[1], src.shape[2], -1
-            d = _lib.P32ConvDesc(st.n, hh, ww, o.cin, o.cout, o.ks, o.stride, o.relu, infmt, 0, 0)
-            if o.out is None:
-                dst = ptr(st.bufs[o.dst])
-            else:
-                t = st.cls if o.out == 'cls' else st.reg
-                cw = t.shape[2]
-                d.out_pixel_stride, d.out_image_stride = cw, st.P * cw
-                dst = C.c_void_p(t.data_ptr() + st.p_off[o.level] * cw * 4)
-            if o.tail is not None:
-                check(l.lfd_p32_conv2d_tail_nhwc_f32(C.byref(d), ptr(src), dst, ptr(o.w), ptr(o.b), ptr(o.tail[0]), ptr(o.tail[1]), 1, sp),
-                      'lfd_p32_conv2d_tail_nhwc_f32')
-                continue
-            check(l.lfd_p32_conv2d_nhwc_f32(C.byref(d), ptr(src), dst, ptr(o.w), ptr(o.b),
-                                            ptr(st.bufs[o.res]) if o.res is not None else None,
-                                            ptr(o.scale) if o.scale is not None else None, sp), 'lfd_p32_conv2d_nhwc_f32')
+            self._run_op(o, x, fmt, st, l, sp)
+
+    def _run_op(self, o, x, fmt, st, l, sp):
+        if o.kind == 'gn':
+            t = st.bufs[o.src]
+            check(l.lfd_p32_groupnorm_relu_f32(ptr(t), st.n, t.shape[1] * t.shape[2], t.shape[3], o.groups, ptr(o.gamma),
+                                               ptr(o.beta), o.eps, o.relu, ptr(st.gn_ws), st.gn_ws.numel(), sp),
+                  'lfd_p32_groupnorm_relu_f32')
+            return
+        if o.patch:
+            src, hh, ww, infmt = x, st.h, st.w, fmt
+        else:
+            src = st.bufs[o.src]
+            hh, ww, infmt = src.shape[1], src.shape[2], -1
+        d = _lib.P32ConvDesc(st.n, hh, ww, o.cin, o.cout, o.ks, o.stride, o.relu, infmt, 0, 0)
+        if o.out is None:
+            dst = ptr(st.bufs[o.dst])
+        else:
+            t = getattr(st, o.out)          # 'cls' | 'reg' (| 'ctr': engine_sibling_p32)
+            cw = t.shape[2]
+            d.out_pixel_stride, d.out_image_stride = cw, st.P * cw
+            dst = C.c_void_p(t.data_ptr() + st.p_off[o.level] * cw * 4)
+        if o.tail is not None:
+            check(l.lfd_p32_conv2d_tail_nhwc_f32(C.byref(d), ptr(src), dst, ptr(o.w), ptr(o.b), ptr(o.tail[0]), ptr(o.tail[1]), 1, sp),
+                  'lfd_p32_conv2d_tail_nhwc_f32')
+            return
+        check(l.lfd_p32_conv2d_nhwc_f32(C.byref(d), ptr(src), dst, ptr(o.w), ptr(o.b),
+                                        ptr(st.bufs[o.res]) if o.res is not None else None,
+                                        ptr(o.scale) if o.scale is not None else None, sp), 'lfd_p32_conv2d_nhwc_f32')
 
 
 class _State(object):
@@ -257,7 +271,7 @@ class _State(object):
                     s //= 2
                 self.dims[b] = (hh, ww)
                 self.bufs[b] = torch.empty((n, hh, ww, plan.buf_channels[b]), dtype=torch.float32, device=dev)
-            self.sizes = [self.dims[t] for t in plan.taps]
+            self.sizes = [self.dims[t] for t in plan.level_bufs()]
             self.p_off, p = [], 0
             for hh, ww in self.sizes:
                 self.p_off.append(p)
@@ -265,6 +279,7 @@ class _State(object):
             self.P = p
             self.cls = torch.empty((n, p, plan.cls_channels), dtype=torch.float32, device=dev)
             self.reg = torch.empty((n, p, 4), dtype=torch.float32, device=dev)
+            self.ctr = torch.empty((n, p, 1), dtype=torch.float32, device=dev) if plan.has_ctr else None
             self.gn_ws = torch.empty(max(int(lib().lfd_p32_groupnorm_workspace_bytes(n, 64)), 1), dtype=torch.uint8, device=dev)
         self.graph = {}
 

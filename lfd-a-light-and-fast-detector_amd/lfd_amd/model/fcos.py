@@ -26,7 +26,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import _lib, engine_sibling, ops, parallel, train_engine
+from .. import _lib, engine_sibling, engine_sibling_p32, ops, parallel, train_engine
 from .lfd import LFD
 from .utils import multiclass_nms  # noqa: F401  (importable like the reference module)
 
@@ -83,6 +83,26 @@ class FCOS(nn.Module):
         self.max_candidates = 8192
         self.use_graph = False       # capture the eval-mode forward into a HIP graph per input buffer
 
+    PRECISIONS = ('fp16', 'fp32_storage')
+
+    @property
+    def precision(self):
+        """Numeric mode of the eval-mode forward (training is unaffected), as LFD.precision:
+        'fp16'          fp16 MFMA operands and fp16 inter-layer storage (engine_sibling): logits within 2e-2 of the fp32 reference;
+        'fp32_storage'  every inter-layer tensor fp32, operands split into fp16 hi + 2^-11 lo parts inside the conv kernel
+                        (engine_sibling_p32, csrc/precise.hip, csrc/precise_pyramid.hip): cls / centerness logits within 1e-4
+                        absolute, distances within 1e-4 relative of the fp32 reference."""
+        return self.__dict__.get('_precision', 'fp16')
+
+    @precision.setter
+    def precision(self, value):
+        if value not in self.PRECISIONS:
+            raise ValueError('precision must be one of %s' % (self.PRECISIONS,))
+        if value != self.precision:
+            for cache in ('_lfd_sibling_cache', '_lfd_sibling_p32_cache'):      # plans and the forward graphs they own
+                self.__dict__.pop(cache, None)
+        self.__dict__['_precision'] = value
+
     @property
     def head_indexes_to_feature_map_sizes(self):
         return self._head_indexes_to_feature_map_sizes
@@ -109,7 +129,12 @@ class FCOS(nn.Module):
         """fcos.py:414-449"""
         if self.training or (torch.is_grad_enabled() and x.requires_grad):
             return self._forward_train(x)
-        cls, reg, ctr, sizes = engine_sibling.sibling_forward(self, x, use_graph=self.use_graph)
+        if self.precision == 'fp32_storage':
+            outs = engine_sibling_p32.sibling_forward(self, x, use_graph=self.use_graph)
+            cls, reg, ctr = [t.clone() for t in outs[:3]]       # engine-owned buffers: fresh tensors, like the fp16 route
+            sizes = outs[3]
+        else:
+            cls, reg, ctr, sizes = engine_sibling.sibling_forward(self, x, use_graph=self.use_graph)
         for i, hw in enumerate(sizes):
             self._head_indexes_to_feature_map_sizes[i] = hw
         return cls, reg, ctr

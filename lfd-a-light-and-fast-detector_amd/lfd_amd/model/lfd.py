@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import engine, engine_p32, engine_sibling, ops, parallel, train_engine
+from .. import engine, engine_p32, engine_sibling, engine_sibling_p32, ops, parallel, train_engine
 from ..data import DeviceAnnotations
 from .utils import multiclass_nms  # noqa: F401  (kept importable like the reference module)
 
@@ -130,6 +130,9 @@ class LFD(nn.Module):
                         way, three MFMAs per k-step, fp32 accumulation and epilogues (engine_p2.py, csrc/planes*.hip;
                         engine_p32.py / csrc/precise.hip for layer shapes without a plane kernel); raw logits within 1e-4
                         of the fp32 reference (north_star: "tensors within 1e-3"; measured 8e-6), ~3.5x the time.
+                        A neck other than SimpleNeck or a head other than LFDHead (FPN / SimpleFPN, LFDHeadV1; LFDv2 and
+                        FCOS alike) runs the fp32-tensor form layer by layer (engine_sibling_p32.py, csrc/precise_pyramid.hip),
+                        same tolerance.
         Both modes take the frames of the model's input_channels: RGB (3) float32 [N,3,H,W], float16 / uint8 [N,H,W,3];
         grayscale (input_channels=1) float32 [N,1,H,W], float16 / uint8 [N,H,W,1] (the first stem unit of csrc/stem_gray.hip);
         uint8 frames get the reference's simple_normalize on the load."""
@@ -142,6 +145,8 @@ class LFD(nn.Module):
         if value != self.precision:
             self.__dict__.get('_step_graphs', {}).clear()
             self.__dict__['_step_graphs_ver'] = None
+            for cache in ('_lfd_sibling_cache', '_lfd_sibling_p32_cache'):      # the layer engines' plans and forward graphs
+                self.__dict__.pop(cache, None)
         self._precision = value
 
     @staticmethod
@@ -202,7 +207,9 @@ class LFD(nn.Module):
     def forward_resident(self, x, slot=0):
         """Fast path: same as forward() in eval mode but returns the engine-owned output buffers
         (no copy, valid until the next forward of the same input shape and `slot`)."""
-        if self.precision == 'fp32_storage':
+        if self.precision == 'fp32_storage' and engine_sibling_p32.covers(self):
+            cls, reg, _, sizes = engine_sibling_p32.sibling_forward(self, x, use_graph=self.use_graph, slot=slot)
+        elif self.precision == 'fp32_storage':
             cls, reg, sizes = engine_p32.lfd_forward(self, x, use_graph=self.use_graph, slot=slot)
         elif x.is_cuda and not self._fused_plan_ok(x.device):
             cls, reg, _, sizes = engine_sibling.sibling_forward(self, x, use_graph=self.use_graph)
@@ -221,7 +228,8 @@ class LFD(nn.Module):
         overlap on the device (the small-map stages, the post-processing kernels and the launch gaps of one batch leave most
         CUs idle -- a second batch in flight fills them: 0.75 -> 0.61 ms per batch of 8 at depth 2, tools/ab_pipeline.py)."""
         precise = self.precision == 'fp32_storage'
-        if not self.use_graph or (not precise and not self._fused_plan_ok(x.device)):
+        layered = engine_sibling_p32.covers(self) if precise else not self._fused_plan_ok(x.device)
+        if not self.use_graph or layered:       # the layer engines replay their forward graph; post-processing follows it
             return self.detect(self.forward_resident(x, slot), meta, score_thr, iou_thr, class_agnostic, max_candidates)
         score_thr = self._classification_threshold if score_thr is None else score_thr
         iou_thr = self._nms_cfg.get('iou_thr', 0.5) if iou_thr is None else iou_thr
