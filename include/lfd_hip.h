@@ -1334,7 +1334,8 @@ typedef struct lfd_head_desc {
   int32_t total_points;                       /* P */
   int32_t cls_channels;                       /* C' (row length of out_cls) */
   int32_t final_reg_rows;                     /* final conv rows [0, reg_rows) -> reg: 0 or 4 */
-  int32_t final_cls_rows;                     /* ... followed by cls_rows rows -> cls (reg+cls <= 64) */
+  int32_t final_cls_rows;                     /* ... followed by cls_rows rows -> cls (output pass: reg+cls <= 64 through
+                                               * lfd_head_forward_f16, 64 < reg+cls <= 128 through lfd_head_forward_wide_f16) */
 } lfd_head_desc_t;
 
 typedef struct lfd_head_level_ptrs {
@@ -1371,6 +1372,15 @@ LFD_API int lfd_head_forward_f16(const lfd_head_desc_t* desc, int32_t pass,
                                  const float* ab1 /*[L][n][128][2]*/, const float* ab2,
                                  float* partial, float* out_cls, float* out_reg, const void* zeros,
                                  lfd_stream_t stream);
+/* The output pass (pass 3) for 64 < final_reg_rows + final_cls_rows <= 128: wf_packed / bf padded with zero rows to 32 * ft rows,
+ * ft = ceil(rows / 32) = 3 or 4.  Passes 1 and 2 and both finalize calls are the entries above (they only validate the final
+ * rows).  Same argument checks as lfd_head_forward_f16.  Runs in the wave-per-32-pixels kernel only: LFD_ERR_UNSUPPORTED, with
+ * nothing launched, for up to 64 rows (use lfd_head_forward_f16), more than 128 rows, GroupNorm groups of fewer than 8 channels
+ * and LFD_TUNE_HEAD2 = 0.  Class rows are written as 16-byte stores when final_reg_rows, final_cls_rows and cls_channels are
+ * multiples of four and out_cls is 16-byte aligned, one by one otherwise: the same values either way. */
+LFD_API int lfd_head_forward_wide_f16(const lfd_head_desc_t* desc, const lfd_head_level_ptrs_t* levels,
+                                      const float* ab1, const float* ab2, float* out_cls, float* out_reg,
+                                      const void* zeros, lfd_stream_t stream);
 /* Pass 3 that also does the front half of lfd_detect_batched (lfd_head.py:164-185 + lfd.py:449-499 in one launch,
  * SURVEY 8b lfd_head_final_decode): sigma(cls) > score_thr -> decode -> append {box, score, label 0, point} to the
  * candidate arrays of `det_workspace`; lfd_detect_from_candidates finishes the step.  out_cls / out_reg may be NULL

@@ -492,6 +492,7 @@ __device__ unsigned long long g_h2_dbg[3 * 32];
 template <int PASS, int FT, bool DEC = false, bool FOLD = false, bool A1 = false>
 __global__ __launch_bounds__(256, H2_WPS(PASS)) void k_head2(HeadArgs a) {
   static_assert(!DEC || (PASS == 3 && FT == 1), "decode rides on the output pass of a merged single-class tower");
+  static_assert(FT >= 1 && FT <= 4 && (FT <= 2 || PASS == 3), "final conv: up to 4 tiles of 32 rows (more than 2: the wide output pass)");
   static_assert(!FOLD || PASS == 3, "AccVGPR-resident filters: output pass");
   static_assert(!A1 || FOLD, "stored tower-1 activations: output pass with folded filters");
   constexpr int NKN = 4, NKNX = 8, NKH = HC / 16;                      // neck k-steps per 64 input channels / maximum (128 channels)
@@ -613,7 +614,9 @@ __global__ __launch_bounds__(256, H2_WPS(PASS)) void k_head2(HeadArgs a) {
     // the shared area -- so their (cold) fetch latency and the two workgroup barriers overlap with useful work.
     const bool new_level = j != cur_j;
     const int nkl = L.cin / 16;              // 4 or 8 neck k-steps for this level
-    half8 t_wn[NKNX], t_wf[(PASS == 3) ? (FT * NKH + 3) / 4 : 1];
+    // (wide heads, FT > 2: 6 / 8 more staging registers across the filter setup spill; their final filter is fetched behind
+    //  the first barrier instead -- a level switch is rare)
+    half8 t_wn[NKNX], t_wf[(PASS == 3 && FT <= 2) ? (FT * NKH + 3) / 4 : 1];
     float t_bn = 0.f, t_bf = 0.f;
     if (new_level) {
 #pragma unroll
@@ -624,7 +627,7 @@ __global__ __launch_bounds__(256, H2_WPS(PASS)) void k_head2(HeadArgs a) {
       t_bn = L.bn[wave * 32 + (lane & 31)];
       if constexpr (PASS == 3) {
 #pragma unroll
-        for (int k = 0; k < (FT * NKH + 3) / 4; ++k) {
+        for (int k = 0; k < (FT <= 2 ? (FT * NKH + 3) / 4 : 0); ++k) {
           const int fq = wave + 4 * k;
           if (fq < FT * NKH) t_wf[k] = perm(L.wf, fq / NKH, fq % NKH, 1.f);
         }
@@ -733,7 +736,7 @@ __global__ __launch_bounds__(256, H2_WPS(PASS)) void k_head2(HeadArgs a) {
 #pragma unroll
         for (int k = 0; k < (FT * NKH + 3) / 4; ++k) {
           const int fq = wave + 4 * k;
-          if (fq < FT * NKH) s_wf[((fq / NKH) * (NKH + 1) + (fq % NKH)) * 64 + lane] = t_wf[k];
+          if (fq < FT * NKH) s_wf[((fq / NKH) * (NKH + 1) + (fq % NKH)) * 64 + lane] = FT <= 2 ? t_wf[FT <= 2 ? k : 0] : perm(L.wf, fq / NKH, fq % NKH, 1.f);
         }
         if (wave < FT) s_wf[(wave * (NKH + 1) + NKH) * 64 + lane] = bias_frag(t_bf);
       }
@@ -895,7 +898,61 @@ __global__ __launch_bounds__(256, H2_WPS(PASS)) void k_head2(HeadArgs a) {
           if constexpr (PASS == 2) add_stats(acc, ct, lane_ok ? 1.f : 0.f, tail);
           else { bq[2 * ct] = to_b(acc, 0); bq[2 * ct + 1] = to_b(acc, 1); }
         }
-        if constexpr (PASS == 3) {
+        if constexpr (PASS == 3 && FT > 2) {
+          // ---- final conv of a wide head (lfd_head_forward_wide_f16: 3 or 4 tiles of 32 rows).  Kept in registers across the
+          //      pixel loop like the one- and two-tile heads keep theirs, 27 / 36 fragments are 108 / 144 registers the wave does
+          //      not have (every variant spilled 120 .. 570 bytes per lane).  So the fragments are read per group -- the
+          //      compiler barrier keeps the reads inside the loop -- through a register ring that runs FWD k-steps ahead of the
+          //      MFMAs, like the neck's: tile by tile, the bias step first, in the order of the narrow heads (same bits).
+          asm volatile("" ::: "memory");
+          const size_t row = (size_t)n * a.P + L.p_off + p0 + pix;
+          // class rows: the lane's rows 8g + 4hh .. + 3 of tile f are four consecutive class channels; when the regression rows,
+          // the class rows and the row length of out_cls are multiples of four (and out_cls is 16-byte aligned) every such
+          // quad is one 16-byte store (80, 124, 128 classes); one by one otherwise (81 channels).  Rows past reg_rows +
+          // cls_rows -- the zero padding of the last tile -- are never stored.  Wave-uniform.
+          const bool quads = (((a.reg_rows | a.cls_rows | a.CC) & 3) == 0) && (((uintptr_t)a.out_cls & 15) == 0);
+          // row 32f + 8g + 4hh + j of the final conv is class channel c0 + 32f + 8g + j: one pointer per lane and group, the
+          // rest of every store address is an immediate
+          const int c0 = 4 * hh - a.reg_rows;
+          float* const cp = a.out_cls + ((ptrdiff_t)(row * a.CC) + c0);
+          constexpr int NF = FT * (NKH + 1), FWD = 3;
+          auto widx = [](int i) { return (i / (NKH + 1)) * (NKH + 1) + ((i % (NKH + 1)) == 0 ? NKH : (i % (NKH + 1)) - 1); };
+          half8 fring[FWD + 1];
+#pragma unroll
+          for (int i = 0; i < FWD; ++i) fring[i] = s_wf[widx(i) * 64 + lane];
+          f32x16 fa;
+#pragma unroll
+          for (int i = 0; i < NF; ++i) {
+            if (i + FWD < NF) fring[(i + FWD) % (FWD + 1)] = s_wf[widx(i + FWD) * 64 + lane];
+            const int f = i / (NKH + 1), j = i % (NKH + 1);
+            fa = __builtin_amdgcn_mfma_f32_32x32x16_f16(fring[i % (FWD + 1)], j == 0 ? ones : bq[j == 0 ? 0 : j - 1], j == 0 ? zero : fa, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (j == NKH && lane_ok) {
+              // final rows: [reg x reg_rows][cls x cls_rows]; lane (pixel, hh) holds rows 32f + 8g + 4hh + j
+              if (a.reg_rows == 4 && f == 0 && hh == 0)
+                *reinterpret_cast<float4*>(a.out_reg + row * 4) = make_float4(fa[0] * scale, fa[1] * scale, fa[2] * scale, fa[3] * scale);
+              // row k = 32f + 8g + j of this lane is a class row when lo <= k < hi (k < lo: only among the first four).  The
+              // empty asm keeps the up to 64 compares here: hoisted out of the pixel loop as lane masks they cost 110 .. 165
+              // spilled SGPRs.
+              int lo = -c0, hi = a.cls_rows - c0;
+              asm volatile("" : "+v"(lo), "+v"(hi));
+              if (quads) {
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                  const int k = f * 32 + 8 * g4;
+                  if ((k >= 4 || k >= lo) && k + 3 < hi)
+                    *reinterpret_cast<float4*>(cp + f * 32 + 8 * g4) = make_float4(fa[4 * g4], fa[4 * g4 + 1], fa[4 * g4 + 2], fa[4 * g4 + 3]);
+                }
+              } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                  const int k = f * 32 + 8 * (r >> 2) + (r & 3);
+                  if ((k >= 4 || k >= lo) && k < hi) cp[k] = fa[r];
+                }
+              }
+            }
+          }
+        } else if constexpr (PASS == 3) {
           const size_t row = (size_t)n * a.P + L.p_off + p0 + pix;
 #pragma unroll
           for (int f = 0; f < FT; ++f) {
@@ -1200,7 +1257,8 @@ size_t lfd_head_partial_floats(const lfd_head_desc_t* d) {
 
 static int head_forward_impl(const lfd_head_desc_t* d, int32_t pass, const lfd_head_level_ptrs_t* lv,
                              const float* ab1, const float* ab2, float* partial, float* out_cls, float* out_reg,
-                             const void* zeros, const LfdAppendTarget* dec, hipStream_t st) {
+                             const void* zeros, const LfdAppendTarget* dec, hipStream_t st, bool wide = false) {
+  // wide (lfd_head_forward_wide_f16): the output pass for 64 < final rows <= 128, k_head2 only
   if (!d || !lv || !zeros) return LFD_ERR_INVALID_ARGUMENT;
   if (d->head_channels != HC) return LFD_ERR_UNSUPPORTED;
   const int gsize = d->num_groups > 0 ? HC / d->num_groups : 0;
@@ -1241,7 +1299,9 @@ static int head_forward_impl(const lfd_head_desc_t* d, int32_t pass, const lfd_h
   if (pass == 3 && (!ab2 || (!dec && (!out_cls || !out_reg)))) return LFD_ERR_INVALID_ARGUMENT;
   if ((d->final_reg_rows != 0 && d->final_reg_rows != 4) || d->final_cls_rows < 0) return LFD_ERR_INVALID_ARGUMENT;
   const int ft = (d->final_reg_rows + d->final_cls_rows + 31) / 32;
-  if (pass == 3 && (ft < 1 || ft > 2)) return LFD_ERR_UNSUPPORTED;
+  if (pass == 3 && (ft < 1 || ft > (wide ? 4 : 2))) return LFD_ERR_UNSUPPORTED;
+  if (wide && ft <= 2) return LFD_ERR_UNSUPPORTED;      // up to 64 rows: lfd_head_forward_f16 serves them
+  if (wide && d->final_cls_rows > d->cls_channels) return LFD_ERR_INVALID_ARGUMENT;
   if (pass < 1 || pass > 3) return LFD_ERR_INVALID_ARGUMENT;
   if (head2_enabled() && gshift >= 3) {
     // wave-per-32-pixels kernel, all levels in one launch: work items = 4 consecutive chunks of one level
@@ -1271,10 +1331,14 @@ static int head_forward_impl(const lfd_head_desc_t* d, int32_t pass, const lfd_h
       if (a1) return launch_head2<3, 1, true, true, true>(a, st);
       return fold ? launch_head2<3, 1, true, true>(a, st) : launch_head2<3, 1, true>(a, st);
     }
+    if (wide) {
+      if (ft == 3) return a1 ? launch_head2<3, 3, false, true, true>(a, st) : (fold ? launch_head2<3, 3, false, true>(a, st) : launch_head2<3, 3>(a, st));
+      return a1 ? launch_head2<3, 4, false, true, true>(a, st) : (fold ? launch_head2<3, 4, false, true>(a, st) : launch_head2<3, 4>(a, st));
+    }
     if (ft == 2) return a1 ? launch_head2<3, 2, false, true, true>(a, st) : (fold ? launch_head2<3, 2, false, true>(a, st) : launch_head2<3, 2>(a, st));
     return a1 ? launch_head2<3, 1, false, true, true>(a, st) : (fold ? launch_head2<3, 1, false, true>(a, st) : launch_head2<3, 1>(a, st));
   }
-  if (dec) return LFD_ERR_UNSUPPORTED;
+  if (dec || wide) return LFD_ERR_UNSUPPORTED;     // (k_head's output pass holds at most two final tiles)
   // one launch per tap-channel class (64 / 128): homogeneous tiles, compile-time ring geometry
   for (int cin = 64; cin <= 128; cin += 64) {
     a.grp_n = 0;
@@ -1297,6 +1361,11 @@ int lfd_head_forward_f16(const lfd_head_desc_t* d, int32_t pass, const lfd_head_
                          const float* ab1, const float* ab2, float* partial, float* out_cls, float* out_reg,
                          const void* zeros, lfd_stream_t stream) {
   return head_forward_impl(d, pass, lv, ab1, ab2, partial, out_cls, out_reg, zeros, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int lfd_head_forward_wide_f16(const lfd_head_desc_t* d, const lfd_head_level_ptrs_t* lv, const float* ab1, const float* ab2,
+                              float* out_cls, float* out_reg, const void* zeros, lfd_stream_t stream) {
+  return head_forward_impl(d, 3, lv, ab1, ab2, nullptr, out_cls, out_reg, zeros, nullptr, reinterpret_cast<hipStream_t>(stream), true);
 }
 
 int lfd_head_forward_decode_f16(const lfd_head_desc_t* d, const lfd_head_level_ptrs_t* lv, const float* ab1,

@@ -428,6 +428,7 @@ _SIGNATURES = {
     'lfd_stem_faster_fused_f16': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'lfd_head_partial_floats': (_SZ, [C.POINTER(HeadDesc)]),
     'lfd_head_forward_f16': (C.c_int, [C.POINTER(HeadDesc), _I32, C.POINTER(HeadLevelPtrs), _P, _P, _P, _P, _P, _P, _P]),
+    'lfd_head_forward_wide_f16': (C.c_int, [C.POINTER(HeadDesc), C.POINTER(HeadLevelPtrs), _P, _P, _P, _P, _P, _P]),
     'lfd_head_forward_decode_f16': (C.c_int, [C.POINTER(HeadDesc), C.POINTER(HeadLevelPtrs), _P, _P, _P, _P, _P,
                                               C.POINTER(DetectDesc), _P, _P, _SZ, _P]),
     'lfd_groupnorm_finalize': (C.c_int, [C.POINTER(HeadDesc), _P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _F, _P, _P]),

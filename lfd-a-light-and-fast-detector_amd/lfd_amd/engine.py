@@ -26,6 +26,9 @@ IN_NCHW_F32, IN_NHWC_F16, IN_NHWC_U8 = 0, 1, 2
 _UNION = ('IoULoss', 'GIoULoss', 'DIoULoss', 'CIoULoss')
 
 
+MAX_FINAL_ROWS = 128     # final conv rows of one tower (4 regression rows + class channels when merged): lfd_head_forward_wide_f16
+
+
 class Unsupported(RuntimeError):
     """a module configuration the fused plan does not cover (a RuntimeError, so callers that expect the reference's error
     type keep working); anything else -- HIP out of memory, a library load failure -- is NOT this type"""
@@ -440,17 +443,25 @@ class EnginePlan(object):
                 # final rows = [reg x4][cls xC']: the 4 reg rows land in one lane -> one float4 store
                 fw = torch.cat([rconv.weight.detach().float(), cconv.weight.detach().float()], 0)
                 fb = torch.cat([rconv.bias.detach().float(), cconv.bias.detach().float()], 0)
-                if cc + 4 > 64:
-                    _unsupported('num classes + 4 > 64 with a merged head')
+                if cc + 4 > MAX_FINAL_ROWS:
+                    _unsupported('num classes + 4 > %d with a merged head (%d class channels)' % (MAX_FINAL_ROWS, cc))
+                self._check_wide_rows(cc + 4)
                 towers.append(make_tower(merge_path, fw, fb, 4, cc, scale))
             else:
                 cconv, rconv = cls_path[2 * lstep], reg_path[2 * lstep]
-                if cc > 64:
-                    _unsupported('more than 64 classification channels')
+                if cc > MAX_FINAL_ROWS:
+                    _unsupported('more than %d classification channels (%d)' % (MAX_FINAL_ROWS, cc))
+                self._check_wide_rows(cc)
                 towers.append(make_tower(cls_path, cconv.weight.detach().float(), cconv.bias.detach().float(), 0, cc, None))
                 towers.append(make_tower(reg_path, rconv.weight.detach().float(), rconv.bias.detach().float(), 4, 0, scale))
             lv.towers = towers
             self.levels.append(lv)
+
+    def _check_wide_rows(self, rows):
+        """more than 64 final rows run in lfd_head_forward_wide_f16, which only the wave-per-32-pixels kernel serves"""
+        if rows > 64 and 128 // self.head_groups < 8:
+            _unsupported('a head with more than 64 output rows (%d) needs GroupNorm groups of at least 8 channels, not %d '
+                         '(GroupNorm(%d, 128))' % (rows, 128 // self.head_groups, self.head_groups))
 
     @staticmethod
     def _static_affine(conv, norm):
@@ -588,6 +599,10 @@ class EnginePlan(object):
             ddesc, meta, out = decode
             check(l.lfd_head_forward_decode_f16(C.byref(d), lv, ptr(ab1), ptr(ab2), None, None, ptr(z), C.byref(ddesc),
                                                 ptr(meta), ptr(out.ws), out.ws.numel(), sp), 'lfd_head_forward_decode_f16')
+            return
+        if d.final_reg_rows + d.final_cls_rows > 64:      # 3 or 4 tiles of final rows: the wide output pass
+            check(l.lfd_head_forward_wide_f16(C.byref(d), lv, ptr(ab1), ptr(ab2), ptr(st.cls), ptr(st.reg), ptr(z), sp),
+                  'lfd_head_forward_wide_f16')
             return
         check(l.lfd_head_forward_f16(C.byref(d), 3, lv, ptr(ab1), ptr(ab2), None, ptr(st.cls), ptr(st.reg), ptr(z), sp),
               'lfd_head_forward_f16(pass 3)')
