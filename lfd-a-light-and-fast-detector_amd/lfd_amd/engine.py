@@ -19,11 +19,10 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, netdesc, ops
 from ._lib import check, lib, ptr, stream_ptr
 
 IN_NCHW_F32, IN_NHWC_F16, IN_NHWC_U8 = 0, 1, 2
-_UNION = ('IoULoss', 'GIoULoss', 'DIoULoss', 'CIoULoss')
 
 
 MAX_FINAL_ROWS = 128     # final conv rows of one tower (4 regression rows + class channels when merged): lfd_head_forward_wide_f16
@@ -85,6 +84,11 @@ def _pad_wb(w, b):
     bp = torch.zeros(co, dtype=b.dtype, device=b.device)
     bp[:b.shape[0]] = b
     return wp, bp
+
+
+def _padded(layer):
+    """(input, output) channels of a netdesc.Layer as the kernels see them"""
+    return pad_channels(layer.conv.in_channels), pad_channels(layer.conv.out_channels)
 
 
 def fold_conv_norm(conv, norm):
@@ -222,16 +226,10 @@ class EnginePlan(object):
         self.input_channels = bb._input_channels
         if bb._norm_cfg is not None and bb._norm_cfg['type'] != 'BatchNorm2d':
             _unsupported('backbone norm must be BatchNorm2d (or None)')
-        if type(bb._stem[2 if bb._norm_cfg is not None else 1]).__name__ != 'ReLU':
+        net = netdesc.backbone_layers(bb)
+        if not net.stem[0].relu:
             _unsupported('activation must be ReLU')
-        has_norm = bb._norm_cfg is not None
-        step = 3 if has_norm else 2
-        stem_convs = []
-        for i, (k, s, cin, cout) in enumerate(bb.stem_spec()):
-            conv = bb._stem[i * step]
-            norm = bb._stem[i * step + 1] if has_norm else None
-            stem_convs.append((k, s, pad_channels(cin), pad_channels(cout)) + fold_conv_norm(conv, norm))
-        import os
+        stem_convs = [(l.ks, l.stride) + _padded(l) + fold_conv_norm(l.conv, l.norm) for l in net.stem]
         self.fuse_blocks = os.environ.get('LFD_FUSED_BLOCK', '1') == '1'
         self.stem_first = None   # (C, w1, b1, w2|None, b2|None)
         self.stem_ref = [(k, s, w, b) for (k, s, _ci, _co, w, b) in stem_convs]   # folded fp32 stem convs, in order
@@ -273,7 +271,6 @@ class EnginePlan(object):
         # ---- whole 'faster' stem in one kernel when it has the fusable shape
         self.stem_fused = None
         self.stem_second = None
-        import os
         # (RGB only: the one-launch stem gathers 3-channel frames; a gray 'faster' stem runs its second pair on lfd_conv2d)
         if (self.input_channels == 3 and bb._stem_mode == 'faster' and c0 in (32, 64) and self.stem_first[3] is not None and len(self.convs) == 1
                 and self.convs[0].tail is not None and self.convs[0].cin == c0 and self.convs[0].cout == c0
@@ -286,79 +283,66 @@ class EnginePlan(object):
             self.stem_fused = (c0,) + tuple(self.stem_first[1:]) + (cv.w, cv.b, cv.tail[0], cv.tail[1], cv.dst)
         # ---- stages
         self.taps = []
+        self.tap_channels = []
         self.tap_ready_after = []
-        for i, nblk in enumerate(bb._body_architecture):
-            for j in range(nblk):
-                blk = getattr(bb, 'stage%d' % i)[j]
-                x_in = cur
-                ident = x_in
-                fuse_ds = None
-                if blk._downsample is not None:
-                    dconv = blk._downsample[0]
-                    dnorm = blk._downsample[1] if len(blk._downsample) > 1 else None
-                    w, b = fold_conv_norm(dconv, dnorm)
-                    c1 = blk._conv1
-                    P = pad_channels
-                    if (c1.kernel_size[0] == 3 and c1.stride[0] == 2 and c1.out_channels == dconv.out_channels and
-                            c1.in_channels == dconv.in_channels and blk.num_convs == 2 and
-                            (P(c1.in_channels), P(c1.out_channels)) in _DS_PAIRS):
-                        # identity branch rides on the block's 3x3 stride-2 conv (one launch, one input read)
-                        ident = new_buf()
-                        self.buf_channels[ident] = P(dconv.out_channels)
-                        self.buf_scale[ident] = self.buf_scale[x_in] * 2
-                        fuse_ds = (ops.pack_conv_weight(w).to(dev), b.to(dev).contiguous(), ident, w)
-                    else:
-                        ident = self._add_conv(x_in, new_buf, P(dconv.in_channels), P(dconv.out_channels), 1, 2, False, w, b)
-                nconv = blk.num_convs
-                y = x_in
-                ci = 1
-                if (self.fuse_blocks and blk._downsample is None and nconv == 2 and
-                        all(getattr(blk, '_conv%d' % q).kernel_size[0] == 3 and getattr(blk, '_conv%d' % q).stride[0] == 1 and
-                            pad_channels(getattr(blk, '_conv%d' % q).in_channels) == 64 and
-                            pad_channels(getattr(blk, '_conv%d' % q).out_channels) == 64
-                            for q in (1, 2))):
-                    # whole residual block in one launch (csrc/block.hip): the intermediate map never reaches HBM
-                    w1, b1 = fold_conv_norm(blk._conv1, getattr(blk, '_norm1', None))
-                    w2, b2 = fold_conv_norm(blk._conv2, getattr(blk, '_norm2', None))
-                    y = self._add_conv(x_in, new_buf, 64, 64, 3, 1, True, w1, b1, res=x_in)
-                    self.convs[-1].blk = (ops.pack_conv_weight(w2).to(dev), b2.to(dev).contiguous(), w2)
-                    ci = nconv + 1
-                while ci <= nconv:
-                    conv = getattr(blk, '_conv%d' % ci)
-                    norm = getattr(blk, '_norm%d' % ci, None)
-                    w, b = fold_conv_norm(conv, norm)
-                    last = ci == nconv
-                    tail = None
-                    if (not last) and ci + 1 < nconv:
-                        nxt = getattr(blk, '_conv%d' % (ci + 1))
-                        if (nxt.kernel_size[0] == 1 and nxt.out_channels == conv.out_channels and
-                                _tail_supported(pad_channels(conv.in_channels), pad_channels(conv.out_channels), conv.kernel_size[0],
-                                                conv.stride[0])):
-                            w2, b2 = fold_conv_norm(nxt, getattr(blk, '_norm%d' % (ci + 1), None))
-                            tail = (ops.pack_conv_weight(w2).to(dev), b2.to(dev), True, w2)   # FastBlock 3x3 -> 1x1
-                    y = self._add_conv(y, new_buf, pad_channels(conv.in_channels), pad_channels(conv.out_channels), conv.kernel_size[0],
-                                       conv.stride[0], True, w, b, tail=tail, res=ident if last else None,
-                                       ds=fuse_ds if ci == 1 else None)
-                    if (fuse_ds is not None and ci == 2 and last and tail is None and conv.kernel_size[0] == 3 and conv.stride[0] == 1
-                            and len(self.convs) >= 2 and self.convs[-2].ds is fuse_ds and self.convs[-2].cin == 64
-                            and self.convs[-2].cout == 64 and self.convs[-1].cin == 64 and self.convs[-1].cout == 64):
-                        # the whole downsample block can run as ONE launch (csrc/down.hip): conv 1 + branch + this conv.  Both
-                        # launches stay in the plan; run_backbone picks per shape (the fused kernel wins on the larger maps)
-                        self.convs[-2].down = len(self.convs) - 1
-                    ci += 2 if tail is not None else 1
-                if (blk._downsample is None and nconv == 2 and len(self.convs) >= 2 and
-                        all(c_.cin == 128 and c_.cout == 128 and c_.ks == 3 and c_.stride == 1 and c_.tail is None and c_.ds is None
-                            and c_.relu for c_ in self.convs[-2:])
-                        and self.convs[-2].src == x_in and self.convs[-2].res is None and self.convs[-1].src == self.convs[-2].dst
-                        and self.convs[-1].res == x_in and self.convs[-1].dst == y):
-                    # a 128-channel block without branch: ONE launch on small maps (csrc/block128.hip); both launches stay in
-                    # the plan, run_backbone picks per shape
-                    self.convs[-2].blk128 = len(self.convs) - 1
-                cur = y
-                if (i, j) in [tuple(t) for t in bb._out_indices]:
-                    self.taps.append(cur)
-                    self.tap_channels = getattr(self, 'tap_channels', []) + [getattr(blk, '_conv%d' % blk.num_convs).out_channels]
-                    self.tap_ready_after.append(len(self.convs))   # number of conv launches that must precede
+        for blk in net.blocks:
+            x_in = cur
+            ident = x_in
+            fuse_ds = None
+            nconv = len(blk.convs)
+            if blk.downsample is not None:
+                dconv, c1 = blk.downsample.conv, blk.convs[0]
+                w, b = fold_conv_norm(dconv, blk.downsample.norm)
+                if (c1.ks == 3 and c1.stride == 2 and c1.conv.out_channels == dconv.out_channels and
+                        c1.conv.in_channels == dconv.in_channels and nconv == 2 and _padded(c1) in _DS_PAIRS):
+                    # identity branch rides on the block's 3x3 stride-2 conv (one launch, one input read)
+                    ident = new_buf()
+                    self.buf_channels[ident] = pad_channels(dconv.out_channels)
+                    self.buf_scale[ident] = self.buf_scale[x_in] * 2
+                    fuse_ds = (ops.pack_conv_weight(w).to(dev), b.to(dev).contiguous(), ident, w)
+                else:
+                    ident = self._add_conv(x_in, new_buf, *_padded(blk.downsample), 1, 2, False, w, b)
+            y = x_in
+            ci = 0
+            if (self.fuse_blocks and blk.downsample is None and nconv == 2 and
+                    all(l.ks == 3 and l.stride == 1 and _padded(l) == (64, 64) for l in blk.convs)):
+                # whole residual block in one launch (csrc/block.hip): the intermediate map never reaches HBM
+                (w1, b1), (w2, b2) = [fold_conv_norm(l.conv, l.norm) for l in blk.convs]
+                y = self._add_conv(x_in, new_buf, 64, 64, 3, 1, True, w1, b1, res=x_in)
+                self.convs[-1].blk = (ops.pack_conv_weight(w2).to(dev), b2.to(dev).contiguous(), w2)
+                ci = nconv
+            while ci < nconv:
+                l = blk.convs[ci]
+                w, b = fold_conv_norm(l.conv, l.norm)
+                last = ci == nconv - 1
+                tail = None
+                if ci + 2 < nconv:
+                    nxt = blk.convs[ci + 1]
+                    if nxt.ks == 1 and nxt.conv.out_channels == l.conv.out_channels and _tail_supported(*_padded(l), l.ks, l.stride):
+                        w2, b2 = fold_conv_norm(nxt.conv, nxt.norm)
+                        tail = (ops.pack_conv_weight(w2).to(dev), b2.to(dev), True, w2)   # FastBlock 3x3 -> 1x1
+                y = self._add_conv(y, new_buf, *_padded(l), l.ks, l.stride, True, w, b, tail=tail, res=ident if last else None,
+                                   ds=fuse_ds if ci == 0 else None)
+                if (fuse_ds is not None and ci == 1 and last and tail is None and l.ks == 3 and l.stride == 1
+                        and len(self.convs) >= 2 and self.convs[-2].ds is fuse_ds and self.convs[-2].cin == 64
+                        and self.convs[-2].cout == 64 and self.convs[-1].cin == 64 and self.convs[-1].cout == 64):
+                    # the whole downsample block can run as ONE launch (csrc/down.hip): conv 1 + branch + this conv.  Both
+                    # launches stay in the plan; run_backbone picks per shape (the fused kernel wins on the larger maps)
+                    self.convs[-2].down = len(self.convs) - 1
+                ci += 2 if tail is not None else 1
+            if (blk.downsample is None and nconv == 2 and len(self.convs) >= 2 and
+                    all(c_.cin == 128 and c_.cout == 128 and c_.ks == 3 and c_.stride == 1 and c_.tail is None and c_.ds is None
+                        and c_.relu for c_ in self.convs[-2:])
+                    and self.convs[-2].src == x_in and self.convs[-2].res is None and self.convs[-1].src == self.convs[-2].dst
+                    and self.convs[-1].res == x_in and self.convs[-1].dst == y):
+                # a 128-channel block without branch: ONE launch on small maps (csrc/block128.hip); both launches stay in
+                # the plan, run_backbone picks per shape
+                self.convs[-2].blk128 = len(self.convs) - 1
+            cur = y
+            if blk.tap:
+                self.taps.append(cur)
+                self.tap_channels.append(blk.convs[-1].conv.out_channels)
+                self.tap_ready_after.append(len(self.convs))   # number of conv launches that must precede
         self.num_bufs = nbuf[0]
 
     def _add_conv(self, src, new_buf, cin, cout, ks, stride, relu, w, b, tail=None, res=None, ds=None):
@@ -397,37 +381,28 @@ class EnginePlan(object):
             if g * self.head_groups != 128 or (g & (g - 1)) or g > 32:
                 _unsupported('GroupNorm group size must be a power of two <= 32')
         self.head_gn = ncfg is not None and ncfg['type'] == 'GroupNorm'
-        union = head._regression_loss_type in _UNION
         cc = head.num_cls_channels
         self.cls_channels = cc
-        has_norm = ncfg is not None
-        lstep = 3 if has_norm else 2
         self.levels = []
-        for i in range(head._num_heads):
+        for i, d in enumerate(netdesc.lfd_head_levels(neck, head)):
             lv = _HeadLevel()
-            nseq = getattr(neck, 'neck%d' % i)
-            nconv = nseq[0]
-            wn, bn = fold_conv_norm(nconv, nseq[1] if neck._norm_cfg is not None else None)
-            lv.cin = pad_channels(nconv.in_channels)
+            wn, bn = fold_conv_norm(d.neck.conv, d.neck.norm)
+            lv.cin = pad_channels(d.neck.conv.in_channels)
             if lv.cin not in (64, 128):
                 _unsupported('backbone tap channels must be 64 or 128')
             lv.wn = ops.pack_conv_weight(wn).to(dev)
             lv.bn = bn.to(dev)
             lv.src = self.taps[i]
-            cls_path = getattr(head, 'head%d_classification_path' % i)
-            reg_path = getattr(head, 'head%d_regression_path' % i)
-            merge_path = getattr(head, 'head%d_merge_path' % i)
-            scale = head._scales[i]._scale if union else None
+            scale = d.scale._scale if d.scale is not None else None
             towers = []
 
-            def make_tower(seq, final_w, final_b, reg_rows, cls_rows, scale_p):
+            def make_tower(layers, final_w, final_b, reg_rows, cls_rows, scale_p):
                 t = _Tower()
-                c1, c2 = seq[0], seq[lstep]
+                c1, c2 = layers[0].conv, layers[1].conv
                 t.w1 = ops.pack_conv_weight(c1.weight.detach().float()).to(dev)
                 t.w2 = ops.pack_conv_weight(c2.weight.detach().float()).to(dev)
                 t.w1p = t.w2p = None
-                t.norm1 = seq[1] if has_norm else None
-                t.norm2 = seq[lstep + 1] if has_norm else None
+                t.norm1, t.norm2 = layers[0].norm, layers[1].norm
                 t.static_ab = None
                 if not self.head_gn:   # BatchNorm / no norm: per-channel affine known ahead of time
                     t.static_ab = [self._static_affine(c1, t.norm1), self._static_affine(c2, t.norm2)]
@@ -438,22 +413,21 @@ class EnginePlan(object):
                 t.reg_rows, t.cls_rows, t.scale = reg_rows, cls_rows, scale_p
                 return t
 
+            cconv, rconv = d.cls_out, d.reg_out
             if head._merge_path_flag:
-                cconv, rconv = cls_path[0], reg_path[0]
                 # final rows = [reg x4][cls xC']: the 4 reg rows land in one lane -> one float4 store
                 fw = torch.cat([rconv.weight.detach().float(), cconv.weight.detach().float()], 0)
                 fb = torch.cat([rconv.bias.detach().float(), cconv.bias.detach().float()], 0)
                 if cc + 4 > MAX_FINAL_ROWS:
                     _unsupported('num classes + 4 > %d with a merged head (%d class channels)' % (MAX_FINAL_ROWS, cc))
                 self._check_wide_rows(cc + 4)
-                towers.append(make_tower(merge_path, fw, fb, 4, cc, scale))
+                towers.append(make_tower(d.merge, fw, fb, 4, cc, scale))
             else:
-                cconv, rconv = cls_path[2 * lstep], reg_path[2 * lstep]
                 if cc > MAX_FINAL_ROWS:
                     _unsupported('more than %d classification channels (%d)' % (MAX_FINAL_ROWS, cc))
                 self._check_wide_rows(cc)
-                towers.append(make_tower(cls_path, cconv.weight.detach().float(), cconv.bias.detach().float(), 0, cc, None))
-                towers.append(make_tower(reg_path, rconv.weight.detach().float(), rconv.bias.detach().float(), 4, 0, scale))
+                towers.append(make_tower(d.cls, cconv.weight.detach().float(), cconv.bias.detach().float(), 0, cc, None))
+                towers.append(make_tower(d.reg, rconv.weight.detach().float(), rconv.bias.detach().float(), 4, 0, scale))
             lv.towers = towers
             self.levels.append(lv)
 

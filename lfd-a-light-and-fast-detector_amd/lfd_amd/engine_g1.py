@@ -22,11 +22,10 @@ import ctypes as C
 import torch
 import torch.nn.functional as F
 
-from . import _lib, engine, ops
+from . import _lib, engine, netdesc, ops
 from ._lib import check, lib, ptr, stream_ptr
 
 _LO = 2048.0    # 2^11
-_UNION = ('IoULoss', 'GIoULoss', 'DIoULoss', 'CIoULoss')
 
 
 def _split(t):
@@ -84,44 +83,32 @@ def _gn(x, norm):
 def lfd_forward_g1(model, x):
     """x: NCHW fp32 on the device.  Returns (cls [N,P,C'] fp32, reg [N,P,4] fp32, sizes) like engine.lfd_forward."""
     _lib.require_cuda(x, 'lfd_forward_g1')
-    bb, neck, head = model._backbone, model._neck, model._head
-    has_norm = bb._norm_cfg is not None
-    step = 3 if has_norm else 2
+    net = netdesc.backbone_layers(model._backbone)
     y = x.float().permute(0, 2, 3, 1).contiguous()
-    for i, (k, s, cin, cout) in enumerate(bb.stem_spec()):
-        w, b = engine.fold_conv_norm(bb._stem[i * step], bb._stem[i * step + 1] if has_norm else None)
-        y = conv_g1(y, w, b, s).relu_()
+    for l in net.stem:
+        y = conv_g1(y, *engine.fold_conv_norm(l.conv, l.norm), l.stride).relu_()
     feats = []
-    taps = [tuple(t) for t in bb._out_indices]
-    for i, nblk in enumerate(bb._body_architecture):
-        for j in range(nblk):
-            blk = getattr(bb, 'stage%d' % i)[j]
-            ident = y
-            if blk._downsample is not None:
-                w, b = engine.fold_conv_norm(blk._downsample[0], blk._downsample[1] if len(blk._downsample) > 1 else None)
-                ident = conv_g1(y, w, b, blk._downsample[0].stride[0])
-            o = y
-            for ci in range(1, blk.num_convs + 1):
-                conv = getattr(blk, '_conv%d' % ci)
-                w, b = engine.fold_conv_norm(conv, getattr(blk, '_norm%d' % ci, None))
-                o = conv_g1(o, w, b, conv.stride[0])
-                if ci < blk.num_convs:
-                    o = o.relu_()
-            y = (o + ident).relu_()
-            if (i, j) in taps:
-                feats.append(y)
-    union = head._regression_loss_type in _UNION
-    has_hn = head._norm_cfg is not None
-    lstep = 3 if has_hn else 2
+    for blk in net.blocks:
+        ident = y
+        if blk.downsample is not None:
+            d = blk.downsample
+            ident = conv_g1(y, *engine.fold_conv_norm(d.conv, d.norm), d.stride)
+        o = y
+        for l in blk.convs:
+            o = conv_g1(o, *engine.fold_conv_norm(l.conv, l.norm), l.stride)
+            if l is not blk.convs[-1]:
+                o = o.relu_()
+        y = (o + ident).relu_()
+        if blk.tap:
+            feats.append(y)
     cls_l, reg_l, sizes = [], [], []
 
-    def tower(seq, t, nlayers):
-        for l in range(nlayers):
-            conv = seq[l * lstep]
+    def tower(layers, t):
+        for layer in layers:
+            conv, nm = layer.conv, layer.norm
             bias = conv.bias.detach().float() if conv.bias is not None else torch.zeros(conv.out_channels, device=t.device)
             t = conv_g1(t, conv.weight.detach().float(), bias, 1)
-            if has_hn:
-                nm = seq[l * lstep + 1]
+            if nm is not None:
                 if isinstance(nm, torch.nn.GroupNorm):
                     t = _gn(t, nm)
                 else:
@@ -130,24 +117,16 @@ def lfd_forward_g1(model, x):
             t = t.relu_()
         return t
 
-    nl = head._num_conv_layers
-    for i, f in enumerate(feats):
-        nseq = getattr(neck, 'neck%d' % i)
-        w, b = engine.fold_conv_norm(nseq[0], nseq[1] if neck._norm_cfg is not None else None)
-        t = conv_g1(f, w, b, 1).relu_()
-        cls_path = getattr(head, 'head%d_classification_path' % i)
-        reg_path = getattr(head, 'head%d_regression_path' % i)
-        if head._merge_path_flag:
-            tt = tower(getattr(head, 'head%d_merge_path' % i), t, nl)
-            cconv, rconv = cls_path[0], reg_path[0]
-            c = conv_g1(tt, cconv.weight.detach().float(), cconv.bias.detach().float(), 1)
-            r = conv_g1(tt, rconv.weight.detach().float(), rconv.bias.detach().float(), 1)
+    for f, d in zip(feats, netdesc.lfd_head_levels(model._neck, model._head)):
+        t = conv_g1(f, *engine.fold_conv_norm(d.neck.conv, d.neck.norm), 1).relu_()
+        if d.merge:
+            tc = tr = tower(d.merge, t)
         else:
-            cconv, rconv = cls_path[nl * lstep], reg_path[nl * lstep]
-            c = conv_g1(tower(cls_path, t, nl), cconv.weight.detach().float(), cconv.bias.detach().float(), 1)
-            r = conv_g1(tower(reg_path, t, nl), rconv.weight.detach().float(), rconv.bias.detach().float(), 1)
-        if union:
-            r = r * head._scales[i]._scale.detach().float()
+            tc, tr = tower(d.cls, t), tower(d.reg, t)
+        c = conv_g1(tc, d.cls_out.weight.detach().float(), d.cls_out.bias.detach().float(), 1)
+        r = conv_g1(tr, d.reg_out.weight.detach().float(), d.reg_out.bias.detach().float(), 1)
+        if d.scale is not None:
+            r = r * d.scale._scale.detach().float()
         sizes.append((c.shape[1], c.shape[2]))
         cls_l.append(c.reshape(c.shape[0], -1, c.shape[3]))
         reg_l.append(r.reshape(r.shape[0], -1, 4))

@@ -24,10 +24,9 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, engine, ops
+from . import _lib, engine, netdesc, ops
 from ._lib import check, lib, ptr, stream_ptr
 
-_UNION = engine._UNION
 _LO = 2048.0
 
 
@@ -264,12 +263,11 @@ class PlanesPlan(object):
                 if not any(True for _ in mod.children()) and type(mod).__name__ not in (
                         'Conv2d', 'BatchNorm2d', 'GroupNorm', 'ReLU', 'Scale', 'Identity', 'Sequential', 'ModuleList'):
                     raise Unsupported('module %s (activation must be ReLU)' % type(mod).__name__)
-        has_norm = bb._norm_cfg is not None
-        step = 3 if has_norm else 2
-        spec = list(bb.stem_spec())
-        folded = [engine.fold_conv_norm(bb._stem[i * step], bb._stem[i * step + 1] if has_norm else None) for i in range(len(spec))]
+        net = netdesc.backbone_layers(bb)
+        spec = net.stem
+        folded = [engine.fold_conv_norm(l.conv, l.norm) for l in spec]
         # ---- stem: pairs conv3x3 s2 -> conv1x1 (lfd_resnet.py:356-413)
-        if len(spec) not in (2, 4) or [(k, s) for k, s, _, _ in spec] != [(3, 2), (1, 1)] * (len(spec) // 2):
+        if len(spec) not in (2, 4) or [(l.ks, l.stride) for l in spec] != [(3, 2), (1, 1)] * (len(spec) // 2):
             raise Unsupported('stem mode')
         c = folded[0][0].shape[0]
         if c not in (32, 64) or tuple(folded[1][0].shape[:2]) != (c, c):
@@ -299,59 +297,53 @@ class PlanesPlan(object):
                 f.tail = pair2
                 self.stem2x = f
         # ---- residual stages (lfd_resnet.py:96-154, :458-468, :488-501)
-        taps = [tuple(t) for t in bb._out_indices]
         self.taps = []
-        for i, nblk in enumerate(bb._body_architecture):
-            for j in range(nblk):
-                blk = getattr(bb, 'stage%d' % i)[j]
-                ident, y = cur, cur
-                for ci in range(1, blk.num_convs + 1):
-                    conv = getattr(blk, '_conv%d' % ci)
-                    w, b = engine.fold_conv_norm(conv, getattr(blk, '_norm%d' % ci, None))
-                    ks, st = conv.kernel_size[0], conv.stride[0]
-                    last = ci == blk.num_convs
-                    ds = None
-                    if ci == 1 and blk._downsample is not None:
-                        dconv = blk._downsample[0]
-                        if dconv.kernel_size[0] != 1 or dconv.stride[0] != 2 or (ks, st) != (3, 2) or last:
-                            raise Unsupported('downsample branch')
-                        ds = engine.fold_conv_norm(dconv, blk._downsample[1] if len(blk._downsample) > 1 else None)
-                    elif ci > 1 and st != 1:
-                        raise Unsupported('stride inside a block')
-                    if ci == 1 and blk._downsample is None and st != 1:
-                        raise Unsupported('strided block without a downsample branch')
-                    op = self._conv(y, w, b, ks, st, True, res=ident if last else None, ds=ds)
-                    if (ci == 2 and last and blk._downsample is None and self.ops[-2].dst == y and self.ops[-2].src == ident and
-                            op.res == ident and
-                            all(q.ks == 3 and q.stride == 1 and q.cin == 64 and q.cout == 64 and q.relu and q.tail is None
-                                and q.ds is None and q.out_mode == 0 for q in self.ops[-2:])):
-                        self.block_pairs[len(self.ops) - 2] = len(self.ops) - 1
-                    y = op.dst
-                    if ds is not None:
-                        ident = op.ds_dst
-                cur = y
-                if (i, j) in taps:
-                    self.taps.append(cur)
-                    self.tap_ready.append(len(self.ops) - 1)
+        for blk in net.blocks:
+            ident, y = cur, cur
+            for ci, l in enumerate(blk.convs, 1):
+                w, b = engine.fold_conv_norm(l.conv, l.norm)
+                ks, st = l.ks, l.stride
+                last = ci == len(blk.convs)
+                ds = None
+                if ci == 1 and blk.downsample is not None:
+                    if blk.downsample.ks != 1 or blk.downsample.stride != 2 or (ks, st) != (3, 2) or last:
+                        raise Unsupported('downsample branch')
+                    ds = engine.fold_conv_norm(blk.downsample.conv, blk.downsample.norm)
+                elif ci > 1 and st != 1:
+                    raise Unsupported('stride inside a block')
+                if ci == 1 and blk.downsample is None and st != 1:
+                    raise Unsupported('strided block without a downsample branch')
+                op = self._conv(y, w, b, ks, st, True, res=ident if last else None, ds=ds)
+                if (ci == 2 and last and blk.downsample is None and self.ops[-2].dst == y and self.ops[-2].src == ident and
+                        op.res == ident and
+                        all(q.ks == 3 and q.stride == 1 and q.cin == 64 and q.cout == 64 and q.relu and q.tail is None
+                            and q.ds is None and q.out_mode == 0 for q in self.ops[-2:])):
+                    self.block_pairs[len(self.ops) - 2] = len(self.ops) - 1
+                y = op.dst
+                if ds is not None:
+                    ident = op.ds_dst
+            cur = y
+            if blk.tap:
+                self.taps.append(cur)
+                self.tap_ready.append(len(self.ops) - 1)
         # ---- neck + head (simple_neck.py:67-74, lfd_head.py:164-185)
         if head._norm_cfg is None or head._conv_kernel_size != 1:
             raise Unsupported('head towers must be 1x1 conv + GroupNorm')
         nl = head._num_conv_layers
-        union = head._regression_loss_type in _UNION
         self.cls_channels = head.num_cls_channels
         self.num_levels = head._num_heads
         ccls = self.cls_channels
 
-        def tower(seq, t, first_tail_of=None):
+        def tower(layers, t, first_tail_of=None):
             """conv -> GroupNorm -> ReLU layers: every conv stores its pre-normalisation output + the GroupNorm sums, its
             consumer normalises the tile it has just fetched.  Returns (buffer, pending (sums index, norm)).  With
             `first_tail_of` = (neck w, b, src) the neck conv and the first tower conv are one launch."""
             pend = None
-            for l in range(nl):
-                conv, norm = seq[l * 3], seq[l * 3 + 1]
+            for l, layer in enumerate(layers):
+                conv, norm = layer.conv, layer.norm
                 if not isinstance(norm, nn.GroupNorm):
                     raise Unsupported('head norm must be GroupNorm')
-                if not isinstance(seq[l * 3 + 2], nn.ReLU):
+                if not layer.relu:
                     raise Unsupported('head activation must be ReLU')
                 bias = conv.bias.detach().float() if conv.bias is not None else torch.zeros(conv.out_channels, device=conv.weight.device)
                 w = conv.weight.detach().float()
@@ -365,20 +357,17 @@ class PlanesPlan(object):
             return t, pend
 
         self.head_start = len(self.ops)
-        for i, f in enumerate(self.taps):
+        for i, (f, d) in enumerate(zip(self.taps, netdesc.lfd_head_levels(neck, head))):
             first_op = len(self.ops)
-            nseq = getattr(neck, 'neck%d' % i)
-            nw, nb = engine.fold_conv_norm(nseq[0], nseq[1] if neck._norm_cfg is not None else None)
+            nw, nb = engine.fold_conv_norm(d.neck.conv, d.neck.norm)
             if nw.shape[0] != 128 or nw.shape[2] != 1:
                 raise Unsupported('neck must be 1x1 -> 128')
-            cls_path = getattr(head, 'head%d_classification_path' % i)
-            reg_path = getattr(head, 'head%d_regression_path' % i)
-            scale = head._scales[i]._scale.detach().float().reshape(1).to(self.device) if union else None
+            scale = d.scale._scale.detach().float().reshape(1).to(self.device) if d.scale is not None else None
+            cconv, rconv = d.cls_out, d.reg_out
             if head._merge_path_flag:
                 if nl < 1:
                     raise Unsupported('merge path without tower convs')
-                tt, pend = tower(getattr(head, 'head%d_merge_path' % i), None, first_tail_of=(nw, nb, f))
-                cconv, rconv = cls_path[0], reg_path[0]
+                tt, pend = tower(d.merge, None, first_tail_of=(nw, nb, f))
                 if cconv.kernel_size[0] != 1 or rconv.kernel_size[0] != 1 or ccls + 4 > 64:
                     raise Unsupported('output convs')
                 w = torch.cat([cconv.weight.detach().float(), rconv.weight.detach().float()], 0)
@@ -386,12 +375,11 @@ class PlanesPlan(object):
                 self._conv(tt, w, b, 1, 1, False, out32=(i, ccls, 4, scale), gnin=pend)
             else:
                 t = self._conv(f, nw, nb, 1, 1, True).dst
-                cconv, rconv = cls_path[nl * 3], reg_path[nl * 3]
                 if cconv.kernel_size[0] != 1 or rconv.kernel_size[0] != 1 or ccls > 64:
                     raise Unsupported('output convs')
                 if nl < 1:
                     raise Unsupported('towers without convs')
-                (tc, pc), (tr, pr) = tower(cls_path, t), tower(reg_path, t)
+                (tc, pc), (tr, pr) = tower(d.cls, t), tower(d.reg, t)
                 self._conv(tc, cconv.weight.detach().float(), cconv.bias.detach().float(), 1, 1, False, out32=(i, ccls, 0, None), gnin=pc)
                 self._conv(tr, rconv.weight.detach().float(), rconv.bias.detach().float(), 1, 1, False, out32=(i, 0, 4, scale), gnin=pr)
             self.level_ops.append((first_op, len(self.ops)))

@@ -14,14 +14,14 @@ Measured (tests/test_gpu_precise.py): raw logits within 1e-5 of the fp
 shapes; cost: bench.py `precise` key.  Decode + NMS are the same fp32 kernels as in fp16 mode (ops.detect_batched).
 """
 import ctypes as C
+import os
 
 import torch
 import torch.nn as nn
 
-from . import _lib, engine, ops
+from . import _lib, engine, netdesc, ops
 from ._lib import check, lib, ptr, stream_ptr
 
-_UNION = engine._UNION
 _LO = 2048.0
 
 
@@ -125,49 +125,42 @@ class PrecisePlan(object):
         if bb._norm_cfg is not None and bb._norm_cfg['type'] != 'BatchNorm2d':
             engine._unsupported('backbone norm must be BatchNorm2d (or None)')
         engine.require_narrow(bb, "precision='fp32_storage'")
-        has_norm = bb._norm_cfg is not None
-        step = 3 if has_norm else 2
+        net = netdesc.backbone_layers(bb)
         cur = 'input'
-        spec = list(bb.stem_spec())
-        folded = [engine.fold_conv_norm(bb._stem[i * step], bb._stem[i * step + 1] if has_norm else None) for i in range(len(spec))]
-        import os
+        spec = net.stem
+        folded = [engine.fold_conv_norm(l.conv, l.norm) for l in spec]
         fuse_tail = os.environ.get('LFD_P32_TAIL', '1') != '0'
         i = 0
         while i < len(spec):
-            k, s, cin, cout = spec[i]
+            k, s = spec[i].ks, spec[i].stride
             w, b = folded[i]
             # a stem pair conv3x3 s2 -> conv1x1 (64 -> 64) runs as ONE launch: the fp32 intermediate stays in LDS
             tail = None
-            if (fuse_tail and i + 1 < len(spec) and (k, s) == (3, 2) and w.shape[0] == 64 and spec[i + 1][0] == 1 and spec[i + 1][1] == 1
+            if (fuse_tail and i + 1 < len(spec) and (k, s) == (3, 2) and w.shape[0] == 64 and (spec[i + 1].ks, spec[i + 1].stride) == (1, 1)
                     and tuple(folded[i + 1][0].shape[:2]) == (64, 64)):
                 tail = folded[i + 1]
             if i == 0:
-                if (k, s, cin) != (3, 2, bb._input_channels):
+                if (k, s, spec[0].conv.in_channels) != (3, 2, bb._input_channels):
                     engine._unsupported('first stem conv must be 3x3 stride 2 on the frame')
                 cur = self._conv(cur, w, b, 3, 2, True, patch=True, tail=tail)
             else:
                 cur = self._conv(cur, w, b, k, s, True, tail=tail)
             i += 2 if tail is not None else 1
-        taps = [tuple(t) for t in bb._out_indices]
         self.taps = []
-        for i, nblk in enumerate(bb._body_architecture):
-            for j in range(nblk):
-                blk = getattr(bb, 'stage%d' % i)[j]
-                ident = cur
-                if blk._downsample is not None:
-                    dconv = blk._downsample[0]
-                    w, b = engine.fold_conv_norm(dconv, blk._downsample[1] if len(blk._downsample) > 1 else None)
-                    ident = self._conv(cur, w, b, dconv.kernel_size[0], dconv.stride[0], False)
-                y = cur
-                for ci in range(1, blk.num_convs + 1):
-                    conv = getattr(blk, '_conv%d' % ci)
-                    w, b = engine.fold_conv_norm(conv, getattr(blk, '_norm%d' % ci, None))
-                    last = ci == blk.num_convs
-                    # lfd_resnet.py:140-152: out = relu(norm_n(conv_n(...)) + identity)
-                    y = self._conv(y, w, b, conv.kernel_size[0], conv.stride[0], True, res=ident if last else None)
-                cur = y
-                if (i, j) in taps:
-                    self.taps.append(cur)
+        for blk in net.blocks:
+            ident = cur
+            if blk.downsample is not None:
+                d = blk.downsample
+                w, b = engine.fold_conv_norm(d.conv, d.norm)
+                ident = self._conv(cur, w, b, d.ks, d.stride, False)
+            y = cur
+            for l in blk.convs:
+                w, b = engine.fold_conv_norm(l.conv, l.norm)
+                # lfd_resnet.py:140-152: out = relu(norm_n(conv_n(...)) + identity)
+                y = self._conv(y, w, b, l.ks, l.stride, True, res=ident if l is blk.convs[-1] else None)
+            cur = y
+            if blk.tap:
+                self.taps.append(cur)
 
     def _build(self, model):
         bb, neck, head = model._backbone, model._neck, model._head
@@ -175,18 +168,13 @@ class PrecisePlan(object):
             engine._unsupported("precision='fp32_storage' covers SimpleNeck + LFDHead (every shipped configuration)")
         self._build_backbone(bb)
         # ---- neck + head (simple_neck.py:67-74, lfd_head.py:164-185)
-        ncfg = head._norm_cfg
-        has_hn = ncfg is not None
-        lstep = 3 if has_hn else 2
-        nl = head._num_conv_layers
         ks_h = head._conv_kernel_size
-        union = head._regression_loss_type in _UNION
         self.cls_channels = head.num_cls_channels
         self.num_levels = head._num_heads
 
-        def tower(seq, t):
-            for l in range(nl):
-                conv, norm = seq[l * lstep], (seq[l * lstep + 1] if has_hn else None)
+        def tower(layers, t):
+            for layer in layers:
+                conv, norm = layer.conv, layer.norm
                 if isinstance(norm, nn.GroupNorm):
                     bias = conv.bias.detach().float() if conv.bias is not None else torch.zeros(conv.out_channels)
                     t = self._conv(t, conv.weight.detach().float(), bias.to(conv.weight.device), ks_h, 1, False)
@@ -196,19 +184,15 @@ class PrecisePlan(object):
                     t = self._conv(t, w, b, ks_h, 1, True)
             return t
 
-        for i, f in enumerate(self.taps):
-            nseq = getattr(neck, 'neck%d' % i)
-            w, b = engine.fold_conv_norm(nseq[0], nseq[1] if neck._norm_cfg is not None else None)
+        for i, (f, d) in enumerate(zip(self.taps, netdesc.lfd_head_levels(neck, head))):
+            w, b = engine.fold_conv_norm(d.neck.conv, d.neck.norm)
             t = self._conv(f, w, b, 1, 1, True)
-            cls_path = getattr(head, 'head%d_classification_path' % i)
-            reg_path = getattr(head, 'head%d_regression_path' % i)
-            scale = head._scales[i]._scale.detach().float().reshape(1).to(self.device) if union else None
+            scale = d.scale._scale.detach().float().reshape(1).to(self.device) if d.scale is not None else None
+            cconv, rconv = d.cls_out, d.reg_out
             if head._merge_path_flag:
-                tt = tower(getattr(head, 'head%d_merge_path' % i), t)
-                cconv, rconv, tc, tr = cls_path[0], reg_path[0], tt, tt
+                tc = tr = tower(d.merge, t)
             else:
-                cconv, rconv = cls_path[nl * lstep], reg_path[nl * lstep]
-                tc, tr = tower(cls_path, t), tower(reg_path, t)
+                tc, tr = tower(d.cls, t), tower(d.reg, t)
             kf = cconv.kernel_size[0]
             self._conv(tc, cconv.weight.detach().float(), cconv.bias.detach().float(), kf, 1, False, out='cls', level=i)
             self._conv(tr, rconv.weight.detach().float(), rconv.bias.detach().float(), kf, 1, False, scale=scale, out='reg',
@@ -286,7 +270,6 @@ class _State(object):
 
 def planes_enabled():
     """host-side A/B switch (tests, tools): LFD_P32_PLANES=0 keeps the fp32-tensor plan of this file"""
-    import os
     return os.environ.get('LFD_P32_PLANES', '1') != '0'
 
 

@@ -20,9 +20,7 @@ unsupported module raises.
 import torch
 import torch.nn as nn
 
-from . import _lib, engine, ops
-
-_UNION = ('IoULoss', 'GIoULoss', 'DIoULoss', 'CIoULoss')
+from . import _lib, engine, netdesc, ops
 
 
 def _unsupported(msg):
@@ -77,50 +75,28 @@ class _Conv(object):
         return y
 
 
-def _split_sequential(seq):
-    """nn.Sequential of [conv, (norm), (ReLU)] groups / bare ReLU / MaxPool -> list of ('conv', conv, norm, relu) |
-    ('relu',) | ('pool',) steps"""
-    mods = list(seq)
-    steps, i = [], 0
-    while i < len(mods):
-        m = mods[i]
-        if isinstance(m, nn.Conv2d):
-            norm, relu, j = None, False, i + 1
-            if j < len(mods) and isinstance(mods[j], (nn.BatchNorm2d, nn.GroupNorm)):
-                norm, j = mods[j], j + 1
-            if j < len(mods) and isinstance(mods[j], nn.ReLU):
-                relu, j = True, j + 1
-            steps.append(('conv', m, norm, relu))
-            i = j
-        elif isinstance(m, nn.ReLU):
-            steps.append(('relu',))
-            i += 1
-        elif isinstance(m, nn.MaxPool2d):
-            if (m.kernel_size, m.stride, m.padding) != (3, 2, 1):
-                _unsupported('MaxPool2d %s' % (m,))
-            steps.append(('pool',))
-            i += 1
-        else:
-            _unsupported('module %s in a neck / head path' % type(m).__name__)
-    return steps
+def _steps(seq):
+    try:
+        return netdesc.split_sequential(seq)
+    except netdesc.UnknownModule as e:
+        _unsupported(str(e))
 
 
 class _Path(object):
-    """a compiled nn.Sequential"""
+    """the compiled steps (netdesc.split_sequential) of an nn.Sequential"""
 
-    def __init__(self, seq, cin_have, dev, f32out_last=False):
+    def __init__(self, steps, cin_have, dev, f32out_last=False):
         self.ops = []
         c = cin_have
-        steps = _split_sequential(seq)
         for k, s in enumerate(steps):
-            if s[0] == 'conv':
-                layer = _Conv(s[1], s[2], s[3], c, dev, f32out=f32out_last and k == len(steps) - 1)
+            if isinstance(s, netdesc.Layer):
+                layer = _Conv(s.conv, s.norm, s.relu, c, dev, f32out=f32out_last and k == len(steps) - 1)
                 self.ops.append(layer)
                 c = layer.cout
             else:
-                self.ops.append(s[0])
+                self.ops.append(s)
         self.cout = c
-        self.inplace_relu_first = bool(steps) and steps[0][0] == 'relu'
+        self.inplace_relu_first = bool(steps) and steps[0] == 'relu'
 
     def __call__(self, x):
         for o in self.ops:
@@ -150,7 +126,7 @@ class SiblingPlan(object):
         kind = type(neck).__name__
         self.neck_kind = kind
         if kind == 'SimpleNeck':
-            self.laterals = [_Path(getattr(neck, 'neck%d' % i), c, self.dev) for i, c in enumerate(self.tap_have)]
+            self.laterals = [_Path(_steps(getattr(neck, 'neck%d' % i)), c, self.dev) for i, c in enumerate(self.tap_have)]
             self.outs, self.num_inputs, self.num_outputs = None, len(self.laterals), len(self.laterals)
             self.bottom_up = False
             self.merge = False
@@ -161,13 +137,13 @@ class SiblingPlan(object):
         self.num_inputs, self.num_outputs = neck._num_inputs, neck._num_outputs
         self.extra_on_input = neck._extra_on_input
         self.bottom_up = bool(getattr(neck, '_neighbouring_mode', False))
-        self.laterals = [_Path(getattr(neck, 'lateral%d' % i), c, self.dev) for i, c in enumerate(self.tap_have)]
+        self.laterals = [_Path(_steps(getattr(neck, 'lateral%d' % i)), c, self.dev) for i, c in enumerate(self.tap_have)]
         cn = self.laterals[0].cout
         self.outs, self.out_real = [], []
         for i in range(self.num_outputs):
             from_input = i == self.num_inputs and self.extra_on_input
             src_c = self.tap_have[-1] if from_input else (self.outs[-1].cout if i >= self.num_inputs else cn)
-            path = _Path(getattr(neck, 'fpn_out%d' % i), src_c, self.dev)
+            path = _Path(_steps(getattr(neck, 'fpn_out%d' % i)), src_c, self.dev)
             self.outs.append(path)
             if any(isinstance(o, _Conv) for o in path.ops) or i < self.num_inputs:
                 self.out_real.append(neck._num_output_channels)
@@ -205,8 +181,8 @@ class SiblingPlan(object):
         cn = self.laterals[0].cout
         self.levels = []
         if kind == 'FCOSHead':
-            cls_t = _Path(nn.Sequential(*list(head._classification_path)), cn, self.dev)
-            reg_t = _Path(nn.Sequential(*list(head._regression_path)), cn, self.dev)
+            cls_t = _Path(_steps(head._classification_path), cn, self.dev)
+            reg_t = _Path(_steps(head._regression_path), cn, self.dev)
             cls_o = _Conv(head._classification, None, False, cls_t.cout, self.dev, f32out=True)
             ctr_o = _Conv(head._centerness, None, False, cls_t.cout, self.dev, f32out=True)
             reg_o = _Conv(head._regression, None, False, reg_t.cout, self.dev, f32out=True)
@@ -220,34 +196,31 @@ class SiblingPlan(object):
             _unsupported('head %s' % kind)
         self.has_ctr = False
         self.num_cls_channels = head.num_cls_channels
-        union = head._regression_loss_type in _UNION
         cache = {}
 
-        def compiled(seq, cin, f32out_last=False):
-            key = (id(seq), cin, f32out_last)
+        def compiled(layers, cin, f32out_last=False):
+            """towers shared between the levels (share_head_flag) are compiled once"""
+            key = (tuple(id(l.conv) for l in layers), cin, f32out_last)
             if key not in cache:
-                cache[key] = _Path(seq, cin, self.dev, f32out_last=f32out_last)
+                cache[key] = _Path(_steps(layers), cin, self.dev, f32out_last=f32out_last)
             return cache[key]
 
-        for i in range(head._num_heads):
-            merge = getattr(head, 'head%d_merge_path' % i)
-            cls_p = getattr(head, 'head%d_classification_path' % i)
-            reg_p = getattr(head, 'head%d_regression_path' % i)
+        for i, d in enumerate(netdesc.lfd_head_levels(None, head)):
             # (a parameter update changes the plan signature, so the value read here cannot go stale)
-            lv = dict(exp=False, scale=float(head._scales[i]._scale.detach()) if union else 1.0, ctr_o=None)
+            lv = dict(exp=False, scale=float(d.scale._scale.detach()) if d.scale is not None else 1.0, ctr_o=None)
             if head._merge_path_flag:
-                lv['merge'] = compiled(merge, cn)
+                lv['merge'] = compiled(d.merge, cn)
                 c = lv['merge'].cout
             else:
                 lv['merge'] = None
                 c = cn
             if kind == 'LFDHeadV1':     # towers end without the output convs: those are per-level members
-                lv['cls_p'], lv['reg_p'] = compiled(cls_p, c), compiled(reg_p, c)
-                lv['cls_o'] = _Conv(head._classifiers[i], None, False, lv['cls_p'].cout, self.dev, f32out=True)
-                lv['reg_o'] = _Conv(head._regressors[i], None, False, lv['reg_p'].cout, self.dev, f32out=True)
+                lv['cls_p'], lv['reg_p'] = compiled(d.cls, c), compiled(d.reg, c)
+                lv['cls_o'] = _Conv(d.cls_out, None, False, lv['cls_p'].cout, self.dev, f32out=True)
+                lv['reg_o'] = _Conv(d.reg_out, None, False, lv['reg_p'].cout, self.dev, f32out=True)
             else:
-                lv['cls_p'] = compiled(cls_p, c, True)
-                lv['reg_p'] = compiled(reg_p, c, True)
+                lv['cls_p'] = compiled(d.cls + [netdesc.layer(d.cls_out)], c, True)
+                lv['reg_p'] = compiled(d.reg + [netdesc.layer(d.reg_out)], c, True)
             self.levels.append(lv)
 
     def run_head(self, feats):

@@ -28,10 +28,8 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, engine, engine_p32, engine_sibling
+from . import _lib, engine, engine_p32, netdesc
 from ._lib import check, ptr
-
-_UNION = engine._UNION
 
 
 def merge_enabled():
@@ -51,8 +49,8 @@ _LAUNCH = {'gn': 'lfd_p32_groupnorm_relu_f32', 'merge': 'lfd_p32_conv2d_merge_nh
 
 def _steps(seq):
     try:
-        return engine_sibling._split_sequential(seq)
-    except RuntimeError as e:       # the fp16 layer engine's wording; this mode raises engine.Unsupported like engine_p32
+        return netdesc.split_sequential(seq)
+    except netdesc.UnknownModule as e:       # this mode raises engine.Unsupported like engine_p32
         engine._unsupported(str(e))
 
 
@@ -130,23 +128,23 @@ class SiblingPrecisePlan(engine_p32.PrecisePlan):
             shared[key, 'gn'] = self.ops[-1]
         return dst
 
-    def _path(self, seq, src, scale=None, out=None, level=None):
-        """an nn.Sequential of [conv, (norm), (ReLU)] groups / bare in-place ReLU / MaxPool2d(3, 2, 1) from buffer `src`;
-        out: its last conv writes the level's rows of that output tensor (with `scale` in its epilogue)"""
-        steps = _steps(seq)
-        if out is not None and (not steps or steps[-1][0] != 'conv' or isinstance(steps[-1][2], nn.GroupNorm)):
+    def _path(self, steps, src, scale=None, out=None, level=None):
+        """the steps (netdesc.split_sequential) of an nn.Sequential of [conv, (norm), (ReLU)] groups / bare in-place ReLU /
+        MaxPool2d(3, 2, 1) from buffer `src`; out: its last conv writes the level's rows of that output tensor (with `scale`
+        in its epilogue)"""
+        if out is not None and (not steps or not isinstance(steps[-1], netdesc.Layer) or isinstance(steps[-1].norm, nn.GroupNorm)):
             engine._unsupported('a head path must end in its output conv')
         cur = src
         for k, s in enumerate(steps):
-            if s[0] == 'relu':
+            if s == 'relu':
                 self._simple('relu', cur)       # nn.ReLU(inplace=True): the tensor it reads changes too (by design)
-            elif s[0] == 'pool':
+            elif s == 'pool':
                 dst = self._new_buf(self.buf_channels[cur], self.buf_scale[cur] * 2)
                 self._simple('pool', cur, dst)
                 cur = dst
             else:
                 last = out is not None and k == len(steps) - 1
-                cur = self._layer(cur, s[1], s[2], s[3], scale=scale if last else None, out=out if last else None,
+                cur = self._layer(cur, s.conv, s.norm, s.relu, scale=scale if last else None, out=out if last else None,
                                   level=level if last else None)
         return cur
 
@@ -154,7 +152,7 @@ class SiblingPrecisePlan(engine_p32.PrecisePlan):
     def _build_neck(self, neck):
         kind = type(neck).__name__
         if kind == 'SimpleNeck':
-            return [self._path(getattr(neck, 'neck%d' % i), t) for i, t in enumerate(self.taps)]
+            return [self._path(_steps(getattr(neck, 'neck%d' % i)), t) for i, t in enumerate(self.taps)]
         if kind not in ('FPN', 'SimpleFPN'):
             engine._unsupported('neck %s' % kind)
         ni, no = neck._num_inputs, neck._num_outputs
@@ -164,15 +162,15 @@ class SiblingPrecisePlan(engine_p32.PrecisePlan):
         lat = [None] * ni
         # top-down: lateral[i-1] += up(lateral[i]) walking from the coarsest level, so each merge reads an already-merged map
         for i in range(ni - 1, -1, -1):
-            seq = getattr(neck, 'lateral%d' % i)
-            steps = _steps(seq)
+            steps = _steps(getattr(neck, 'lateral%d' % i))
             merged = not bottom_up and i < ni - 1
-            fuse = merged and self.merge and len(steps) == 1 and steps[0][0] == 'conv' and steps[0][1].kernel_size == (1, 1) \
-                and steps[0][1].stride == (1, 1) and not isinstance(steps[0][2], nn.GroupNorm)
+            one = steps[0] if len(steps) == 1 and isinstance(steps[0], netdesc.Layer) else None
+            fuse = merged and self.merge and one is not None and one.conv.kernel_size == (1, 1) and one.conv.stride == (1, 1) \
+                and not isinstance(one.norm, nn.GroupNorm)
             if fuse:
-                lat[i] = self._layer(self.taps[i], steps[0][1], steps[0][2], steps[0][3], up=lat[i + 1])
+                lat[i] = self._layer(self.taps[i], one.conv, one.norm, one.relu, up=lat[i + 1])
             else:
-                lat[i] = self._path(seq, self.taps[i])
+                lat[i] = self._path(steps, self.taps[i])
                 if merged:
                     self._simple('upadd', lat[i + 1], lat[i])
         if bottom_up:       # simple_fpn.py:147-151 neighbouring_mode: from the finest level, each reads its UNmerged neighbour
@@ -186,12 +184,12 @@ class SiblingPrecisePlan(engine_p32.PrecisePlan):
                 src = outs[-1]
             else:
                 src = lat[i]
-            outs.append(self._path(getattr(neck, 'fpn_out%d' % i), src))
+            outs.append(self._path(_steps(getattr(neck, 'fpn_out%d' % i)), src))
         return outs
 
     # ------------------------------------------------------------------ head
-    def _scale(self, head, i):
-        return head._scales[i]._scale.detach().float().reshape(1).to(self.device)
+    def _scale(self, scale):
+        return scale._scale.detach().float().reshape(1).to(self.device)
 
     def _build_head(self, head, feats):
         kind = type(head).__name__
@@ -201,31 +199,28 @@ class SiblingPrecisePlan(engine_p32.PrecisePlan):
         if kind == 'FCOSHead':
             self.has_ctr = True
             self.cls_channels = head._num_classes
-            cls_t, reg_t = nn.Sequential(*list(head._classification_path)), nn.Sequential(*list(head._regression_path))
+            cls_t, reg_t = _steps(head._classification_path), _steps(head._regression_path)
             for i, f in enumerate(feats):
                 tc, tr = self._path(cls_t, f), self._path(reg_t, f)
                 self._layer(tc, head._classification, None, False, out='cls', level=i)
                 self._layer(tc, head._centerness, None, False, out='ctr', level=i)
                 # fcos_head.py:145-146 `scales[i](regression(x)).float().exp()`: conv, bias, Scale in the epilogue, then expf
-                self._layer(tr, head._regression, None, False, scale=self._scale(head, i), out='reg', level=i)
+                self._layer(tr, head._regression, None, False, scale=self._scale(head._scales[i]), out='reg', level=i)
                 self._simple('exp', None, out='reg', level=i)
             return
         if kind not in ('LFDHead', 'LFDHeadV1'):
             engine._unsupported('head %s' % kind)
         self.cls_channels = head.num_cls_channels
-        union = head._regression_loss_type in _UNION
-        for i, f in enumerate(feats):
-            scale = self._scale(head, i) if union else None
-            cls_p = getattr(head, 'head%d_classification_path' % i)
-            reg_p = getattr(head, 'head%d_regression_path' % i)
-            t = self._path(getattr(head, 'head%d_merge_path' % i), f) if head._merge_path_flag else f
+        for i, (f, d) in enumerate(zip(feats, netdesc.lfd_head_levels(None, head))):
+            scale = self._scale(d.scale) if d.scale is not None else None
+            t = self._path(_steps(d.merge), f)
             if kind == 'LFDHeadV1':       # towers end without the output convs: those are per-level members
-                tc, tr = self._path(cls_p, t), self._path(reg_p, t)
-                self._layer(tc, head._classifiers[i], None, False, out='cls', level=i)
-                self._layer(tr, head._regressors[i], None, False, scale=scale, out='reg', level=i)
+                tc, tr = self._path(_steps(d.cls), t), self._path(_steps(d.reg), t)
+                self._layer(tc, d.cls_out, None, False, out='cls', level=i)
+                self._layer(tr, d.reg_out, None, False, scale=scale, out='reg', level=i)
             else:
-                self._path(cls_p, t, out='cls', level=i)
-                self._path(reg_p, t, scale=scale, out='reg', level=i)
+                self._path(_steps(d.cls + [netdesc.layer(d.cls_out)]), t, out='cls', level=i)
+                self._path(_steps(d.reg + [netdesc.layer(d.reg_out)]), t, scale=scale, out='reg', level=i)
 
     def _build(self, model):
         self._build_backbone(model._backbone)

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import engine, engine_p32, engine_sibling, engine_sibling_p32, ops, parallel, train_engine
+from .. import engine, engine_p32, engine_sibling, engine_sibling_p32, netdesc, ops, parallel, train_engine
 from ..data import DeviceAnnotations
 from .utils import multiclass_nms  # noqa: F401  (kept importable like the reference module)
 
@@ -321,7 +321,7 @@ class LFD(nn.Module):
             r = getattr(head, 'head%d_regression_path' % i)(t)
             if hasattr(head, '_classifiers'):      # LFDHeadV1: per-level output convs outside the (shared) towers
                 c, r = head._classifiers[i](c), head._regressors[i](r)
-            if head._regression_loss_type in _UNION:
+            if hasattr(head, '_scales'):           # the IoU-family regression losses: a learnable Scale per level
                 r = head._scales[i](r)
             self._head_indexes_to_feature_map_sizes[i] = (c.shape[2], c.shape[3])
             cls_l.append(c.permute(0, 2, 3, 1).reshape(c.shape[0], -1, c.shape[1]))
@@ -329,24 +329,22 @@ class LFD(nn.Module):
         return torch.cat(cls_l, 1), torch.cat(reg_l, 1)
 
     def _backbone_train_torch(self, x):
-        bb = self._backbone
-        y = bb._stem(x)
+        net = netdesc.backbone_layers(self._backbone)
+        y = self._backbone._stem(x)
         feats = []
-        taps = [tuple(t) for t in bb._out_indices]
-        for i, nblk in enumerate(bb._body_architecture):
-            for j in range(nblk):
-                blk = getattr(bb, 'stage%d' % i)[j]
-                ident = y if blk._downsample is None else blk._downsample(y)
-                o = y
-                for ci in range(1, blk.num_convs + 1):
-                    o = getattr(blk, '_conv%d' % ci)(o)
-                    if blk._norm_cfg is not None:
-                        o = getattr(blk, '_norm%d' % ci)(o)
-                    if ci < blk.num_convs:
-                        o = F.relu(o)
-                y = F.relu(o + ident)
-                if (i, j) in taps:
-                    feats.append(y)
+
+        def conv_norm(l, t):
+            t = l.conv(t)
+            return t if l.norm is None else l.norm(t)
+
+        for blk in net.blocks:
+            ident = y if blk.downsample is None else conv_norm(blk.downsample, y)
+            o = y
+            for l in blk.convs[:-1]:
+                o = F.relu(conv_norm(l, o))
+            y = F.relu(conv_norm(blk.convs[-1], o) + ident)
+            if blk.tap:
+                feats.append(y)
         return feats
 
     # ------------------------------------------------------------------ point grid / targets

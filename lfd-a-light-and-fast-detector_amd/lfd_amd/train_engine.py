@@ -27,7 +27,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import netdesc, ops
 
 LOSS_SCALE = 1024.0   # initial value; power of two; activation gradients are stored as fp16 * loss_scale()
 _scale_state = {'value': LOSS_SCALE}
@@ -197,26 +197,16 @@ class _Builder(object):
 
 
 def _build_backbone(b, backbone):
-    cur = 0
-    mods = list(backbone._stem)
-    for i in range(0, len(mods), 3):          # (conv, norm, activation) triples
-        cur = b.add(mods[i], mods[i + 1], True, cur)
-    taps = {}
-    want = [tuple(t) for t in backbone._out_indices]
-    for si, nblk in enumerate(backbone._body_architecture):
-        for bi in range(nblk):
-            blk = getattr(backbone, 'stage%d' % si)[bi]
-            ident = cur
-            if blk._downsample is not None:
-                ident = b.add(blk._downsample[0], blk._downsample[1], False, cur)
-            a = cur
-            for ci in range(1, blk.num_convs + 1):
-                last = ci == blk.num_convs
-                a = b.add(getattr(blk, '_conv%d' % ci), getattr(blk, '_norm%d' % ci), True, a, ident if last else None)
-            cur = a
-            if (si, bi) in want:
-                taps[(si, bi)] = cur
-    return [taps[t] for t in want]
+    net = netdesc.backbone_layers(backbone)
+    cur = _tower(b, net.stem, 0)
+    taps = []
+    for blk in net.blocks:
+        ident = cur if blk.downsample is None else _tower(b, [blk.downsample], cur)
+        for l in blk.convs:
+            cur = b.add(l.conv, l.norm, l.relu, cur, ident if l is blk.convs[-1] else None)
+        if blk.tap:
+            taps.append(cur)
+    return taps
 
 
 def build_units(backbone):
@@ -226,13 +216,10 @@ def build_units(backbone):
     return b.units, taps
 
 
-def _tower(b, path, cur):
-    """the (conv, norm, ReLU) triples of a head path as units from activation `cur` on -> the last activation (LFDHead's
-    classification / regression paths end in their output conv, which is no unit: it goes into an _Out record)"""
-    mods = list(path)
-    n3 = len(mods) - (1 if mods and isinstance(mods[-1], nn.Conv2d) else 0)
-    for i in range(0, n3, 3):
-        cur = b.add(mods[i], mods[i + 1], True, cur)
+def _tower(b, layers, cur):
+    """a chain of netdesc.Layers as units from activation `cur` on -> the last activation"""
+    for l in layers:
+        cur = b.add(l.conv, l.norm, l.relu, cur)
     return cur
 
 
@@ -242,16 +229,14 @@ def _out(level, convs, src, scale):
     return o
 
 
-def _lfd_head_level(b, head, i, src):
-    """LFDHead's level i on activation `src` (lfd_head.py:164-185): the merge path's units, the two towers' units -> the level's
-    _Out records: ONE (rows of both output convs) when they read the same activation, else two"""
-    cur = _tower(b, getattr(head, 'head%d_merge_path' % i), src)
-    cpath, rpath = getattr(head, 'head%d_classification_path' % i), getattr(head, 'head%d_regression_path' % i)
-    csrc, rsrc = _tower(b, cpath, cur), _tower(b, rpath, cur)
-    scale = head._scales[i] if hasattr(head, '_scales') else None
+def _lfd_head_level(b, d, i, src):
+    """level i of an LFDHead (netdesc.Level `d`) on activation `src` (lfd_head.py:164-185): the merge path's units, the two
+    towers' units -> the level's _Out records: ONE (rows of both output convs) when they read the same activation, else two"""
+    cur = _tower(b, d.merge, src)
+    csrc, rsrc = _tower(b, d.cls, cur), _tower(b, d.reg, cur)
     if csrc == rsrc:
-        return [_out(i, [('cls', cpath[-1]), ('reg', rpath[-1])], csrc, scale)]
-    return [_out(i, [('cls', cpath[-1])], csrc, scale), _out(i, [('reg', rpath[-1])], rsrc, scale)]
+        return [_out(i, [('cls', d.cls_out), ('reg', d.reg_out)], csrc, d.scale)]
+    return [_out(i, [('cls', d.cls_out)], csrc, d.scale), _out(i, [('reg', d.reg_out)], rsrc, d.scale)]
 
 
 def build_network(model):
@@ -259,10 +244,9 @@ def build_network(model):
     b = _Builder()
     taps = _build_backbone(b, model._backbone)
     outs = []
-    for i, tap in enumerate(taps):
+    for i, (tap, d) in enumerate(zip(taps, netdesc.lfd_head_levels(model._neck, model._head))):
         b.level = i
-        nk = getattr(model._neck, 'neck%d' % i)
-        outs += _lfd_head_level(b, model._head, i, b.add(nk[0], nk[1], True, tap))
+        outs += _lfd_head_level(b, d, i, _tower(b, [d.neck], tap))
     return b.units, outs
 
 
@@ -1650,8 +1634,13 @@ def build_detector(backbone, neck, head):
     """-> _DetectorPlan of an FCOSHead: per level, in FCOSHead.forward's order (fcos_head.py:129-150), the classification tower's
     units, the regression tower's units and two output records, (cls + ctr) then (reg, with the level's Scale); 3x3 output convs
     of FCOS_OUT_ROWS rows (what fcos_head_supported admits fits them)"""
+    try:
+        cls_t, reg_t = netdesc.split_sequential(head._classification_path), netdesc.split_sequential(head._regression_path)
+    except netdesc.UnknownModule as e:      # (fcos_head_supported admits conv -> GroupNorm -> ReLU towers only)
+        raise RuntimeError('build_detector: %s' % e)
+
     def level(b, i, src):
-        csrc, rsrc = _tower(b, head._classification_path, src), _tower(b, head._regression_path, src)
+        csrc, rsrc = _tower(b, cls_t, src), _tower(b, reg_t, src)
         return [_out(i, [('cls', head._classification), ('ctr', head._centerness)], csrc, None),
                 _out(i, [('reg', head._regression)], rsrc, head._scales[i])]
 
@@ -1731,8 +1720,9 @@ def lfd_head_supported(backbone, neck, head):
 def build_lfd_detector(backbone, neck, head):
     """-> _DetectorPlan of an LFDHead: per level, in LFD._forward_train's order (lfd.py:526-542), the merge path's units, the two
     towers' units and the output records exactly as build_network forms them; 1x1 output convs of 64 or 128 rows"""
+    levels = netdesc.lfd_head_levels(None, head)
     return _build_detector(backbone, neck, head, _LFDGlue, 1, dict(cls=head.num_cls_channels, reg=4),
-                           lambda b, i, src: _lfd_head_level(b, head, i, src))
+                           lambda b, i, src: _lfd_head_level(b, levels[i], i, src))
 
 
 def _lfd_out_levels(plan, starts, raws, dys=None, store=None):
