@@ -842,6 +842,19 @@ LFD_API int lfd_stem_conv_f16(const void* in, int32_t in_format, int32_t n, int3
                               int32_t channels, const void* w1_packed, const float* b1,
                               const void* w2_packed, const float* b2, void* out, lfd_stream_t stream);
 
+/* First layer of the torchvision-style ResNet: conv7x7 stride 2 pad 3 (3 -> 64) + BatchNorm (folded on the host) + ReLU on a
+ * frame (resnet.py:366-370, :470-473; csrc/stem7.hip).  in_format as lfd_stem_conv_f16 (uint8: simple_normalize on the load).
+ * w_packed: [2 = co / 32][10 k-steps][64 lanes][8] fp16, lane (hk, co % 32) slot j of k-step s = tap slot k = 16 s + 8 hk + j:
+ *   s < 7:  filter row ky = s, e = 8 hk + j                                   (e = 3 kx + c)
+ *   s >= 7: i = 8 (2 (s - 7) + hk) + j < 35: ky = i / 5, e = 16 + i % 5;  i >= 35: zero
+ * (engine_resnet.pack_stem7_weight); lfd_stem7_packed_weight_halfs() = 64 * 160 is its size.  bias fp32 [64].
+ * out: NHWC fp16 [n, (h+1)/2, (w+1)/2, 64].  The max-pool that follows is lfd_maxpool3x3s2_nhwc_f16.
+ * w_packed, bias, out: 16-byte aligned.  LFD_ERR_INVALID_ARGUMENT: a null pointer, n / h / w < 1, an in_format other than
+ * 0..2, misalignment -- checked on the host before any launch. */
+LFD_API int lfd_stem7_conv_f16(const void* in, int32_t in_format, int32_t n, int32_t h, int32_t w, const void* w_packed,
+                               const float* bias, void* out, lfd_stream_t stream);
+LFD_API size_t lfd_stem7_packed_weight_halfs(void);
+
 /* First stem unit of a one-channel (grayscale, input_channels = 1) model: conv3x3 s2 (1 -> C) + BN + ReLU, chained with
  * conv1x1 (C -> C) + BN + ReLU when w2_packed != NULL (lfd_resnet.py:356-374 'fast' stem; first half of the 'faster' stem
  * :376-395; csrc/stem_gray.hip).  The frame is one [n, h, w] plane -- NCHW [n,1,h,w] and NHWC [n,h,w,1] are the same bytes:

@@ -424,6 +424,8 @@ _SIGNATURES = {
     'lfd_stem_gray_bn_bwd_wgrad_rows': (C.c_int, [_P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _F, _I32, _I32, _P, _SZ, _P, _P, _P, _P]),
     'lfd_stem_conv_f16': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     'lfd_stem_gray_f16': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    'lfd_stem7_conv_f16': (C.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    'lfd_stem7_packed_weight_halfs': (_SZ, []),
     'lfd_pl_stem_gray_pair': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _I64, _P]),
     'lfd_stem_faster_fused_f16': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'lfd_head_partial_floats': (_SZ, [C.POINTER(HeadDesc)]),

@@ -264,6 +264,11 @@ def build_sibling(spec, B, N, H, M, L, seed=1, input_channels=3):
                      body_channels=list(bbk['body_channels']), out_indices=bbk['out_indices'], frozen_stages=-1,
                      activation_cfg=dict(type='ReLU', inplace=True), norm_cfg=dict(type='BatchNorm2d'),
                      init_with_weight_file=None, norm_eval=False)
+    return synthetic_weights(_sibling_behind(spec, bb, N, H, M, L), seed)
+
+
+def _sibling_behind(spec, bb, N, H, M, L):
+    """neck, head and meta-architecture of a SIBLINGS / RESNET_SIBLINGS entry around the backbone `bb`"""
     nk = dict(spec['neck'])
     kind = nk.pop('kind')
     if kind == 'SimpleNeck':
@@ -294,13 +299,18 @@ def build_sibling(spec, B, N, H, M, L, seed=1, input_channels=3):
         head = getattr(H, hkind)(num_input_channels=cn, num_heads=len(strides), activation_cfg=dict(type='ReLU', inplace=True),
                                  classification_loss_type=type(cls_loss).__name__,
                                  regression_loss_type=type(reg_loss).__name__, **hk)
+        if spec['meta'] == 'LFD':
+            return M.LFD(backbone=bb, neck=neck, head=head, num_classes=hk['num_classes'], regression_ranges=spec['regression_ranges'],
+                         gray_range_factors=spec['gray_range_factors'], range_assign_mode=spec['range_assign_mode'],
+                         point_strides=strides, classification_loss_func=cls_loss, regression_loss_func=reg_loss,
+                         distance_to_bbox_mode=spec['distance_to_bbox_mode'])
         model = M.LFDv2(backbone=bb, neck=neck, head=head, num_classes=hk['num_classes'],
                         regression_ranges=spec['regression_ranges'], gray_range_factors=spec['gray_range_factors'],
                         range_assign_mode=spec['range_assign_mode'], point_strides=strides, classification_loss_func=cls_loss,
                         regression_loss_func=reg_loss, distance_to_bbox_mode=spec['distance_to_bbox_mode'],
                         classification_threshold=0.05, nms_threshold=0.5, pre_nms_bbox_limit=spec['pre_nms_bbox_limit'],
                         post_nms_bbox_limit=spec['post_nms_bbox_limit'])
-    return synthetic_weights(model, seed)
+    return model
 
 
 def build_sibling_model(name, seed=1, input_channels=3):
@@ -308,3 +318,39 @@ def build_sibling_model(name, seed=1, input_channels=3):
     from .model import backbone as B, head as H, losses as L, neck as N
     from . import model as M
     return build_sibling(name, B, N, H, M, L, seed, input_channels=input_channels)
+
+
+# ------------------------------------------------------------------ the torchvision-style ResNet (resnet.py) under the siblings
+# ResNet-18 / 34 is the canonical FCOS / FPN backbone and the one that takes ImageNet-pretrained weights; no shipped config uses
+# it.  Three small compositions (tests, fixtures tests/golden/make_golden_resnet.py, tools/bench_resnet.py); out_indices are
+# (stage 1-based, block 0-based).
+RESNET_SIBLINGS = {
+    # FCOS: stages 2..4 (128 / 256 / 512 channels) -> FPN 128 with two conv extra levels -> GroupNorm FCOSHead
+    'R18_FCOS_FPN': dict(SIBLINGS['FCOS_FPN'], resnet=dict(depth=18, out_indices=((2, 1), (3, 1), (4, 1)))),
+    # LFDv2: the last block of stages 2..4 of a ResNet-34 -> SimpleFPN 64 (pooled extra level) -> LFDHead of 3x3 convs
+    'R34_LFDV2_SFPN': dict(SIBLINGS['LFDV2_SFPN'], resnet=dict(depth=34, out_indices=((2, 3), (3, 5), (4, 2)))),
+    # LFD: all four stages -> SimpleNeck(128) -> the WIDERFACE head (one class, merged 1x1 towers, GroupNorm(16))
+    'R18_LFD_SIMPLE': dict(meta='LFD', resnet=dict(depth=18, out_indices=((1, 1), (2, 1), (3, 1), (4, 1))),
+                           neck=dict(kind='SimpleNeck', num_neck_channels=128),
+                           head=dict(kind='LFDHead', num_classes=1, num_head_channels=128, num_conv_layers=2, conv_kernel_size=1,
+                                     norm_cfg=dict(type='GroupNorm', num_groups=16), share_head_flag=True, merge_path_flag=True),
+                           classification_loss_type='FocalLoss', regression_loss_type='IoULoss',
+                           regression_ranges=TT100K_RANGES, gray_range_factors=(0.9, 1.1), range_assign_mode='dist',
+                           distance_to_bbox_mode='sigmoid'),
+}
+
+
+def build_resnet(spec, B, N, H, M, L, seed=1, **resnet_kwargs):
+    """Instantiate a RESNET_SIBLINGS entry from module namespaces (this package's or the reference's, as build_sibling) and give
+    it synthetic_weights(seed) -- drawn per state_dict key, which also un-zeros the norm2 weights zero_init_residual leaves at 0
+    (they would hide every conv2).  resnet_kwargs: further ResNet constructor arguments (frozen_stages, norm_eval, ...)."""
+    spec = RESNET_SIBLINGS[spec] if isinstance(spec, str) else spec
+    bb = B.ResNet(**dict(spec['resnet'], **resnet_kwargs))
+    return synthetic_weights(_sibling_behind(spec, bb, N, H, M, L), seed)
+
+
+def build_resnet_model(name, seed=1, **resnet_kwargs):
+    """This package's model for a RESNET_SIBLINGS entry."""
+    from .model import backbone as B, head as H, losses as L, neck as N
+    from . import model as M
+    return build_resnet(name, B, N, H, M, L, seed, **resnet_kwargs)

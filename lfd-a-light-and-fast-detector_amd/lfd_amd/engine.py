@@ -282,10 +282,18 @@ class EnginePlan(object):
             self.stem_second = cv
             self.stem_fused = (c0,) + tuple(self.stem_first[1:]) + (cv.w, cv.b, cv.tail[0], cv.tail[1], cv.dst)
         # ---- stages
+        self._build_stages(net.blocks, cur, new_buf)
+        self.num_bufs = nbuf[0]
+
+    def _build_stages(self, blocks, cur, new_buf):
+        """the residual stages (netdesc.Block records) behind buffer `cur`: fused 64-channel block, downsample pair, 128-channel
+        block, wide layers one by one; fills taps / tap_channels / tap_ready_after (engine_resnet.ResNetPlan lowers its
+        stages through here too)"""
+        dev = self.device
         self.taps = []
         self.tap_channels = []
         self.tap_ready_after = []
-        for blk in net.blocks:
+        for blk in blocks:
             x_in = cur
             ident = x_in
             fuse_ds = None
@@ -343,7 +351,6 @@ class EnginePlan(object):
                 self.taps.append(cur)
                 self.tap_channels.append(blk.convs[-1].conv.out_channels)
                 self.tap_ready_after.append(len(self.convs))   # number of conv launches that must precede
-        self.num_bufs = nbuf[0]
 
     def _add_conv(self, src, new_buf, cin, cout, ks, stride, relu, w, b, tail=None, res=None, ds=None):
         c = _Conv()
@@ -489,6 +496,13 @@ class EnginePlan(object):
             c0, w1, b1, w2, b2 = self.stem_first
             check(l.lfd_stem_conv_f16(ptr(x), fmt, st.n, st.h, st.w, c0, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
                                       ptr(st.bufs[self.stem_out]), sp), 'lfd_stem_conv_f16')
+        self._run_convs(st, after)
+
+    def _run_convs(self, st, after=None):
+        """the launches of self.convs in order, each in the form its shape selects (engine_resnet.ResNetPlan runs its stages
+        through here too)"""
+        l = lib()
+        sp = stream_ptr()
         z = ops.zero_line(self.device)
         skip = -1
         for ci, c in enumerate(self.convs):

@@ -1,12 +1,13 @@
 """Layer-by-layer gfx950 engine for the sibling meta-architectures: FCOS (lfd/model/fcos.py:414-449) and
-LFDv2 (lfd/model/lfdv2.py:671-702) over an LFDResNet backbone, an FPN / SimpleFPN / SimpleNeck neck
+LFDv2 (lfd/model/lfdv2.py:671-702) over an LFDResNet or a ResNet-18 / 34 backbone, an FPN / SimpleFPN / SimpleNeck neck
 (lfd/model/neck/fpn.py:127-152, simple_fpn.py:141-172, simple_neck.py) and an FCOSHead / LFDHead with 1x1 or 3x3 towers
 (lfd/model/head/fcos_head.py:129-154, lfd_head.py:164-185).
 
 The LFD configurations the reference ships run on the fused plan of engine.py (stem / residual-block / 3-pass head
 kernels).  The siblings are not used by any shipped config; they get the same kernels one layer at a time:
 
-  backbone             engine.EnginePlan.run_backbone (the fused stem / block / conv kernels, unchanged)
+  backbone             engine.EnginePlan.run_backbone (the fused stem / block / conv kernels, unchanged); a ResNet:
+                       engine_resnet.ResNetPlan.run_backbone (7x7 stem, max-pool, the same block / conv kernels)
   conv (+ folded BN)   lfd_conv2d_nhwc_f16                     (MFMA implicit GEMM, csrc/conv_impl.h)
   GroupNorm (+ ReLU)   lfd_gn_train_stats_f16 + lfd_gn_train_apply_f16   (GroupNorm has no eval mode: same kernels as training)
   top-down merge       lfd_upsample_nearest_add_nhwc_f16       (csrc/sibling.hip)
@@ -20,7 +21,7 @@ unsupported module raises.
 import torch
 import torch.nn as nn
 
-from . import _lib, engine, netdesc, ops
+from . import _lib, engine, engine_resnet, netdesc, ops
 
 
 def _unsupported(msg):
@@ -49,6 +50,9 @@ class _Conv(object):
             _unsupported('neck / head convs with more than 128 output channels (%d)' % self.cout_real)
         if f32out and cin_have == 128 and cout == 32:
             cout = 64                     # the 128-channel fp32-output kernels are instantiated for >= 64 outputs
+        if cin_have > 128 and not f32out and not ops.conv2d_supported(cin_have, cout, ks, st):
+            # a lateral on a 256 / 512-channel tap: asked with the key __call__ launches (lfd_conv2d_nhwc_f16, csrc/conv_wide.hip)
+            _unsupported('no conv kernel for %d -> %d channels, %dx%d stride %d' % (cin_have, cout, ks, ks, st))
         if self.gn is not None:
             if cout != self.cout_real or self.cout_real != 8 * self.gn.num_groups:
                 _unsupported('GroupNorm(%d, %d): the kernels take 8 channels per group on 32/64/128 channels'
@@ -115,7 +119,13 @@ class SiblingPlan(object):
     def __init__(self, backbone, neck, head, dev):
         self.param_sig = engine._param_signature(backbone, neck, head)
         self.dev = dev
-        self.bb_plan = engine.get_plan(backbone, backbone, None, None, dev)
+        # the backbone plan by backbone class: the torchvision-style ResNet has its own (7x7 stem + pool, engine_resnet)
+        if engine_resnet.is_resnet(backbone):
+            self.bb_plan = engine_resnet.get_plan(backbone, dev)
+        elif engine_resnet.is_lfd_resnet(backbone):
+            self.bb_plan = engine.get_plan(backbone, backbone, None, None, dev)
+        else:        # a foreign backbone: say so, instead of an AttributeError on the first attribute a plan reads
+            engine._unsupported('backbone %s (LFDResNet and ResNet have plans)' % type(backbone).__name__)
         self.tap_real = list(self.bb_plan.tap_channels)
         self.tap_have = [engine.pad_channels(c) for c in self.tap_real]      # the plan's buffers carry padded channels
         self._build_neck(neck)

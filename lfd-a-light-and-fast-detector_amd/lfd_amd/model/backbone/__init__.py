@@ -1,1 +1,2 @@
 from .lfd_resnet import *
+from .resnet import *

@@ -26,7 +26,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import _lib, engine_sibling, engine_sibling_p32, ops, parallel, train_engine
+from .. import _lib, engine_resnet, engine_sibling, engine_sibling_p32, ops, parallel, train_engine
 from .lfd import LFD
 from .utils import multiclass_nms  # noqa: F401  (importable like the reference module)
 
@@ -130,6 +130,7 @@ class FCOS(nn.Module):
         if self.training or (torch.is_grad_enabled() and x.requires_grad):
             return self._forward_train(x)
         if self.precision == 'fp32_storage':
+            engine_resnet.require_fp16_mode(self)
             outs = engine_sibling_p32.sibling_forward(self, x, use_graph=self.use_graph)
             cls, reg, ctr = [t.clone() for t in outs[:3]]       # engine-owned buffers: fresh tensors, like the fp16 route
             sizes = outs[3]

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import engine, engine_p32, engine_sibling, engine_sibling_p32, netdesc, ops, parallel, train_engine
+from .. import engine, engine_p32, engine_resnet, engine_sibling, engine_sibling_p32, netdesc, ops, parallel, train_engine
 from ..data import DeviceAnnotations
 from .utils import multiclass_nms  # noqa: F401  (kept importable like the reference module)
 
@@ -184,8 +184,9 @@ class LFD(nn.Module):
         3x3 head convs, LFDHeadV1) run layer by layer on the same kernels (engine_sibling)"""
         ok = self.__dict__.get('_fused_ok')
         if ok is None:
-            ok = type(self._neck).__name__ == 'SimpleNeck' and type(self._head).__name__ == 'LFDHead' \
-                and self._head._conv_kernel_size == 1
+            # (a backbone that is not an LFDResNet -- the torchvision-style ResNet -- is asked nothing: layer engine)
+            ok = engine_resnet.is_lfd_resnet(self._backbone) and type(self._neck).__name__ == 'SimpleNeck' \
+                and type(self._head).__name__ == 'LFDHead' and self._head._conv_kernel_size == 1
             if ok:
                 try:
                     engine.get_plan(self, self._backbone, self._neck, self._head, device)
@@ -207,11 +208,14 @@ class LFD(nn.Module):
     def forward_resident(self, x, slot=0):
         """Fast path: same as forward() in eval mode but returns the engine-owned output buffers
         (no copy, valid until the next forward of the same input shape and `slot`)."""
-        if self.precision == 'fp32_storage' and engine_sibling_p32.covers(self):
+        precise = self.precision == 'fp32_storage'
+        if precise:
+            engine_resnet.require_fp16_mode(self)
+        if precise and engine_sibling_p32.covers(self):
             cls, reg, _, sizes = engine_sibling_p32.sibling_forward(self, x, use_graph=self.use_graph, slot=slot)
-        elif self.precision == 'fp32_storage':
+        elif precise:
             cls, reg, sizes = engine_p32.lfd_forward(self, x, use_graph=self.use_graph, slot=slot)
-        elif x.is_cuda and not self._fused_plan_ok(x.device):
+        elif (x.is_cuda or not engine_resnet.is_lfd_resnet(self._backbone)) and not self._fused_plan_ok(x.device):
             cls, reg, _, sizes = engine_sibling.sibling_forward(self, x, use_graph=self.use_graph)
         else:
             cls, reg, sizes = engine.lfd_forward(self, x, use_graph=self.use_graph, slot=slot)
@@ -228,6 +232,8 @@ class LFD(nn.Module):
         overlap on the device (the small-map stages, the post-processing kernels and the launch gaps of one batch leave most
         CUs idle -- a second batch in flight fills them: 0.75 -> 0.61 ms per batch of 8 at depth 2, tools/ab_pipeline.py)."""
         precise = self.precision == 'fp32_storage'
+        if precise:
+            engine_resnet.require_fp16_mode(self)
         layered = engine_sibling_p32.covers(self) if precise else not self._fused_plan_ok(x.device)
         if not self.use_graph or layered:       # the layer engines replay their forward graph; post-processing follows it
             return self.detect(self.forward_resident(x, slot), meta, score_thr, iou_thr, class_agnostic, max_candidates)
@@ -329,6 +335,8 @@ class LFD(nn.Module):
         return torch.cat(cls_l, 1), torch.cat(reg_l, 1)
 
     def _backbone_train_torch(self, x):
+        if not engine_resnet.is_lfd_resnet(self._backbone):
+            return list(self._backbone(x))          # ResNet's forward is plain torch ops (model/backbone/resnet.py)
         net = netdesc.backbone_layers(self._backbone)
         y = self._backbone._stem(x)
         feats = []

@@ -1,5 +1,6 @@
 """What an LFD model's module tree consists of, as plain records: the one place that knows how LFDResNet, SimpleNeck and
-LFDHead lay out their children (lfd_resnet.py:96-154, :354-501, simple_neck.py:35-47, lfd_head.py:86-149).
+LFDHead lay out their children (lfd_resnet.py:96-154, :354-501, simple_neck.py:35-47, lfd_head.py:86-149), and how the
+torchvision-style ResNet does (resnet.py:17-76, :348-400; resnet_layers).
 
 No device tensors, no folding, no kernel knowledge, and no opinion on what is supported: every launch plan (engine, engine_p2,
 engine_p32, engine_sibling*, engine_g1), the training schedules (train_engine) and the PyTorch-ROCm training route
@@ -53,6 +54,29 @@ def backbone_layers(bb):
                      for ci in range(1, blk.num_convs + 1)]
             blocks.append(Block(i, j, ds, convs, (i, j) in taps))
     return Backbone(_groups(bb._stem, len(bb.stem_spec()), has_norm), blocks)
+
+
+def resnet_layers(bb):
+    """ResNet (model/backbone/resnet.py) -> Backbone: stem = [Layer(conv1, norm1, relu), 'pool'] (deep_stem: the Layers of
+    bb.stem, then 'pool'); one Block per BasicBlock / Bottleneck with convs = [conv + norm + ReLU, ..., last conv + norm (ReLU
+    after the add)] and downsample = Layer(1x1, norm) (avg_down: its AvgPool2d is NOT described -- callers that lower the
+    records look at bb.avg_down).  Block.stage is 1-based like bb.out_indices, whose order the taps have."""
+    taps = [tuple(t) for t in bb.out_indices]
+    if bb.deep_stem:
+        stem = _groups(bb.stem, 3, True) + ['pool']
+    else:
+        stem = [layer(bb.conv1, bb.norm1, bb.relu), 'pool']
+    blocks = []
+    for i in range(1, bb.num_stages + 1):
+        for j in range(bb.stage_blocks[i - 1]):
+            blk = getattr(bb, 'layer%d' % i)[j]
+            ds = blk.downsample
+            if ds is not None:
+                ds = layer(ds[-2], ds[-1], None)
+            nconv = 3 if hasattr(blk, 'conv3') else 2
+            convs = [layer(getattr(blk, 'conv%d' % ci), getattr(blk, 'norm%d' % ci), blk.relu) for ci in range(1, nconv + 1)]
+            blocks.append(Block(i, j, ds, convs, (i, j) in taps))
+    return Backbone(stem, blocks)
 
 
 def lfd_head_levels(neck, head):

@@ -27,7 +27,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import netdesc, ops
+from . import engine_resnet, netdesc, ops
 
 LOSS_SCALE = 1024.0   # initial value; power of two; activation gradients are stored as fp16 * loss_scale()
 _scale_state = {'value': LOSS_SCALE}
@@ -110,6 +110,8 @@ def supported(backbone):
     (input_channels 3 or 1).  Frozen parameters and eval-mode norms: exactly what the backbone's own frozen_stages /
     norm_eval produce in train() -- the stem and the first stages frozen (forward only), every BatchNorm2d on its running
     statistics."""
+    if not engine_resnet.is_lfd_resnet(backbone):
+        return False          # the torchvision-style ResNet (7x7 stem, max-pool): PyTorch-ROCm autograd, its attributes unread
     if backbone._norm_cfg is None or backbone._norm_cfg.get('type') != 'BatchNorm2d':
         return False
     if backbone._activation_cfg.get('type') != 'ReLU' or not backbone.training:
