@@ -602,6 +602,22 @@ LFD_API int lfd_conv2d_nhwc_f16_acc32(const lfd_conv_desc_t* desc, const void* i
                                       const float* bias, const void* zeros, lfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Large-map conv of the 256-channel FPN necks and head towers (csrc/conv256.hip): NHWC fp16, stride 1, pad ks/2, 256 input
+ * channels, cout a multiple of 32 up to 256; fp32 accumulation on MFMA, one fixed summation order (no atomics, no workspace).
+ * Replaces the nn.Conv2d units of the FPN output convs (lfd/model/neck/fpn.py:57-82), of the FCOSHead towers and output
+ * convs (lfd/model/head/fcos_head.py:60-110,129-154) and of LFDHead's towers and output convs (lfd_head.py:97-117,164-185)
+ * at num_output_channels / num_head_channels = 256; executed by cuDNN in the reference.
+ *   out_f32 = 0: out [n,h,w,cout] fp16 = relu?( conv(in, w) + bias ), ks = 3.
+ *   out_f32 = 1: out [n,h,w,cout] fp32 = relu?( conv(in, w) + bias ), the accumulators un-rounded (the heads' logits),
+ *                ks = 3 or 1.
+ * w_packed: lfd_pack_conv_weight_f16 order for (cin 256, cout, ks).  in / out / w_packed / bias 16-byte aligned.  h * w * 256
+ * must stay below 2^31 (LFD_ERR_UNSUPPORTED otherwise); n * h * w * 256 may pass it.  lfd_conv256_nhwc_f16_supported answers
+ * for a (cin, cout, ks, out_f32) key without launching. */
+LFD_API int lfd_conv256_nhwc_f16_supported(int32_t cin, int32_t cout, int32_t ks, int32_t out_f32);
+LFD_API int lfd_conv256_nhwc_f16(const void* in, void* out, const void* w_packed, const float* bias, int32_t n, int32_t h,
+                                 int32_t w, int32_t cout, int32_t ks, int32_t relu, int32_t out_f32, lfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * 'fp32_storage' precision mode of the eval forward (LFD.precision = 'fp32_storage'): a shipped mode of the product for
  * callers that need the reference's fp32 outputs to <= 1e-4 on the raw logits (north_star: "cls/bbox tensors within
  * 1e-3"); replaces the same reference code as the fp16 entry points above -- nn.Conv2d + eval BatchNorm2d (+ residual)

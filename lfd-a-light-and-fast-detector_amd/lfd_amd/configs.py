@@ -340,6 +340,41 @@ RESNET_SIBLINGS = {
 }
 
 
+# ------------------------------------------------------------------ siblings at the width their classes default to: 256 channels
+# FCOSHead's defaults are num_head_channels=256, num_layers=4 (fcos_head.py:22-28); the canonical FCOS is a ResNet under a
+# 256-channel FPN with GroupNorm(32, 256) towers.  Kept apart from SIBLINGS / RESNET_SIBLINGS (the narrow fixtures and plan
+# fingerprints iterate those); tests/golden/make_golden_wide_siblings.py, tools/bench_wide_siblings.py.
+WIDE_SIBLINGS = {
+    # FCOS: ResNet-18 stages 2..4 (128 / 256 / 512 channels) -> FPN 256 with two conv extra levels -> the class-default head
+    'R18_FCOS_FPN256': dict(meta='FCOS', resnet=dict(depth=18, out_indices=((2, 1), (3, 1), (4, 1))),
+                            neck=dict(SIBLINGS['FCOS_FPN']['neck'], num_output_channels=256),
+                            head=dict(kind='FCOSHead', num_classes=80, num_head_channels=256, num_layers=4,
+                                      norm_cfg=dict(type='GroupNorm', num_groups=32)),
+                            regress_ranges=SIBLINGS['FCOS_FPN']['regress_ranges'], pre_nms_bbox_limit=100, post_nms_bbox_limit=20),
+    # LFDv2: the 64 / 64 / 128-channel taps of SIBLING_BACKBONE -> SimpleFPN 256 (BN + ReLU laterals, pooled extra level) ->
+    # LFDHead of 3x3 convs, separate shared towers, GroupNorm(32, 256); the rest as LFDV2_SFPN
+    'LFDV2_SFPN256': dict(SIBLINGS['LFDV2_SFPN'],
+                          neck=dict(SIBLINGS['LFDV2_SFPN']['neck'], num_output_channels=256),
+                          head=dict(SIBLINGS['LFDV2_SFPN']['head'], num_head_channels=256,
+                                    norm_cfg=dict(type='GroupNorm', num_groups=32))),
+}
+
+
+def build_wide_sibling(spec, B, N, H, M, L, seed=1):
+    """Instantiate a WIDE_SIBLINGS entry from module namespaces (this package's or the reference's, as build_sibling)."""
+    spec = WIDE_SIBLINGS[spec] if isinstance(spec, str) else spec
+    if 'resnet' in spec:
+        return build_resnet(spec, B, N, H, M, L, seed)
+    return build_sibling(spec, B, N, H, M, L, seed)
+
+
+def build_wide_sibling_model(name, seed=1):
+    """This package's model for a WIDE_SIBLINGS entry."""
+    from .model import backbone as B, head as H, losses as L, neck as N
+    from . import model as M
+    return build_wide_sibling(name, B, N, H, M, L, seed)
+
+
 def build_resnet(spec, B, N, H, M, L, seed=1, **resnet_kwargs):
     """Instantiate a RESNET_SIBLINGS entry from module namespaces (this package's or the reference's, as build_sibling) and give
     it synthetic_weights(seed) -- drawn per state_dict key, which also un-zeros the norm2 weights zero_init_residual leaves at 0

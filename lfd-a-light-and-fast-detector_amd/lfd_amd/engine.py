@@ -44,8 +44,9 @@ def pad_channels(c):
     zero bias, so they stay exactly 0 through ReLU / residual adds and meet zero weights in every consumer -- the real
     channels are bit-identical to an unpadded evaluation.  3 and 1 (an RGB / a grayscale image) are left alone.
     256 and 512 (the last stages of LFDResNet's own 'fast' / 'faster' body presets, lfd_resnet.py:222-231) are the widths of
-    csrc/conv_wide.hip: backbone convs of the 'fp16' mode only (require_narrow guards the fp32_storage plans; necks and
-    heads stay at 128)."""
+    csrc/conv_wide.hip, in the 'fp16' mode only (require_narrow guards the fp32_storage plans): backbone convs, and at 256 the
+    necks and heads of the sibling engine (engine_sibling.MAX_WIDTH; csrc/conv256.hip on their large maps).  The fused LFD plan's
+    necks and heads stay at 128."""
     if c in (1, 3):
         return c
     for a in (32, 64, 128, 256, 512):

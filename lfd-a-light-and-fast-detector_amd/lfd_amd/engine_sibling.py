@@ -8,20 +8,32 @@ kernels).  The siblings are not used by any shipped config; they get the same ke
 
   backbone             engine.EnginePlan.run_backbone (the fused stem / block / conv kernels, unchanged); a ResNet:
                        engine_resnet.ResNetPlan.run_backbone (7x7 stem, max-pool, the same block / conv kernels)
-  conv (+ folded BN)   lfd_conv2d_nhwc_f16                     (MFMA implicit GEMM, csrc/conv_impl.h)
+  conv (+ folded BN)   lfd_conv2d_nhwc_f16                     (MFMA implicit GEMM, csrc/conv_impl.h; with cin or cout above 128
+                                                               csrc/conv_wide.hip behind the same entry point)
+                       lfd_conv256_nhwc_f16                    (csrc/conv256.hip: 3x3 stride 1 from 256 channels on a batch of at
+                                                               least CONV256_MIN_PIXELS output pixels -- _Conv.route)
   GroupNorm (+ ReLU)   lfd_gn_train_stats_f16 + lfd_gn_train_apply_f16   (GroupNorm has no eval mode: same kernels as training)
   top-down merge       lfd_upsample_nearest_add_nhwc_f16       (csrc/sibling.hip)
   extra levels         lfd_relu_inplace_f16, conv 3x3 s2 | lfd_maxpool3x3s2_nhwc_f16
-  output convs         lfd_conv2d_nhwc_f16_acc32 (fp32 logits) + lfd_pack_level_outputs_f32 (Scale, exp, [N,P,C] concat)
+  output convs         lfd_conv2d_nhwc_f16_acc32 (fp32 logits; from 256 channels lfd_conv256_nhwc_f16 in its fp32-output form, 3x3
+                       or 1x1) + lfd_pack_level_outputs_f32 (Scale, exp, [N,P,C] concat)
 
-Inter-layer storage is NHWC fp16 like the LFD plan.  Widths: 32 / 64 / 128 channels (others zero-padded up); a backbone tap
-may have 256 or 512 channels (csrc/conv_wide.hip reads it), neck and head convs with more than 128 outputs are rejected; GroupNorm with 8 channels per group (the kernels' group size: 128/16, 64/8).  No PyTorch fallback: an
-unsupported module raises.
+Inter-layer storage is NHWC fp16 like the LFD plan.  Widths: 32 / 64 / 128 / 256 channels (others zero-padded up: the rule of
+engine.pad_channels); a backbone tap may have 512 channels (csrc/conv_wide.hip reads it), neck and head convs with more than
+256 outputs (MAX_WIDTH) are rejected; GroupNorm with 8 channels per group (the kernels' group size: 256/32, 128/16, 64/8).  No
+PyTorch fallback: an unsupported module raises.
 """
 import torch
 import torch.nn as nn
 
 from . import _lib, engine, engine_resnet, netdesc, ops
+
+
+# Neck and head widths: up to 256 channels (csrc/conv_wide.hip and csrc/conv256.hip); 512 is a backbone tap's width only.
+MAX_WIDTH = 256
+# A 3x3 stride-1 conv from 256 channels runs on csrc/conv256.hip (128 pixels x all channels per workgroup) when the batch has at
+# least this many output pixels, else on csrc/conv_wide.hip (64 pixels x 32 channels): the crossover of DESIGN 4i.
+CONV256_MIN_PIXELS = 12288
 
 
 def _unsupported(msg):
@@ -46,12 +58,17 @@ class _Conv(object):
         w, b = engine._fold_conv_norm(conv, bn)
         self.cout_real = w.shape[0]
         cout = engine.pad_channels(max(self.cout_real, 32))        # output convs have 1 .. 6 filters: one 32-wide MFMA tile
-        if cout > 128:          # the 256 / 512-channel kernels are the backbone's; a lateral conv READS such a tap (cin_have)
-            _unsupported('neck / head convs with more than 128 output channels (%d)' % self.cout_real)
+        if cout > MAX_WIDTH:    # the 512-channel kernels are the backbone's; a lateral conv READS such a tap (cin_have)
+            _unsupported('neck / head convs with more than %d output channels (%d)' % (MAX_WIDTH, self.cout_real))
         if f32out and cin_have == 128 and cout == 32:
             cout = 64                     # the 128-channel fp32-output kernels are instantiated for >= 64 outputs
-        if cin_have > 128 and not f32out and not ops.conv2d_supported(cin_have, cout, ks, st):
-            # a lateral on a 256 / 512-channel tap: asked with the key __call__ launches (lfd_conv2d_nhwc_f16, csrc/conv_wide.hip)
+        if f32out and cin_have > 128:
+            # fp32 logits from a 256-channel tower: csrc/conv256.hip at every map size (conv_wide has no fp32-output form)
+            if st != 1 or not ops.conv256_supported(cin_have, cout, ks, True):
+                _unsupported('no fp32-output conv kernel for %d -> %d channels, %dx%d stride %d' % (cin_have, cout, ks, ks, st))
+        elif (cin_have > 128 or cout > 128) and not ops.conv2d_supported(cin_have, cout, ks, st):
+            # a lateral on a 256 / 512-channel tap, any conv of a 256-channel neck / head: asked with the key __call__
+            # launches (lfd_conv2d_nhwc_f16, csrc/conv_wide.hip; the large-map route of route() shares conv_wide's keys)
             _unsupported('no conv kernel for %d -> %d channels, %dx%d stride %d' % (cin_have, cout, ks, ks, st))
         if self.gn is not None:
             if cout != self.cout_real or self.cout_real != 8 * self.gn.num_groups:
@@ -69,10 +86,26 @@ class _Conv(object):
         self.b = bp.to(dev).contiguous()
         self.cin, self.cout, self.ks, self.stride, self.relu, self.f32out = cin_have, cout, ks, st, bool(relu), f32out
 
+    def route(self, pixels):
+        """the kernel that computes this conv on a batch of `pixels` output pixels.  A function of the layer and of the input's
+        SHAPE alone (never of its values), so a captured graph replays the route it was captured with."""
+        if self.f32out:
+            return 'conv256_f32' if self.cin > 128 else 'acc32'
+        if self.cin == 256 and self.ks == 3 and self.stride == 1 and pixels >= CONV256_MIN_PIXELS \
+                and ops.conv256_supported(self.cin, self.cout, self.ks):
+            return 'conv256'
+        return 'conv_wide' if self.cin > 128 or self.cout > 128 else 'conv'
+
     def __call__(self, x):
+        r = self.route(x.shape[0] * x.shape[1] * x.shape[2])
+        if r == 'conv256_f32':
+            return ops.conv256_nhwc(x, self.w, self.b, self.cout, self.ks, relu=False, f32out=True)
         if self.f32out:
             return ops.conv2d_nhwc_f32out(x, self.w, self.b, self.cin, self.cout, self.ks, self.stride)
-        y = ops.conv2d_nhwc(x, self.w, self.b, self.cin, self.cout, self.ks, self.stride, self.relu and self.gn is None)
+        if r == 'conv256':
+            y = ops.conv256_nhwc(x, self.w, self.b, self.cout, self.ks, relu=self.relu and self.gn is None)
+        else:
+            y = ops.conv2d_nhwc(x, self.w, self.b, self.cin, self.cout, self.ks, self.stride, self.relu and self.gn is None)
         if self.gn is not None:
             stats = ops.gn_train_stats(y, self.gn.num_groups, self.gn.eps)
             y = ops.gn_train_apply(y, self.gn.num_groups, stats, self.gamma, self.beta, relu=self.relu)
@@ -130,6 +163,25 @@ class SiblingPlan(object):
         self.tap_have = [engine.pad_channels(c) for c in self.tap_real]      # the plan's buffers carry padded channels
         self._build_neck(neck)
         self._build_head(head)
+
+    def routes(self, pixels):
+        """[(where, cin, cout, ks, stride, _Conv.route)] of every conv of the neck and of the first level's head on a map of
+        `pixels` output pixels (batch included), in launch order"""
+        out = []
+
+        def walk(tag, what):
+            for o in (what.ops if isinstance(what, _Path) else [what]):
+                if isinstance(o, _Conv):
+                    out.append((tag, o.cin, o.cout, o.ks, o.stride, o.route(pixels)))
+
+        for i, p in enumerate(self.laterals):
+            walk('lateral%d' % i, p)
+        for i, p in enumerate(self.outs or []):
+            walk('out%d' % i, p)
+        for k in ('merge', 'cls_t', 'reg_t', 'cls_p', 'reg_p', 'cls_o', 'ctr_o', 'reg_o'):
+            if self.levels[0].get(k) is not None:
+                walk(k, self.levels[0][k])
+        return out
 
     # ------------------------------------------------------------------ neck
     def _build_neck(self, neck):

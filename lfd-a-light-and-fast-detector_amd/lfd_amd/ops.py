@@ -856,6 +856,27 @@ def conv2d_nhwc_f32out(x, w_packed, bias, cin, cout, ks, stride):
     return out
 
 
+def conv256_supported(cin, cout, ks, f32out=False):
+    """does lfd_conv256_nhwc_f16 (csrc/conv256.hip: 256 input channels, stride 1, large maps) take this layer?  Nothing
+    launched -- works without a device."""
+    return lib().lfd_conv256_nhwc_f16_supported(cin, cout, ks, int(bool(f32out))) == 0
+
+
+def conv256_nhwc(x, w_packed, bias, cout, ks=3, relu=False, f32out=False, out=None):
+    """x [N,H,W,256] fp16 -> relu?(conv + bias) [N,H,W,cout], stride 1, pad ks // 2: fp16, or with f32out the un-rounded
+    fp32 accumulators (lfd_conv256_nhwc_f16).  w_packed: pack_conv_weight of [cout, 256, ks, ks]."""
+    require_cuda(x, 'conv256')
+    if x.dtype != torch.float16 or not x.is_contiguous() or x.dim() != 4 or x.shape[3] != 256:
+        raise RuntimeError('conv256_nhwc: x must be contiguous fp16 NHWC with 256 channels')
+    n, h, w_, _ = x.shape
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty((n, h, w_, cout), dtype=torch.float32 if f32out else torch.float16, device=x.device)
+        check(lib().lfd_conv256_nhwc_f16(ptr(x), ptr(out), ptr(w_packed), ptr(bias), n, h, w_, cout, ks, int(bool(relu)),
+                                         int(bool(f32out)), stream_ptr()), 'lfd_conv256_nhwc_f16')
+    return out
+
+
 def upsample_nearest_add_(dst, src):
     """dst [N,H,W,C] += nearest-neighbour resize of src [N,h,w,C] (fp16 NHWC, in place): the FPN merge step"""
     _nhwc16(dst, 'upsample_nearest_add')
