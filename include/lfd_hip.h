@@ -618,6 +618,38 @@ LFD_API int lfd_conv256_nhwc_f16(const void* in, void* out, const void* w_packed
                                  int32_t w, int32_t cout, int32_t ks, int32_t relu, int32_t out_f32, lfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * INT8 deployment mode (csrc/conv_i8.hip; lfd_amd/deployment.py, lfd_amd/engine_i8.py): the convs of the residual
+ * stages on v_mfma_i32_32x32x32_i8 with exact i32 accumulation and a requantising epilogue, and the quantise step behind the
+ * fp16 stem.  Replaces what the reference obtains from TensorRT's INT8 builder and its INT8Calibrator
+ * (lfd/deployment/tensorrt/build_engine.py:22-126); the calibration contract is this project's own (symmetric, per-output-
+ * channel weight scales, one scale per activation tensor, range [-127, 127]).
+ *
+ * lfd_conv2d_nhwc_i8: desc = (n, h, w, cin, cout, ks, stride, relu) of an lfd_conv_desc_t (tail_cout must be 0); ks 1 | 3,
+ * stride 1 | 2, pad ks / 2, cin and cout in {64, 128} (anything else: LFD_ERR_UNSUPPORTED, nothing written;
+ * lfd_conv2d_nhwc_i8_supported answers for a key without launching).  in [n,h,w,cin] int8; w_packed: the fragment order of
+ * lfd_amd.ops.pack_conv_weight_i8, cout * ks * ks * cin bytes; mult / biasq [cout] fp32; res [n,oh,ow,cout] int8 or NULL.
+ * With acc the exact i32 sum:
+ *   v = fmaf((float)acc, mult[co], biasq[co]);  res: v = fmaf((float)res, res_mult, v);  desc->relu: v = max(v, 0)
+ *   out_i8  [n,oh,ow,cout] int8 = clamp(rint(v), -127, 127), round half even
+ *   out_f16 [n,oh,ow,cout] fp16 = half(v * out_scale), the un-requantised value (a pyramid tap for the fp16 head), this v
+ *           evaluated in float64 and rounded once (within one fp16 ulp of the exact value even where the residual add
+ *           cancels); NULL: not written (out_scale ignored).
+ * Every pointer 16-byte aligned; out_i8 must not alias in or res.  h * w * 128 must stay below 2^31.
+ *
+ * lfd_quantize_nhwc_f16_i8: out[i] = clamp(rint((float)in[i] * inv_scale), -127, 127) for i < count (any count >= 1); in fp16,
+ * out int8, both 16-byte aligned.
+ * lfd_quantize_pad_nhwc_f16_i8: the same step into wider pixels: out [pixels][cout] = the quantised in [pixels][cin] in channels
+ * below cin and 0 above (a 32-channel stem in front of stages that run zero-padded to 64); cin, cout multiples of 16,
+ * cin <= cout <= 128. */
+LFD_API int lfd_conv2d_nhwc_i8_supported(int32_t cin, int32_t cout, int32_t ks, int32_t stride);
+LFD_API int lfd_conv2d_nhwc_i8(const lfd_conv_desc_t* desc, const void* in, const void* w_packed, const float* mult,
+                               const float* biasq, const void* res, float res_mult, void* out_i8, void* out_f16,
+                               float out_scale, lfd_stream_t stream);
+LFD_API int lfd_quantize_nhwc_f16_i8(const void* in, void* out, int64_t count, float inv_scale, lfd_stream_t stream);
+LFD_API int lfd_quantize_pad_nhwc_f16_i8(const void* in, void* out, int64_t pixels, int32_t cin, int32_t cout, float inv_scale,
+                                         lfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * 'fp32_storage' precision mode of the eval forward (LFD.precision = 'fp32_storage'): a shipped mode of the product for
  * callers that need the reference's fp32 outputs to <= 1e-4 on the raw logits (north_star: "cls/bbox tensors within
  * 1e-3"); replaces the same reference code as the fp16 entry points above -- nn.Conv2d + eval BatchNorm2d (+ residual)

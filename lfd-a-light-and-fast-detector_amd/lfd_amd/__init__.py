@@ -6,3 +6,12 @@ Host-side mirror of the reference's operator interface (`LFDResNet`, `SimpleNeck
 `liblfd_hip.so` (include/lfd_hip.h) whose kernels are hand-written HIP for CDNA4.
 """
 __version__ = '0.1.0'
+
+_DEPLOYMENT = ('INT8Calibrator', 'Int8Engine', 'build_int8_engine')      # lfd_amd/deployment.py, imported on first use
+
+
+def __getattr__(name):
+    if name in _DEPLOYMENT:
+        from . import deployment
+        return getattr(deployment, name)
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -1,0 +1,188 @@
+"""INT8 deployment: the third precision the reference publishes next to FP32 and FP16 (lfd/deployment/tensorrt/build_engine.py:
+INT8Calibrator + build_tensorrt_engine(..., precision_mode='int8', int8_calibrator=...)).
+
+    calibrator = INT8Calibrator(frames, 'model.int8.json', batch_size=8)     # frames: float32 [N,C,H,W], already normalised
+    eng = build_int8_engine(model, calibrator)                               # calibrates, or reads the cache
+    cls, reg = eng(x)                                                         # as LFD.forward
+
+The calibrator mirrors the reference's constructor and method names; what is calibrated, and how, is this project's own contract
+(lfd_amd/engine_i8.py) -- TensorRT's entropy calibration is proprietary and is not reproduced.  The cache is UTF-8
+JSON: {"format", "version", "state_sha256", "amax": {tensor name: largest |value| over the calibration batches}}; a cache
+written for other weights (another sha) or another layer list is ignored and calibration runs again."""
+import hashlib
+import json
+import os
+
+import numpy
+import torch
+
+from . import engine, engine_i8
+
+CACHE_FORMAT = 'lfd_amd.int8_calibration'
+CACHE_VERSION = 1
+
+
+def state_sha256(state_dict):
+    """sha256 over the names and the bytes of a state_dict, in its order"""
+    h = hashlib.sha256()
+    for k in state_dict:
+        h.update(k.encode())
+        h.update(state_dict[k].detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+def encode_cache(sha, amax):
+    return json.dumps(dict(format=CACHE_FORMAT, version=CACHE_VERSION, state_sha256=sha,
+                           amax=dict((k, float(v)) for k, v in amax.items())), indent=1).encode('utf-8')
+
+
+def decode_cache(blob, sha, names):
+    """cache bytes -> {name: amax}, or None when the bytes are not a cache of this format for these weights and tensors"""
+    try:
+        d = json.loads(blob.decode('utf-8'))
+    except (ValueError, AttributeError):
+        return None
+    if not isinstance(d, dict) or d.get('format') != CACHE_FORMAT or d.get('version') != CACHE_VERSION:
+        return None
+    amax = d.get('amax')
+    if d.get('state_sha256') != sha or not isinstance(amax, dict) or sorted(amax) != sorted(names):
+        return None
+    try:
+        return dict((k, float(amax[k])) for k in names)
+    except (TypeError, ValueError):
+        return None
+
+
+class INT8Calibrator(object):
+    """Calibration frames in batches, and the cache file.  data: float32 [N,C,H,W], each image already normalised (numpy array
+    or torch tensor); frames beyond the last whole batch are not used, as in the reference."""
+
+    def __init__(self, data, cache_file, batch_size=8, device=None):
+        self._cache_file = cache_file
+        self._batch_size = int(batch_size)
+        if isinstance(data, torch.Tensor):
+            data = data.detach().cpu().numpy()
+        assert data.ndim == 4 and data.dtype == numpy.float32
+        assert self._batch_size >= 1
+        self._data = numpy.array(data, dtype=numpy.float32, order='C')
+        self._current_index = 0
+        self._device = device
+
+    def get_batch_size(self):
+        return self._batch_size
+
+    def get_batch(self, names=None, p_str=None):
+        """the next batch as a device tensor [batch_size,C,H,W]; None when fewer than batch_size frames remain"""
+        if self._current_index + self._batch_size > self._data.shape[0]:
+            return None
+        batch = self._data[self._current_index:self._current_index + self._batch_size]
+        self._current_index += self._batch_size
+        return torch.from_numpy(batch).to(self._device if self._device is not None else 'cuda')
+
+    def reset(self):
+        self._current_index = 0
+
+    def read_calibration_cache(self):
+        if os.path.exists(self._cache_file):
+            with open(self._cache_file, 'rb') as f:
+                return f.read()
+        return None
+
+    def write_calibration_cache(self, cache):
+        with open(self._cache_file, 'wb') as f:
+            f.write(cache)
+
+
+class Int8Engine(object):
+    """An LFD model's eval forward with int8 residual stages.  scales: {tensor name: (amax, scale)}; calibrated: whether this
+    build ran the calibration batches (False: the cache was used)."""
+
+    def __init__(self, model, plan, calibrated):
+        self.model = model
+        self.plan = plan
+        self.calibrated = calibrated
+        self.use_graph = False
+
+    @property
+    def scales(self):
+        return self.plan.scales
+
+    def _check_fresh(self):
+        m = self.model
+        if engine._param_signature(m._backbone, m._neck, m._head) != self.plan.param_sig:
+            raise RuntimeError('Int8Engine: the model\'s parameters or buffers changed after the engine was built (optimizer step, '
+                               'load_state_dict, .to()): the quantised weights and the calibration no longer belong to them -- '
+                               'rebuild with build_int8_engine')
+        if m.training:
+            raise RuntimeError('Int8Engine: the model is in training mode; the engine folds eval-mode BatchNorm (call model.eval())')
+
+    def forward_resident(self, x, slot=0):
+        """(cls [N,P,C'], reg [N,P,4]) fp32, level-concatenated, in engine-owned buffers (valid until the next forward of the same
+        input shape and slot).  x: the frame formats of LFD.forward."""
+        self._check_fresh()
+        from . import _lib
+        _lib.require_cuda(x, 'Int8Engine.forward')
+        if not x.is_contiguous():
+            x = x.contiguous()
+        plan = self.plan
+        fmt, n, h, w = engine._input_format(x, plan.input_channels)
+        st = plan.state_for(n, h, w, slot)
+        with torch.cuda.device(x.device):
+            if self.use_graph:
+                engine._run_graphed(plan, st, x, fmt)
+            else:
+                plan.run_all(x, fmt, st)
+        for i, hw in enumerate(st.sizes):
+            self.model._head_indexes_to_feature_map_sizes[i] = hw
+        return st.cls, st.reg
+
+    def forward(self, x):
+        cls, reg = self.forward_resident(x)
+        return cls.clone(), reg.clone()
+
+    __call__ = forward
+
+    def detect(self, x, meta, score_thr=None, iou_thr=None, class_agnostic=None, max_candidates=None, slot=0):
+        """forward + the model's fused device post-processing (LFD.detect); meta [N,3] on the device"""
+        return self.model.detect(self.forward_resident(x, slot), meta, score_thr, iou_thr, class_agnostic, max_candidates)
+
+    def get_results(self, predict_outputs, *args):
+        return self.model.get_results(predict_outputs, *args)
+
+
+def build_int8_engine(model, int8_calibrator):
+    """LFD model (eval mode, on the device) + INT8Calibrator -> Int8Engine.  Uses the calibrator's cache when it was written
+    for these weights and this layer list; otherwise runs the calibration batches and writes it."""
+    assert int8_calibrator is not None, 'calibrator is not provided!'
+    engine_i8.check_model(model)
+    if model.training:
+        raise RuntimeError('build_int8_engine: call model.eval() first (eval-mode BatchNorm is folded into the weights)')
+    device = next(model.parameters()).device
+    if device.type != 'cuda':
+        raise RuntimeError('build_int8_engine: the model must be on the MI355X (got %s)' % device)
+    with torch.no_grad():
+        plan = engine_i8.Int8Plan(model._backbone, model._neck, model._head, device)
+    sha = state_sha256(model.state_dict())
+    blob = int8_calibrator.read_calibration_cache()
+    amax = decode_cache(blob, sha, plan.tensor_names) if blob is not None else None
+    calibrated = amax is None
+    if calibrated:
+        def batches():
+            while True:
+                b = int8_calibrator.get_batch([])
+                if b is None:
+                    return
+                yield b.to(device)
+        seen = [0]
+
+        def counted():
+            for b in batches():
+                seen[0] += 1
+                yield b
+        amax = plan.calibrate(counted())
+        if seen[0] == 0:
+            raise RuntimeError('build_int8_engine: the calibrator has no whole batch (fewer frames than batch_size, or already '
+                               'consumed) and no usable cache')
+        int8_calibrator.write_calibration_cache(encode_cache(sha, amax))
+    plan.set_scales(amax)
+    return Int8Engine(model, plan, calibrated)

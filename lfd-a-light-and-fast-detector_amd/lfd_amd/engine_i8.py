@@ -1,0 +1,277 @@
+"""INT8 deployment plan: the fp16 engine's stem and neck + head around residual stages that run in int8 on
+csrc/conv_i8.hip -- what the reference gets from a TensorRT engine built with precision_mode='int8'
+(lfd/deployment/tensorrt/build_engine.py:22-126).  lfd_amd/deployment.py is the public interface.
+
+Split of the network: stem = the parent plan's fp16 launches; one quantise launch; every conv of the residual stages, identity
+branches included, one lfd_conv2d_nhwc_i8 launch each (layer by layer: no fused block kernels yet); a conv whose output is a
+pyramid tap also stores the un-requantised fp16 map the parent's head kernels read.
+
+Numeric contract (symmetric, range [-127, 127], no zero points):
+  weights      BN-folded fp32 (engine.fold_conv_norm, channels zero-padded to 64 / 128); per output channel
+               s_w[co] = max|w[co]| / 127 (a zero row: 1), q_w = clamp(rint(w / s_w))
+  activations  one scale per tensor t (the stem output, or a conv's output after bias, residual add and ReLU):
+               s_t = amax_t / 127 (amax_t == 0: 1), amax_t the largest |value| over all calibration batches of the fp16 pass
+  constants    float64 -> fp32: mult[co] = s_in s_w[co] / s_out, biasq[co] = b[co] / s_out, res_mult = s_res / s_out
+  epilogue     include/lfd_hip.h, lfd_conv2d_nhwc_i8
+There is no fp16 fallback: a model outside the coverage raises engine.Unsupported."""
+import ctypes as C
+
+import torch
+import torch.nn.functional as F
+
+from . import _lib, engine, engine_resnet, netdesc, ops
+from ._lib import check, lib, ptr, stream_ptr
+
+QMAX = 127
+STEM = 'stem'       # name of the calibrated tensor in front of the stages
+
+
+def pad_channels_i8(c, what):
+    """the int8 kernels are instantiated for 64 and 128 channels: 32 / 48 run zero-padded to 64"""
+    if c <= 64:
+        return 64
+    if c <= 128:
+        return 128
+    engine._unsupported('more than 128 channels (%d) in %s: the INT8 mode has kernels for bodies of up to 128 channels' % (c, what))
+
+
+def weight_scales(w):
+    """folded fp32 OIHW weight -> (s_w [cout] float64, q_w int8 OIHW): s_w = max|w[co]| / 127, 1 for a zero row"""
+    amax = w.detach().double().abs().flatten(1).max(1)[0]
+    s_w = torch.where(amax > 0, amax / QMAX, torch.ones_like(amax))
+    q = torch.round(w.detach().double() / s_w.view(-1, 1, 1, 1)).clamp(-QMAX, QMAX).to(torch.int8)
+    return s_w, q
+
+
+def act_scale(amax):
+    """amax of a tensor -> its scale (float64 arithmetic on Python floats)"""
+    return float(amax) / QMAX if amax > 0 else 1.0
+
+
+def epilogue_constants(s_in, s_w, bias, s_out, s_res=None):
+    """(mult [cout] fp32, biasq [cout] fp32, res_mult float): computed in float64, stored as fp32"""
+    mult = (s_w.double() * s_in / s_out).float()
+    biasq = (bias.double() / s_out).float()
+    res_mult = float(torch.tensor(s_res / s_out, dtype=torch.float64).float()) if s_res is not None else 0.0
+    return mult, biasq, res_mult
+
+
+def _pad_to(w, b, cout, cin):
+    if (cout, cin) == tuple(w.shape[:2]):
+        return w, b
+    wp = torch.zeros((cout, cin) + tuple(w.shape[2:]), dtype=w.dtype, device=w.device)
+    wp[:w.shape[0], :w.shape[1]] = w
+    bp = torch.zeros(cout, dtype=b.dtype, device=b.device)
+    bp[:b.shape[0]] = b
+    return wp, bp
+
+
+class ConvI8(object):
+    """one lfd_conv2d_nhwc_i8 launch over symbolic int8 buffer ids; name = the calibrated tensor it produces"""
+    __slots__ = ('name', 'cin', 'cout', 'cout_real', 'ks', 'stride', 'relu', 'src', 'dst', 'res', 'tap', 'src_name', 'res_name',
+                 'ref_w', 'ref_b', 'q_w', 's_w', 'w', 'w16', 'mult', 'biasq', 'res_mult', 's_in', 's_out', 's_res')
+
+
+def check_model(model):
+    """the INT8 mode covers the LFD models of the fused fp16 plan with stage convs of up to 128 (padded) channels; everything
+    else is named here (the plan's own constructor refuses the rest)"""
+    kind = type(model).__name__
+    if kind != 'LFD':
+        engine._unsupported('the INT8 mode covers LFD models only, not %s' % kind)
+    if not engine_resnet.is_lfd_resnet(model._backbone):
+        engine._unsupported('the INT8 mode covers the LFDResNet backbone only, not %s' % type(model._backbone).__name__)
+    if type(model._neck).__name__ != 'SimpleNeck':
+        engine._unsupported('the INT8 mode covers SimpleNeck only, not %s' % type(model._neck).__name__)
+    if type(model._head).__name__ != 'LFDHead' or model._head._conv_kernel_size != 1:
+        engine._unsupported('the INT8 mode covers an LFDHead of 1x1 convs only, not %s' % type(model._head).__name__)
+    if model.precision != 'fp16':
+        engine._unsupported("the INT8 mode keeps the stem and the head on the 'fp16' kernels; the model's precision is %r"
+                            % (model.precision,))
+    for m in model._backbone.modules():
+        if isinstance(m, torch.nn.Conv2d) and max(m.in_channels, m.out_channels) > 128:
+            engine._unsupported('more than 128 channels (conv %d -> %d) in the backbone: the INT8 mode has kernels for bodies of '
+                                'up to 128 channels' % (m.in_channels, m.out_channels))
+
+
+class Int8Plan(engine.EnginePlan):
+    """engine.EnginePlan whose residual stages are int8 launches.  Built without scales (layers, folded and quantised weights);
+    calibrate() measures the amax of every named tensor in fp16, set_scales() turns them into the launches' constants."""
+
+    def __init__(self, backbone, neck=None, head=None, device=None):
+        self.layers = []
+        self.scales = None
+        super().__init__(backbone, neck, head, device)
+
+    # ---- lowering
+    def _build_stages(self, blocks, cur, new_buf):
+        dev = self.device
+        self.taps, self.tap_channels, self.tap_ready_after = [], [], []
+        self.stage_in = cur                                   # fp16 buffer the stem launches leave their output in
+        c_in = pad_channels_i8(self.buf_channels[cur], 'the stem')
+        self.qbuf_channels = {0: c_in}
+        self.qbuf_scale = {0: self.buf_scale[cur]}
+        self.tensor_names = [STEM]
+
+        def add(src, src_name, lay, name, relu, res=None, res_name=None, tap=False):
+            c = ConvI8()
+            c.name, c.ks, c.stride, c.relu = name, lay.ks, lay.stride, bool(relu)
+            c.cin = pad_channels_i8(lay.conv.in_channels, name)
+            c.cout = pad_channels_i8(lay.conv.out_channels, name)
+            c.cout_real = lay.conv.out_channels
+            if lay.ks not in (1, 3) or lay.stride not in (1, 2) or lay.conv.padding[0] != lay.ks // 2 or lay.conv.groups != 1 \
+                    or lay.conv.dilation[0] != 1 or not ops.conv2d_i8_supported(c.cin, c.cout, lay.ks, lay.stride):
+                engine._unsupported('%s: no int8 kernel for a %d -> %d conv, kernel %d, stride %d'
+                                    % (name, lay.conv.in_channels, lay.conv.out_channels, lay.ks, lay.stride))
+            if c.cin != self.qbuf_channels[src]:
+                engine._unsupported('%s: %d input channels behind a %d-channel tensor' % (name, c.cin, self.qbuf_channels[src]))
+            w, b = engine._fold_conv_norm(lay.conv, lay.norm)
+            c.ref_w, c.ref_b = _pad_to(w, b, c.cout, c.cin)
+            c.s_w, c.q_w = weight_scales(c.ref_w)
+            c.w = ops.pack_conv_weight_i8(c.q_w).to(dev)
+            c.w16 = None                                      # fp16 fragment order of ref_w, packed when calibrate() needs it
+            c.ref_b = c.ref_b.to(dev)
+            c.src, c.res, c.src_name, c.res_name = src, res, src_name, res_name
+            c.dst = len(self.qbuf_channels)
+            self.qbuf_channels[c.dst] = c.cout
+            self.qbuf_scale[c.dst] = self.qbuf_scale[src] * lay.stride
+            c.tap = None
+            if tap:                                           # the fp16 map engine.EnginePlan.run_head reads
+                c.tap = new_buf()
+                self.buf_channels[c.tap] = c.cout
+                self.buf_scale[c.tap] = self.qbuf_scale[c.dst]
+            c.mult = c.biasq = None
+            self.layers.append(c)
+            self.tensor_names.append(name)
+            return c.dst
+
+        q, q_name = 0, STEM
+        for blk in blocks:
+            base = 'stage%d.block%d' % (blk.stage, blk.index)
+            ident, ident_name = q, q_name
+            if blk.downsample is not None:
+                ident_name = base + '.downsample'
+                ident = add(q, q_name, blk.downsample, ident_name, False)
+            y, y_name = q, q_name
+            for ci, lay in enumerate(blk.convs):
+                last = ci == len(blk.convs) - 1
+                if not lay.relu:
+                    engine._unsupported('activation must be ReLU')
+                name = '%s.conv%d' % (base, ci + 1)
+                y = add(y, y_name, lay, name, True, res=ident if last else None, res_name=ident_name if last else None,
+                        tap=blk.tap and last)
+                y_name = name
+            if self.qbuf_channels[ident] != self.qbuf_channels[y]:
+                engine._unsupported('%s: residual of %d channels added to %d' % (base, self.qbuf_channels[ident], self.qbuf_channels[y]))
+            q, q_name = y, y_name
+            if blk.tap:
+                self.taps.append(self.layers[-1].tap)
+                self.tap_channels.append(blk.convs[-1].conv.out_channels)
+                self.tap_ready_after.append(len(self.convs) + len(self.layers))
+
+    # ---- calibration (offline: fp16 kernels where they exist, torch otherwise; amax with torch)
+    def calibrate(self, batches):
+        """batches: iterable of device frame batches (any format the stem accepts) -> {tensor name: amax (float)} over all of
+        them.  Runs the stem launches and then the layer list in fp16, one layer at a time."""
+        amax = dict((k, 0.0) for k in self.tensor_names)
+
+        def see(name, t):
+            amax[name] = max(amax[name], float(t.float().abs().max()))
+
+        with torch.no_grad():
+            for x in batches:
+                x = x.contiguous()
+                fmt, n, h, w = engine._input_format(x, self.input_channels)
+                st = self.state_for(n, h, w, slot='calibrate')
+                with torch.cuda.device(self.device):
+                    engine.EnginePlan.run_backbone(self, x, fmt, st)
+                    t = st.bufs[self.stage_in]
+                    if t.shape[3] != self.qbuf_channels[0]:       # a 32-channel stem in front of stages padded to 64
+                        t = F.pad(t, (0, self.qbuf_channels[0] - t.shape[3]))
+                    see(STEM, t)
+                    outs = {0: t}
+                    for c in self.layers:
+                        res = outs[c.res] if c.res is not None else None
+                        if ops.conv2d_supported(c.cin, c.cout, c.ks, c.stride):
+                            if c.w16 is None:
+                                c.w16 = ops.pack_conv_weight(c.ref_w).to(self.device)
+                            y = ops.conv2d_nhwc(outs[c.src].contiguous(), c.w16, c.ref_b, c.cin, c.cout, c.ks, c.stride, c.relu,
+                                                residual=res)
+                        else:
+                            y = F.conv2d(outs[c.src].permute(0, 3, 1, 2).float(), c.ref_w.to(self.device), c.ref_b, stride=c.stride,
+                                         padding=c.ks // 2).permute(0, 2, 3, 1)
+                            if res is not None:
+                                y = y + res.float()
+                            if c.relu:
+                                y = y.relu()
+                            y = y.half().contiguous()
+                        see(c.name, y)
+                        outs[c.dst] = y
+            self._shape_cache = dict((k, v) for k, v in self._shape_cache.items() if k[3] != 'calibrate')
+        return amax
+
+    def set_scales(self, amax):
+        """{tensor name: amax} -> the constants of every launch; self.scales = {name: (amax, scale)}"""
+        missing = [k for k in self.tensor_names if k not in amax]
+        if missing:
+            raise KeyError('calibration misses the tensors %s' % missing)
+        dev = self.device
+        self.scales = dict((k, (float(amax[k]), act_scale(float(amax[k])))) for k in self.tensor_names)
+        self.inv_stem_scale = float(torch.tensor(1.0 / self.scales[STEM][1], dtype=torch.float64).float())
+        for c in self.layers:
+            c.s_in, c.s_out = self.scales[c.src_name][1], self.scales[c.name][1]
+            c.s_res = self.scales[c.res_name][1] if c.res is not None else None
+            mult, biasq, c.res_mult = epilogue_constants(c.s_in, c.s_w, c.ref_b, c.s_out, c.s_res)
+            c.mult, c.biasq = mult.to(dev).contiguous(), biasq.to(dev).contiguous()
+
+    # ---- shape-dependent state: the parent's (fp16 stem, tap and head buffers) plus the int8 maps
+    def state_for(self, n, h, w, slot=0):
+        st = super().state_for(n, h, w, slot)
+        if not hasattr(st, 'qbufs'):
+            st.qbufs = {}
+            with torch.cuda.device(self.device):
+                for b, sc in self.qbuf_scale.items():
+                    hh, ww, s = h, w, sc
+                    while s > 1:
+                        hh, ww = (hh + 1) // 2, (ww + 1) // 2
+                        s //= 2
+                    st.qbufs[b] = torch.zeros((n, hh, ww, self.qbuf_channels[b]), dtype=torch.int8, device=self.device)
+        return st
+
+    # ---- execution
+    def run_stem(self, x, fmt, st):
+        """the parent's stem launches into the fp16 buffer, then the quantise launch"""
+        engine.EnginePlan.run_backbone(self, x, fmt, st)
+        self.run_quantise(st)
+
+    def run_quantise(self, st):
+        src = st.bufs[self.stage_in]
+        l, sp = lib(), stream_ptr()
+        if src.shape[3] == self.qbuf_channels[0]:
+            check(l.lfd_quantize_nhwc_f16_i8(ptr(src), ptr(st.qbufs[0]), src.numel(), self.inv_stem_scale, sp),
+                  'lfd_quantize_nhwc_f16_i8')
+        else:
+            check(l.lfd_quantize_pad_nhwc_f16_i8(ptr(src), ptr(st.qbufs[0]), src.numel() // src.shape[3], src.shape[3],
+                                                 self.qbuf_channels[0], self.inv_stem_scale, sp), 'lfd_quantize_pad_nhwc_f16_i8')
+
+    def run_layer(self, c, st):
+        src = st.qbufs[c.src]
+        d = _lib.ConvDesc(st.n, src.shape[1], src.shape[2], c.cin, c.cout, c.ks, c.stride, int(c.relu), 0, 0)
+        check(lib().lfd_conv2d_nhwc_i8(C.byref(d), ptr(src), ptr(c.w), ptr(c.mult), ptr(c.biasq),
+                                       ptr(st.qbufs[c.res]) if c.res is not None else None, c.res_mult, ptr(st.qbufs[c.dst]),
+                                       ptr(st.bufs[c.tap]) if c.tap is not None else None, c.s_out, stream_ptr()),
+              'lfd_conv2d_nhwc_i8')
+
+    def run_stages(self, st, after=None):
+        base = len(self.convs)
+        for li, c in enumerate(self.layers):
+            if after and base + li in after:
+                after[base + li]()
+            self.run_layer(c, st)
+        if after and base + len(self.layers) in after:
+            after[base + len(self.layers)]()
+
+    def run_backbone(self, x, fmt, st, after=None):
+        if self.scales is None:
+            raise RuntimeError('Int8Plan: no scales yet (calibrate() + set_scales(), or deployment.build_int8_engine)')
+        self.run_stem(x, fmt, st)
+        self.run_stages(st, after)

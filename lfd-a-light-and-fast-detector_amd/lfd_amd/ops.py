@@ -877,6 +877,83 @@ def conv256_nhwc(x, w_packed, bias, cout, ks=3, relu=False, f32out=False, out=No
     return out
 
 
+# ------------------------------------------------------------------ INT8 deployment mode (csrc/conv_i8.hip)
+def _i8_rows(device=None):
+    """MFMA row m of a 32-channel slab -> the slab's output channel it carries: 16 ((m >> 2) & 1) + (m & 3) + 4 (m >> 3), so that
+    register g of lane half h of the 32x32 result (row (g & 3) + 8 (g >> 2) + 4 h) is channel 16 h + g"""
+    m = torch.arange(32, device=device)
+    return 16 * ((m >> 2) & 1) + (m & 3) + 4 * (m >> 3)
+
+
+def pack_conv_weight_i8(q_w):
+    """[Cout,Cin,k,k] int8 (quantised, BN already folded) -> MFMA fragment order [Cout/32][k*k*Cin/32][64][16] int8.
+    lane = 32*half + m; MFMA row m of slab t carries output channel 32 t + 16 ((m >> 2) & 1) + (m & 3) + 4 (m >> 3) (the C/D
+    map then leaves 16 consecutive channels in a lane); the 16 bytes of a lane are input channels 32q + 16*half + 0..15 of tap
+    (r,s), k-step index = (r*k + s)*(Cin/32) + q  (csrc/conv_i8.hip)."""
+    cout, cin, ks, _ = q_w.shape
+    assert q_w.dtype == torch.int8 and cout % 32 == 0 and cin % 32 == 0
+    nq = cin // 32
+    w6 = q_w.detach().permute(0, 2, 3, 1).reshape(cout // 32, 32, ks, ks, nq, 2, 16)
+    w6 = w6[:, _i8_rows(q_w.device)]                      # [slab][m][r][s][q][half][16]
+    return w6.permute(0, 2, 3, 4, 5, 1, 6).reshape(cout // 32, ks * ks * nq, 64, 16).contiguous()
+
+
+def unpack_conv_weight_i8(packed, cin, ks):
+    """the inverse of pack_conv_weight_i8: [Cout/32][k*k*Cin/32][64][16] -> [Cout,Cin,k,k] int8"""
+    slabs, nq = packed.shape[0], cin // 32
+    w6 = packed.reshape(slabs, ks, ks, nq, 2, 32, 16).permute(0, 5, 1, 2, 3, 4, 6)    # [slab][m][r][s][q][half][16]
+    out = torch.empty_like(w6)
+    out[:, _i8_rows(packed.device)] = w6
+    return out.reshape(slabs * 32, ks, ks, cin).permute(0, 3, 1, 2).contiguous()
+
+
+def conv2d_i8_supported(cin, cout, ks, stride):
+    """does lfd_conv2d_nhwc_i8 have a kernel for this layer (channels as the plan pads them)?  Nothing launched."""
+    return lib().lfd_conv2d_nhwc_i8_supported(cin, cout, ks, stride) == 0
+
+
+def conv2d_nhwc_i8(x, w_packed, mult, biasq, cout, ks, stride, relu, residual=None, res_mult=0.0, out_scale=None, out=None,
+                   out_f16=None):
+    """x [N,H,W,cin] int8 -> (q_out [N,OH,OW,cout] int8, fp16 map | None): the INT8 mode's conv with its requantising epilogue
+    (include/lfd_hip.h).  out_scale (s_out) not None: the un-requantised fp16 map is stored as well (a pyramid tap)."""
+    require_cuda(x, 'conv2d_i8')
+    if x.dtype != torch.int8 or not x.is_contiguous() or x.dim() != 4:
+        raise RuntimeError('conv2d_nhwc_i8: x must be contiguous int8 NHWC')
+    n, h, w_, cin = x.shape
+    pad = ks // 2
+    oh = (h + 2 * pad - ks) // stride + 1
+    ow = (w_ + 2 * pad - ks) // stride + 1
+    d = _lib.ConvDesc(n, h, w_, cin, cout, ks, stride, int(relu), 0, 0)
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty((n, oh, ow, cout), dtype=torch.int8, device=x.device)
+        if out_scale is not None and out_f16 is None:
+            out_f16 = torch.empty((n, oh, ow, cout), dtype=torch.float16, device=x.device)
+        check(lib().lfd_conv2d_nhwc_i8(C.byref(d), ptr(x), ptr(w_packed), ptr(mult), ptr(biasq), ptr(residual), float(res_mult),
+                                       ptr(out), ptr(out_f16), float(out_scale if out_scale is not None else 0.0), stream_ptr()),
+              'lfd_conv2d_nhwc_i8')
+    return out, out_f16
+
+
+def quantize_f16_i8(x, inv_scale, out=None, channels=None):
+    """fp16 tensor -> int8 of the same shape: clamp(rint(float(x) * inv_scale), -127, 127) (lfd_quantize_nhwc_f16_i8).
+    channels > x.shape[-1]: the last axis is widened to `channels` with zeros (lfd_quantize_pad_nhwc_f16_i8)."""
+    require_cuda(x, 'quantize_f16_i8')
+    if x.dtype != torch.float16 or not x.is_contiguous() or x.numel() < 1:
+        raise RuntimeError('quantize_f16_i8: x must be a non-empty contiguous fp16 tensor')
+    with torch.cuda.device(x.device):
+        if channels is not None and channels != x.shape[-1]:
+            if out is None:
+                out = torch.empty(tuple(x.shape[:-1]) + (channels,), dtype=torch.int8, device=x.device)
+            check(lib().lfd_quantize_pad_nhwc_f16_i8(ptr(x), ptr(out), x.numel() // x.shape[-1], x.shape[-1], channels,
+                                                     float(inv_scale), stream_ptr()), 'lfd_quantize_pad_nhwc_f16_i8')
+            return out
+        if out is None:
+            out = torch.empty(x.shape, dtype=torch.int8, device=x.device)
+        check(lib().lfd_quantize_nhwc_f16_i8(ptr(x), ptr(out), x.numel(), float(inv_scale), stream_ptr()), 'lfd_quantize_nhwc_f16_i8')
+    return out
+
+
 def upsample_nearest_add_(dst, src):
     """dst [N,H,W,C] += nearest-neighbour resize of src [N,h,w,C] (fp16 NHWC, in place): the FPN merge step"""
     _nhwc16(dst, 'upsample_nearest_add')

@@ -1,0 +1,133 @@
+"""The INT8 deployment mode (lfd_amd.deployment, csrc/conv_i8.hip) against the 'fp16' mode, frames resident in device memory (NHWC
+fp16, 1920 x 1080 unless --size=HxW):
+
+    python tools/bench_int8.py [CONFIG ...] [--bs=8,1] [--size=1080x1920] [--out=FILE]
+
+per configuration (default WIDERFACE_LFD_S, WIDERFACE_LFD_XS, TT100K_LFD_L) and batch size:
+  * stages: the quantise launch + the int8 plan's layer-by-layer stage launches (Int8Plan.run_stages) against the fp16 plan's
+    stage launches (EnginePlan._run_convs: fused blocks, downsample pairs), eager launches on one stream;
+  * forward: Int8Engine.forward_resident against LFD.forward_resident in the 'fp16' mode, both as one graph replay;
+  * detect: forward + LFD.detect (decode, threshold, NMS on the device) behind each of the two forwards;
+  * layers: every distinct int8 launch of the plan at that frame size on its own -- microseconds per call and TOP/s
+    (2 * n * oh * ow * cout * cin * ks^2 integer operations of the padded layer over the call time).
+The pairs follow tools/bench_resnet.py: HIP events around `reps` back-to-back calls, alternating the two sides, the median of
+`rounds` such windows divided by `reps` and max - min of the windows as the spread -- call times (kernel + launch), not profiler
+kernel times.  The calibration set is four seeded frames of a quarter of the size: scales do not change a launch's time.
+
+Records, no pass / fail gate.  Prints one JSON line; --out=FILE also keeps the results gathered so far after every measurement."""
+import json
+import os
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'lfd-a-light-and-fast-detector_amd')):
+    sys.path.insert(0, p)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from lfd_amd import INT8Calibrator, build_int8_engine, configs, engine  # noqa: E402
+
+
+def opt(name, default):
+    return ([a[len(name) + 3:] for a in sys.argv[1:] if a.startswith('--%s=' % name)] or [default])[0]
+
+
+NAMES = [a for a in sys.argv[1:] if not a.startswith('--')] or ['WIDERFACE_LFD_S', 'WIDERFACE_LFD_XS', 'TT100K_LFD_L']
+BATCHES = [int(v) for v in opt('bs', '8,1').split(',')]
+H, W = [int(v) for v in opt('size', '1080x1920').split('x')]
+OUT = opt('out', None)
+REPS, ROUNDS = 20, 7
+assert torch.cuda.is_available(), 'bench_int8.py measures on the GPU'
+res = dict(workload='INT8 deployment mode vs the fp16 mode, %dx%d NHWC fp16 frames' % (W, H), reps=REPS, rounds=ROUNDS, configs={})
+
+
+def save():
+    if OUT:
+        json.dump(res, open(OUT, 'w'), indent=1)
+
+
+def window_ms(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def pair(*sides, reps=REPS):
+    """-> [(median ms, max - min ms)] per side over alternating windows"""
+    for _ in range(2):
+        for f in sides:
+            window_ms(f, reps)
+    ts = [[] for _ in sides]
+    for _ in range(ROUNDS):
+        for k, f in enumerate(sides):
+            ts[k].append(window_ms(f, reps))
+    return [(float(np.median(t)), float(max(t) - min(t))) for t in ts]
+
+
+def both(tag8, tag16, got, unit=1.0, nd=4):
+    return {tag8: round(got[0][0] * unit, nd), tag8 + '_spread': round(got[0][1] * unit, nd),
+            tag16: round(got[1][0] * unit, nd), tag16 + '_spread': round(got[1][1] * unit, nd),
+            'int8_over_fp16': round(got[0][0] / got[1][0], 3)}
+
+
+with torch.no_grad():
+    for name in NAMES:
+        m = configs.build_model(name)
+        configs.perturb_weights(m)
+        m.eval().cuda()
+        frames = (torch.rand(4, 3, H // 4, W // 4, generator=torch.Generator().manual_seed(5)) * 2 - 1).numpy()
+        cache = os.path.join(tempfile.mkdtemp(prefix='bench_int8_'), 'cal.json')
+        eng = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2))
+        plan8 = eng.plan
+        plan16 = engine.get_plan(m, m._backbone, m._neck, m._head, torch.device('cuda', torch.cuda.current_device()))
+        ent = res['configs'][name] = dict(int8_launches=len(plan8.layers) + 1, fp16_stage_launches=len(plan16.convs))
+        for bs in BATCHES:
+            x = (torch.rand(bs, H, W, 3, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1)) * 2 - 1).half()
+            meta = torch.tensor([[float(W), float(H), 1.0]] * bs, device='cuda')
+            fmt = engine.IN_NHWC_F16
+            st8, st16 = plan8.state_for(bs, H, W), plan16.state_for(bs, H, W)
+            plan8.run_all(x, fmt, st8)
+            plan16.run_all(x, fmt, st16)
+            torch.cuda.synchronize()
+            r = ent['bs%d' % bs] = {}
+
+            def stages8():
+                plan8.run_quantise(st8)
+                plan8.run_stages(st8)
+
+            r['stages_ms'] = both('int8', 'fp16', pair(stages8, lambda: plan16._run_convs(st16), reps=5))
+            save()
+            eng.use_graph = m.use_graph = True
+            r['forward_ms'] = both('int8', 'fp16', pair(lambda: eng.forward_resident(x), lambda: m.forward_resident(x)))
+            save()
+            thr = float(np.quantile(st16.cls.sigmoid().float().cpu().numpy(), 0.999)) if st16.cls.shape[2] == 1 else 0.5
+            r['detect_ms'] = both('int8', 'fp16', pair(lambda: eng.detect(x, meta, score_thr=thr),
+                                                      lambda: m.detect(m.forward_resident(x), meta, score_thr=thr)))
+            eng.use_graph = m.use_graph = False
+            save()
+            # ---- every distinct int8 launch on its own
+            layers = {}
+            for c in plan8.layers:
+                src = st8.qbufs[c.src]
+                key = '%dto%d k%d s%d %dx%d%s%s' % (c.cin, c.cout, c.ks, c.stride, src.shape[1], src.shape[2],
+                                                     ' +res' if c.res is not None else '', ' +tap' if c.tap is not None else '')
+                if key in layers:
+                    continue
+                (t, spread), = pair(lambda: plan8.run_layer(c, st8))
+                dst = st8.qbufs[c.dst]
+                ops_ = 2.0 * dst.numel() * c.cin * c.ks * c.ks
+                layers[key] = dict(us=round(1e3 * t, 2), spread_us=round(1e3 * spread, 2), TOPs=round(ops_ / (t * 1e-3) / 1e12, 1))
+            r['layers'] = layers
+            save()
+            del x, st8, st16
+            plan8._shape_cache.clear()
+            plan16._shape_cache.clear()
+            m.__dict__.get('_step_graphs', {}).clear()
+            torch.cuda.empty_cache()
+        del m, eng, plan8, plan16
+        torch.cuda.empty_cache()
+print(json.dumps(res))
