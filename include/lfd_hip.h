@@ -650,6 +650,26 @@ LFD_API int lfd_quantize_pad_nhwc_f16_i8(const void* in, void* out, int64_t pixe
                                          lfd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * INT8 calibration histogram (csrc/calib_hist.hip; lfd_amd/calibration.py): the counts from which the percentile,
+ * entropy and MSE thresholds are computed on the host.  Stands where the reference hands its calibration batches to
+ * tensorrt.IInt8EntropyCalibrator2 (lfd/deployment/tensorrt/build_engine.py:22).
+ *
+ * lfd_abs_histogram_f16: x [rows, c] fp16; hist[bits(x[r][ch]) & 0x7fff] += 1 for every r < rows and ch < c_real.  The 32768
+ * bins are the fp16 magnitudes themselves (+0 and -0 share bin 0; the Inf and NaN patterns, bins >= 0x7c00, are counted in
+ * their own bins: judging them is the caller's business).  Channels c_real .. c - 1 (the plan's zero padding) are not counted,
+ * whatever they hold.  hist [32768] uint64 on the device is added to, never cleared: calls accumulate.  Integer sums do not
+ * depend on the order, so equal inputs give equal bits.
+ * c % 8 == 0, 1 <= c_real <= c, rows >= 0, x 16-byte aligned, hist 8-byte aligned (LFD_ERR_INVALID_ARGUMENT otherwise);
+ * rows == 0 returns LFD_OK and launches nothing.  A workgroup counts in 32-bit bins and flushes them once, at its end: a map
+ * of more than 2^39 elements (rows * c), whose share per workgroup could wrap a bin, is refused with LFD_ERR_UNSUPPORTED
+ * (nothing written) rather than flushed early -- split such a map by rows.
+ * Geometry (restated by the tests): at most LFD_CALIB_HIST_MAX_WORKGROUPS workgroups, each walking chunks of
+ * LFD_CALIB_HIST_CHUNK_VECS 16-byte vectors (8 elements each) with the grid as stride. */
+#define LFD_CALIB_HIST_MAX_WORKGROUPS 256
+#define LFD_CALIB_HIST_CHUNK_VECS 4096
+LFD_API int lfd_abs_histogram_f16(const void* x, int64_t rows, int32_t c, int32_t c_real, uint64_t* hist, lfd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * 'fp32_storage' precision mode of the eval forward (LFD.precision = 'fp32_storage'): a shipped mode of the product for
  * callers that need the reference's fp32 outputs to <= 1e-4 on the raw logits (north_star: "cls/bbox tensors within
  * 1e-3"); replaces the same reference code as the fp16 entry points above -- nn.Conv2d + eval BatchNorm2d (+ residual)

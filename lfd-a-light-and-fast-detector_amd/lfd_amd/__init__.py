@@ -8,10 +8,14 @@ Host-side mirror of the reference's operator interface (`LFDResNet`, `SimpleNeck
 __version__ = '0.1.0'
 
 _DEPLOYMENT = ('INT8Calibrator', 'Int8Engine', 'build_int8_engine')      # lfd_amd/deployment.py, imported on first use
+_CALIBRATION = ('calibration',)                                          # lfd_amd/calibration.py: the INT8 calibration rules
 
 
 def __getattr__(name):
     if name in _DEPLOYMENT:
         from . import deployment
         return getattr(deployment, name)
+    if name in _CALIBRATION:
+        import importlib
+        return importlib.import_module('.' + name, __name__)
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -8,7 +8,13 @@ INT8Calibrator + build_tensorrt_engine(..., precision_mode='int8', int8_calibrat
 The calibrator mirrors the reference's constructor and method names; what is calibrated, and how, is this project's own contract
 (lfd_amd/engine_i8.py) -- TensorRT's entropy calibration is proprietary and is not reproduced.  The cache is UTF-8
 JSON: {"format", "version", "state_sha256", "amax": {tensor name: largest |value| over the calibration batches}}; a cache
-written for other weights (another sha) or another layer list is ignored and calibration runs again."""
+written for other weights (another sha) or another layer list is ignored and calibration runs again.
+
+Calibration rules (lfd_amd/calibration.py): INT8Calibrator(..., algorithm='amax' | 'percentile' | 'entropy' | 'mse',
+**the rule's parameters).  'amax' (the default) is the path above, unchanged.  The other rules clip: one pass over the batches
+collects a magnitude histogram of every tensor on the device (csrc/calib_hist.hip), the thresholds are chosen from it on the host,
+and the cache is version 2: {"format", "version", "state_sha256", "algorithm", "params", "amax", "threshold"}, used only when sha,
+tensor names, algorithm and params all match.  A version-1 cache never satisfies a clipping calibrator, and the reverse."""
 import hashlib
 import json
 import os
@@ -16,10 +22,11 @@ import os
 import numpy
 import torch
 
-from . import engine, engine_i8
+from . import calibration, engine, engine_i8
 
 CACHE_FORMAT = 'lfd_amd.int8_calibration'
 CACHE_VERSION = 1
+CACHE_VERSION_RULES = 2      # caches of the clipping rules ('percentile', 'entropy', 'mse')
 
 
 def state_sha256(state_dict):
@@ -53,11 +60,43 @@ def decode_cache(blob, sha, names):
         return None
 
 
+def encode_cache_v2(sha, algorithm, params, amax, threshold):
+    """version-2 cache bytes of a clipping rule: the rule, its full parameter dict, and per tensor the amax seen and the
+    threshold chosen (floats as their shortest round-tripping decimal: decoding gives the same bits)"""
+    return json.dumps(dict(format=CACHE_FORMAT, version=CACHE_VERSION_RULES, state_sha256=sha, algorithm=algorithm,
+                           params=dict(params), amax=dict((k, float(v)) for k, v in amax.items()),
+                           threshold=dict((k, float(v)) for k, v in threshold.items())), indent=1).encode('utf-8')
+
+
+def decode_cache_v2(blob, sha, names, algorithm, params):
+    """cache bytes -> ({name: amax}, {name: threshold}), or None when the bytes are not a version-2 cache for these weights,
+    these tensors, this rule and these parameters"""
+    try:
+        d = json.loads(blob.decode('utf-8'))
+    except (ValueError, AttributeError):
+        return None
+    if not isinstance(d, dict) or d.get('format') != CACHE_FORMAT or d.get('version') != CACHE_VERSION_RULES:
+        return None
+    if d.get('state_sha256') != sha or d.get('algorithm') != algorithm or d.get('params') != dict(params):
+        return None
+    amax, thr = d.get('amax'), d.get('threshold')
+    if not isinstance(amax, dict) or not isinstance(thr, dict) or sorted(amax) != sorted(names) or sorted(thr) != sorted(names):
+        return None
+    try:
+        return dict((k, float(amax[k])) for k in names), dict((k, float(thr[k])) for k in names)
+    except (TypeError, ValueError):
+        return None
+
+
 class INT8Calibrator(object):
     """Calibration frames in batches, and the cache file.  data: float32 [N,C,H,W], each image already normalised (numpy array
-    or torch tensor); frames beyond the last whole batch are not used, as in the reference."""
+    or torch tensor); frames beyond the last whole batch are not used, as in the reference.  algorithm and its parameters
+    (lfd_amd/calibration.py: 'amax'; 'percentile': percentile; 'entropy': nbins, nlevels, start_bin, stride; 'mse': nbins,
+    start_bin, stride) come after the reference's arguments; an unknown rule or a value out of range is a ValueError here."""
 
-    def __init__(self, data, cache_file, batch_size=8, device=None):
+    def __init__(self, data, cache_file, batch_size=8, device=None, algorithm='amax', **params):
+        self.algorithm = algorithm
+        self.params = calibration.check_params(algorithm, params)
         self._cache_file = cache_file
         self._batch_size = int(batch_size)
         if isinstance(data, torch.Tensor):
@@ -94,13 +133,17 @@ class INT8Calibrator(object):
 
 
 class Int8Engine(object):
-    """An LFD model's eval forward with int8 residual stages.  scales: {tensor name: (amax, scale)}; calibrated: whether this
-    build ran the calibration batches (False: the cache was used)."""
+    """An LFD model's eval forward with int8 residual stages.  scales: {tensor name: (threshold, scale)}, the threshold being
+    the amax under the default rule; calibrated: whether this build ran the calibration batches (False: the cache was used);
+    calibration: {'algorithm', 'params', 'amax': {name: value}, 'threshold': {name: value}, 'clipped': {name: share of the
+    calibration elements above the threshold}} ('clipped' is None where the thresholds came from a cache, which does not
+    keep it)."""
 
-    def __init__(self, model, plan, calibrated):
+    def __init__(self, model, plan, calibrated, calibration=None):
         self.model = model
         self.plan = plan
         self.calibrated = calibrated
+        self.calibration = calibration
         self.use_graph = False
 
     @property
@@ -164,25 +207,43 @@ def build_int8_engine(model, int8_calibrator):
         plan = engine_i8.Int8Plan(model._backbone, model._neck, model._head, device)
     sha = state_sha256(model.state_dict())
     blob = int8_calibrator.read_calibration_cache()
-    amax = decode_cache(blob, sha, plan.tensor_names) if blob is not None else None
-    calibrated = amax is None
-    if calibrated:
-        def batches():
-            while True:
-                b = int8_calibrator.get_batch([])
-                if b is None:
-                    return
-                yield b.to(device)
-        seen = [0]
+    seen = [0]
 
-        def counted():
-            for b in batches():
-                seen[0] += 1
-                yield b
-        amax = plan.calibrate(counted())
+    def counted():
+        while True:
+            b = int8_calibrator.get_batch([])
+            if b is None:
+                return
+            seen[0] += 1
+            yield b.to(device)
+
+    def check_seen():
         if seen[0] == 0:
             raise RuntimeError('build_int8_engine: the calibrator has no whole batch (fewer frames than batch_size, or already '
                                'consumed) and no usable cache')
-        int8_calibrator.write_calibration_cache(encode_cache(sha, amax))
-    plan.set_scales(amax)
-    return Int8Engine(model, plan, calibrated)
+
+    algorithm = getattr(int8_calibrator, 'algorithm', 'amax')
+    if algorithm == 'amax':
+        amax = decode_cache(blob, sha, plan.tensor_names) if blob is not None else None
+        calibrated = amax is None
+        if calibrated:
+            amax = plan.calibrate(counted())
+            check_seen()
+            int8_calibrator.write_calibration_cache(encode_cache(sha, amax))
+        plan.set_scales(amax)
+        return Int8Engine(model, plan, calibrated, dict(algorithm='amax', params={}, amax=dict(amax), threshold=dict(amax),
+                                                        clipped=dict((k, 0.0) for k in amax)))
+    # a clipping rule: one histogram pass, thresholds on the host, a version-2 cache
+    params = calibration.check_params(algorithm, getattr(int8_calibrator, 'params', None))
+    got = decode_cache_v2(blob, sha, plan.tensor_names, algorithm, params) if blob is not None else None
+    calibrated = got is None
+    if calibrated:
+        hists = plan.calibrate_histograms(counted())
+        check_seen()
+        res = calibration.thresholds(hists, algorithm, **params)
+        amax, thr, clipped = res['amax'], res['threshold'], res['clipped']
+        int8_calibrator.write_calibration_cache(encode_cache_v2(sha, algorithm, params, amax, thr))
+    else:
+        (amax, thr), clipped = got, None
+    plan.set_scales(thr)
+    return Int8Engine(model, plan, calibrated, dict(algorithm=algorithm, params=params, amax=amax, threshold=thr, clipped=clipped))

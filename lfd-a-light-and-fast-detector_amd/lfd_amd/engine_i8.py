@@ -16,6 +16,7 @@ Numeric contract (symmetric, range [-127, 127], no zero points):
 There is no fp16 fallback: a model outside the coverage raises engine.Unsupported."""
 import ctypes as C
 
+import numpy
 import torch
 import torch.nn.functional as F
 
@@ -95,12 +96,14 @@ def check_model(model):
 
 class Int8Plan(engine.EnginePlan):
     """engine.EnginePlan whose residual stages are int8 launches.  Built without scales (layers, folded and quantised weights);
-    calibrate() measures the amax of every named tensor in fp16, set_scales() turns them into the launches' constants."""
+    calibrate() measures the amax of every named tensor in fp16 (calibrate_histograms(): its magnitude histogram, for the
+    clipping rules of lfd_amd/calibration.py), set_scales() turns one value per tensor into the launches' constants."""
 
     def __init__(self, backbone, neck=None, head=None, device=None):
         self.layers = []
         self.scales = None
         super().__init__(backbone, neck, head, device)
+        self.stem_channels_real = netdesc.backbone_layers(backbone).stem[-1].conv.out_channels
 
     # ---- lowering
     def _build_stages(self, blocks, cur, new_buf):
@@ -168,15 +171,10 @@ class Int8Plan(engine.EnginePlan):
                 self.tap_channels.append(blk.convs[-1].conv.out_channels)
                 self.tap_ready_after.append(len(self.convs) + len(self.layers))
 
-    # ---- calibration (offline: fp16 kernels where they exist, torch otherwise; amax with torch)
-    def calibrate(self, batches):
-        """batches: iterable of device frame batches (any format the stem accepts) -> {tensor name: amax (float)} over all of
-        them.  Runs the stem launches and then the layer list in fp16, one layer at a time."""
-        amax = dict((k, 0.0) for k in self.tensor_names)
-
-        def see(name, t):
-            amax[name] = max(amax[name], float(t.float().abs().max()))
-
+    # ---- calibration (offline: fp16 kernels where they exist, torch otherwise)
+    def _calibration_walk(self, batches, see):
+        """the stem launches and then the layer list in fp16, one layer at a time, over every batch; see(name, t, c_real) is
+        called with each named tensor t (fp16 NHWC, channels c_real .. zero padding)"""
         with torch.no_grad():
             for x in batches:
                 x = x.contiguous()
@@ -187,7 +185,7 @@ class Int8Plan(engine.EnginePlan):
                     t = st.bufs[self.stage_in]
                     if t.shape[3] != self.qbuf_channels[0]:       # a 32-channel stem in front of stages padded to 64
                         t = F.pad(t, (0, self.qbuf_channels[0] - t.shape[3]))
-                    see(STEM, t)
+                    see(STEM, t, self.stem_channels_real)
                     outs = {0: t}
                     for c in self.layers:
                         res = outs[c.res] if c.res is not None else None
@@ -204,10 +202,34 @@ class Int8Plan(engine.EnginePlan):
                             if c.relu:
                                 y = y.relu()
                             y = y.half().contiguous()
-                        see(c.name, y)
+                        see(c.name, y, c.cout_real)
                         outs[c.dst] = y
             self._shape_cache = dict((k, v) for k, v in self._shape_cache.items() if k[3] != 'calibrate')
+
+    def calibrate(self, batches):
+        """batches: iterable of device frame batches (any format the stem accepts) -> {tensor name: amax (float)} over all of
+        them (amax with torch).  Runs the stem launches and then the layer list in fp16, one layer at a time."""
+        amax = dict((k, 0.0) for k in self.tensor_names)
+
+        def see(name, t, c_real):
+            amax[name] = max(amax[name], float(t.float().abs().max()))
+
+        self._calibration_walk(batches, see)
         return amax
+
+    def calibrate_histograms(self, batches):
+        """the same fp16 walk -> {tensor name: numpy int64 [32768]}: the magnitude histogram (ops.abs_histogram_f16) of every
+        named tensor's real channels over all batches, from which lfd_amd/calibration.py chooses the thresholds"""
+        hists = {}
+
+        def see(name, t, c_real):
+            if name not in hists:
+                hists[name] = torch.zeros(ops.ABS_HIST_BINS, dtype=torch.int64, device=self.device)
+            ops.abs_histogram_f16(t.contiguous(), c_real, out=hists[name])
+
+        self._calibration_walk(batches, see)
+        zero = numpy.zeros(ops.ABS_HIST_BINS, dtype=numpy.int64)
+        return dict((k, hists[k].cpu().numpy() if k in hists else zero.copy()) for k in self.tensor_names)
 
     def set_scales(self, amax):
         """{tensor name: amax} -> the constants of every launch; self.scales = {name: (amax, scale)}"""

@@ -954,6 +954,28 @@ def quantize_f16_i8(x, inv_scale, out=None, channels=None):
     return out
 
 
+ABS_HIST_BINS = 32768        # one bin per fp16 magnitude pattern (bits & 0x7fff)
+
+
+def abs_histogram_f16(t, c_real=None, out=None):
+    """fp16 tensor [..., c] -> int64 device tensor [32768]: out[bits & 0x7fff] += 1 for every element in channels below c_real
+    (default: all of them) -- lfd_abs_histogram_f16.  out: an int64 [32768] device tensor to add to (accumulation over batches);
+    None: a new zeroed one.  c must be a multiple of 8; a tensor without elements leaves out as it is."""
+    require_cuda(t, 'abs_histogram_f16')
+    if t.dtype != torch.float16 or not t.is_contiguous() or t.dim() < 1:
+        raise RuntimeError('abs_histogram_f16: t must be a contiguous fp16 tensor with a channel axis')
+    c = int(t.shape[-1])
+    c_real = c if c_real is None else int(c_real)
+    with torch.cuda.device(t.device):
+        if out is None:
+            out = torch.zeros(ABS_HIST_BINS, dtype=torch.int64, device=t.device)
+        elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != ABS_HIST_BINS or out.device != t.device:
+            raise RuntimeError('abs_histogram_f16: out must be a contiguous int64 [%d] tensor on the device of t' % ABS_HIST_BINS)
+        rows = t.numel() // c if c else 0
+        check(lib().lfd_abs_histogram_f16(ptr(t), rows, c, c_real, ptr(out), stream_ptr()), 'lfd_abs_histogram_f16')
+    return out
+
+
 def upsample_nearest_add_(dst, src):
     """dst [N,H,W,C] += nearest-neighbour resize of src [N,h,w,C] (fp16 NHWC, in place): the FPN merge step"""
     _nhwc16(dst, 'upsample_nearest_add')
