@@ -649,6 +649,36 @@ LFD_API int lfd_quantize_nhwc_f16_i8(const void* in, void* out, int64_t count, f
 LFD_API int lfd_quantize_pad_nhwc_f16_i8(const void* in, void* out, int64_t pixels, int32_t cin, int32_t cout, float inv_scale,
                                          lfd_stream_t stream);
 
+/* Fused int8 launches (csrc/block_i8.hip; the fused=True route of lfd_amd/engine_i8.py).  Both equal the lfd_conv2d_nhwc_i8
+ * launches they replace in every bit: the i32 sums are exact and the epilogues are the expressions above.
+ *
+ * lfd_block_i8_fused: a whole residual block, y = ReLU(conv2(ReLU(conv1(x))) + x), both convs 3x3, stride 1, pad 1, 64 -> 64
+ * channels.  in [n,h,w,64] int8; w1_packed / mult1 / biasq1 and w2_packed / mult2 / biasq2: the operands of the two
+ * lfd_conv2d_nhwc_i8 calls (the same fragment order: nothing is repacked); res_mult: conv2's, for the identity x.
+ *   mid     = clamp(rint(max(fmaf((float)acc1, mult1[c], biasq1[c]), 0)), -127, 127), int8, never written to memory; mid pixels
+ *             outside the image are conv2's zero padding (0, not conv1 evaluated there)
+ *   v       = max(fmaf((float)x, res_mult, fmaf((float)acc2, mult2[c], biasq2[c])), 0)
+ *   out_i8  [n,h,w,64] int8 = clamp(rint(v), -127, 127)
+ *   out_f16 [n,h,w,64] fp16 = half(v * out_scale), this v evaluated in float64 as lfd_conv2d_nhwc_i8 does; NULL: not written.
+ * LFD_ERR_INVALID_ARGUMENT: a NULL pointer (but out_f16), a pointer that is not 16-byte aligned, n / h / w < 1, out_i8 == in.
+ * LFD_ERR_UNSUPPORTED: h * w * 128 >= 2^31.  A refused call launches and writes nothing.
+ *
+ * lfd_conv2d_downsample_nhwc_i8: the two stride-2 convs that open a stage-entry block, from one staged input tile:
+ *   out_i8    [n,oh,ow,cout] = the 3x3 stride-2 pad-1 conv (w_packed, mult, biasq) with ReLU
+ *   ds_out_i8 [n,oh,ow,cout] = the 1x1 stride-2 identity branch (ds_w_packed, ds_mult, ds_biasq) without ReLU
+ * oh = (h - 1) / 2 + 1, ow = (w - 1) / 2 + 1; each output follows the epilogue of lfd_conv2d_nhwc_i8 without residual, with
+ * its own constants and therefore its own output scale; no fp16 tap.  (cin, cout) in {(64, 64), (64, 128), (128, 128)}, anything
+ * else LFD_ERR_UNSUPPORTED (lfd_conv2d_downsample_nhwc_i8_supported answers without launching).  Pointers 16-byte aligned, the
+ * three tensors distinct, h * w * 128 < 2^31; status codes as above. */
+LFD_API int lfd_block_i8_fused(int32_t n, int32_t h, int32_t w, const void* in, const void* w1_packed, const float* mult1,
+                               const float* biasq1, const void* w2_packed, const float* mult2, const float* biasq2,
+                               float res_mult, void* out_i8, void* out_f16, float out_scale, lfd_stream_t stream);
+LFD_API int lfd_conv2d_downsample_nhwc_i8_supported(int32_t cin, int32_t cout);
+LFD_API int lfd_conv2d_downsample_nhwc_i8(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, const void* in,
+                                          const void* w_packed, const float* mult, const float* biasq, const void* ds_w_packed,
+                                          const float* ds_mult, const float* ds_biasq, void* out_i8, void* ds_out_i8,
+                                          lfd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * INT8 calibration histogram (csrc/calib_hist.hip; lfd_amd/calibration.py): the counts from which the percentile,
  * entropy and MSE thresholds are computed on the host.  Stands where the reference hands its calibration batches to

@@ -150,6 +150,12 @@ class Int8Engine(object):
     def scales(self):
         return self.plan.scales
 
+    @property
+    def fused(self):
+        """whether the stages run the fused launches of csrc/block_i8.hip (build_int8_engine(..., fused=True)); the bits of every
+        output are the same either way"""
+        return self.plan.fused
+
     def _check_fresh(self):
         m = self.model
         if engine._param_signature(m._backbone, m._neck, m._head) != self.plan.param_sig:
@@ -193,9 +199,11 @@ class Int8Engine(object):
         return self.model.get_results(predict_outputs, *args)
 
 
-def build_int8_engine(model, int8_calibrator):
+def build_int8_engine(model, int8_calibrator, fused=False):
     """LFD model (eval mode, on the device) + INT8Calibrator -> Int8Engine.  Uses the calibrator's cache when it was written
-    for these weights and this layer list; otherwise runs the calibration batches and writes it."""
+    for these weights and this layer list; otherwise runs the calibration batches and writes it.  fused=True: the stages run
+    the fused int8 launches (stage-entry pair, whole 64-channel block) where the layer list has them; layers, scales, cache
+    and every output bit are those of the default layer-by-layer route, and a cache written by either serves the other."""
     assert int8_calibrator is not None, 'calibrator is not provided!'
     engine_i8.check_model(model)
     if model.training:
@@ -204,7 +212,7 @@ def build_int8_engine(model, int8_calibrator):
     if device.type != 'cuda':
         raise RuntimeError('build_int8_engine: the model must be on the MI355X (got %s)' % device)
     with torch.no_grad():
-        plan = engine_i8.Int8Plan(model._backbone, model._neck, model._head, device)
+        plan = engine_i8.Int8Plan(model._backbone, model._neck, model._head, device, fused=fused)
     sha = state_sha256(model.state_dict())
     blob = int8_calibrator.read_calibration_cache()
     seen = [0]

@@ -3,8 +3,11 @@ csrc/conv_i8.hip -- what the reference gets from a TensorRT engine built with pr
 (lfd/deployment/tensorrt/build_engine.py:22-126).  lfd_amd/deployment.py is the public interface.
 
 Split of the network: stem = the parent plan's fp16 launches; one quantise launch; every conv of the residual stages, identity
-branches included, one lfd_conv2d_nhwc_i8 launch each (layer by layer: no fused block kernels yet); a conv whose output is a
-pyramid tap also stores the un-requantised fp16 map the parent's head kernels read.
+branches included, one lfd_conv2d_nhwc_i8 launch each (layer by layer, the default); a conv whose output is a pyramid tap also
+stores the un-requantised fp16 map the parent's head kernels read.  Int8Plan(..., fused=True) runs the same layer list through
+lower_fused(): a stage-entry block's two stride-2 convs as one lfd_conv2d_downsample_nhwc_i8 launch, a 64-channel block without
+a downsample as one lfd_block_i8_fused launch (csrc/block_i8.hip), the rest as before -- the same bits in every tensor the route
+still writes (the int8 map between a fused block's convs stays on chip and has no buffer).
 
 Numeric contract (symmetric, range [-127, 127], no zero points):
   weights      BN-folded fp32 (engine.fold_conv_norm, channels zero-padded to 64 / 128); per output channel
@@ -14,6 +17,7 @@ Numeric contract (symmetric, range [-127, 127], no zero points):
   constants    float64 -> fp32: mult[co] = s_in s_w[co] / s_out, biasq[co] = b[co] / s_out, res_mult = s_res / s_out
   epilogue     include/lfd_hip.h, lfd_conv2d_nhwc_i8
 There is no fp16 fallback: a model outside the coverage raises engine.Unsupported."""
+import collections
 import ctypes as C
 
 import numpy
@@ -73,6 +77,41 @@ class ConvI8(object):
                  'ref_w', 'ref_b', 'q_w', 's_w', 'w', 'w16', 'mult', 'biasq', 'res_mult', 's_in', 's_out', 's_res')
 
 
+# a launch of the fused route over indices into the layer list: 'conv' (i,) one lfd_conv2d_nhwc_i8; 'pair' (downsample, conv1) one
+# lfd_conv2d_downsample_nhwc_i8; 'block' (conv1, conv2) one lfd_block_i8_fused
+Launch = collections.namedtuple('Launch', 'kind layers')
+PAIR_KEYS = ((64, 64), (64, 128), (128, 128))     # (cin, cout) of lfd_conv2d_downsample_nhwc_i8
+
+
+def lower_fused(layers):
+    """the plan's layer list -> the launch list of the fused route (a pure function of the layers' shapes and buffer ids).
+    entry block (downsample 1x1 s2, conv1 3x3 s2 of the same input, conv2 adding the downsample): 'pair' + 'conv';
+    block of two 3x3 s1 convs of 64 (padded) channels whose second adds the first's input: 'block'; everything else: 'conv'."""
+    def reads(buf, but):
+        return [j for j, c in enumerate(layers) if j not in but and (c.src == buf or c.res == buf)]
+
+    out, i = [], 0
+    while i < len(layers):
+        a = layers[i]
+        b = layers[i + 1] if i + 1 < len(layers) else None
+        c = layers[i + 2] if i + 2 < len(layers) else None
+        if b is not None and c is not None and (a.ks, a.stride, a.relu, a.res, a.tap) == (1, 2, False, None, None) \
+                and (b.ks, b.stride, b.relu, b.res, b.tap) == (3, 2, True, None, None) and b.src == a.src \
+                and (a.cin, a.cout) == (b.cin, b.cout) and (a.cin, a.cout) in PAIR_KEYS and c.src == b.dst and c.res == a.dst:
+            out.append(Launch('pair', (i, i + 1)))
+            i += 2
+            continue
+        if b is not None and (a.ks, a.stride, a.relu, a.res, a.tap) == (3, 1, True, None, None) \
+                and (b.ks, b.stride, b.relu) == (3, 1, True) and a.cin == a.cout == b.cin == b.cout == 64 \
+                and b.src == a.dst and b.res == a.src and not reads(a.dst, (i + 1,)):
+            out.append(Launch('block', (i, i + 1)))
+            i += 2
+            continue
+        out.append(Launch('conv', (i,)))
+        i += 1
+    return out
+
+
 def check_model(model):
     """the INT8 mode covers the LFD models of the fused fp16 plan with stage convs of up to 128 (padded) channels; everything
     else is named here (the plan's own constructor refuses the rest)"""
@@ -99,9 +138,11 @@ class Int8Plan(engine.EnginePlan):
     calibrate() measures the amax of every named tensor in fp16 (calibrate_histograms(): its magnitude histogram, for the
     clipping rules of lfd_amd/calibration.py), set_scales() turns one value per tensor into the launches' constants."""
 
-    def __init__(self, backbone, neck=None, head=None, device=None):
+    def __init__(self, backbone, neck=None, head=None, device=None, fused=False):
         self.layers = []
         self.scales = None
+        self.fused = bool(fused)
+        self.launches = None                                  # the fused route's launch list (lower_fused), else None
         super().__init__(backbone, neck, head, device)
         self.stem_channels_real = netdesc.backbone_layers(backbone).stem[-1].conv.out_channels
 
@@ -170,6 +211,16 @@ class Int8Plan(engine.EnginePlan):
                 self.taps.append(self.layers[-1].tap)
                 self.tap_channels.append(blk.convs[-1].conv.out_channels)
                 self.tap_ready_after.append(len(self.convs) + len(self.layers))
+        self.unwritten = frozenset()                          # int8 buffers no launch of this plan's route writes
+        if self.fused:
+            self.launches = lower_fused(self.layers)
+            self.unwritten = frozenset(self.layers[la.layers[0]].dst for la in self.launches if la.kind == 'block')
+            done = dict((la.layers[-1], len(self.convs) + k + 1) for k, la in enumerate(self.launches))
+            self.tap_ready_after = [done[i] for i, c in enumerate(self.layers) if c.tap is not None]
+
+    def int8_launches(self):
+        """int8 launches of the stages per forward (the quantise launch not counted)"""
+        return len(self.launches) if self.fused else len(self.layers)
 
     # ---- calibration (offline: fp16 kernels where they exist, torch otherwise)
     def _calibration_walk(self, batches, see):
@@ -252,6 +303,8 @@ class Int8Plan(engine.EnginePlan):
             st.qbufs = {}
             with torch.cuda.device(self.device):
                 for b, sc in self.qbuf_scale.items():
+                    if b in self.unwritten:                   # the map between a fused block's convs stays on chip
+                        continue
                     hh, ww, s = h, w, sc
                     while s > 1:
                         hh, ww = (hh + 1) // 2, (ww + 1) // 2
@@ -283,8 +336,37 @@ class Int8Plan(engine.EnginePlan):
                                        ptr(st.bufs[c.tap]) if c.tap is not None else None, c.s_out, stream_ptr()),
               'lfd_conv2d_nhwc_i8')
 
+    def run_pair(self, d, c, st):
+        """d: the 1x1 stride-2 identity branch, c: the 3x3 stride-2 conv of the same input, one launch"""
+        src = st.qbufs[c.src]
+        check(lib().lfd_conv2d_downsample_nhwc_i8(st.n, src.shape[1], src.shape[2], c.cin, c.cout, ptr(src), ptr(c.w), ptr(c.mult),
+                                                  ptr(c.biasq), ptr(d.w), ptr(d.mult), ptr(d.biasq), ptr(st.qbufs[c.dst]),
+                                                  ptr(st.qbufs[d.dst]), stream_ptr()), 'lfd_conv2d_downsample_nhwc_i8')
+
+    def run_block(self, c1, c2, st):
+        """a whole residual block (c1 -> c2 + the block's input) in one launch, the tap on it if the block is one"""
+        src = st.qbufs[c1.src]
+        check(lib().lfd_block_i8_fused(st.n, src.shape[1], src.shape[2], ptr(src), ptr(c1.w), ptr(c1.mult), ptr(c1.biasq),
+                                       ptr(c2.w), ptr(c2.mult), ptr(c2.biasq), c2.res_mult, ptr(st.qbufs[c2.dst]),
+                                       ptr(st.bufs[c2.tap]) if c2.tap is not None else None, c2.s_out, stream_ptr()),
+              'lfd_block_i8_fused')
+
     def run_stages(self, st, after=None):
         base = len(self.convs)
+        if self.fused:
+            for k, la in enumerate(self.launches):
+                if after and base + k in after:
+                    after[base + k]()
+                cs = [self.layers[i] for i in la.layers]
+                if la.kind == 'pair':
+                    self.run_pair(cs[0], cs[1], st)
+                elif la.kind == 'block':
+                    self.run_block(cs[0], cs[1], st)
+                else:
+                    self.run_layer(cs[0], st)
+            if after and base + len(self.launches) in after:
+                after[base + len(self.launches)]()
+            return
         for li, c in enumerate(self.layers):
             if after and base + li in after:
                 after[base + li]()

@@ -935,6 +935,50 @@ def conv2d_nhwc_i8(x, w_packed, mult, biasq, cout, ks, stride, relu, residual=No
     return out, out_f16
 
 
+def block_i8_fused(x, w1_packed, mult1, biasq1, w2_packed, mult2, biasq2, res_mult, out_scale=None, out=None, out_f16=None):
+    """x [N,H,W,64] int8 -> (q_out [N,H,W,64] int8, fp16 map | None): a whole residual block in one launch (lfd_block_i8_fused),
+    ReLU(conv2(ReLU(conv1(x))) + x) with the operands of the two conv2d_nhwc_i8 calls it equals bit for bit; the int8 map
+    between the convs stays on chip.  out_scale not None: the fp16 pyramid tap is stored as well."""
+    require_cuda(x, 'block_i8_fused')
+    if x.dtype != torch.int8 or not x.is_contiguous() or x.dim() != 4 or x.shape[3] != 64:
+        raise RuntimeError('block_i8_fused: x must be contiguous int8 NHWC with 64 channels')
+    n, h, w_, _ = x.shape
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty((n, h, w_, 64), dtype=torch.int8, device=x.device)
+        if out_scale is not None and out_f16 is None:
+            out_f16 = torch.empty((n, h, w_, 64), dtype=torch.float16, device=x.device)
+        check(lib().lfd_block_i8_fused(n, h, w_, ptr(x), ptr(w1_packed), ptr(mult1), ptr(biasq1), ptr(w2_packed), ptr(mult2),
+                                       ptr(biasq2), float(res_mult), ptr(out), ptr(out_f16),
+                                       float(out_scale if out_scale is not None else 0.0), stream_ptr()), 'lfd_block_i8_fused')
+    return out, out_f16
+
+
+def conv2d_downsample_i8_supported(cin, cout):
+    """does lfd_conv2d_downsample_nhwc_i8 have a kernel for this stage entry (channels as the plan pads them)?  Nothing
+    launched."""
+    return lib().lfd_conv2d_downsample_nhwc_i8_supported(cin, cout) == 0
+
+
+def conv2d_downsample_nhwc_i8(x, w_packed, mult, biasq, ds_w_packed, ds_mult, ds_biasq, cout, out=None, ds_out=None):
+    """x [N,H,W,cin] int8 -> (3x3 stride-2 conv with ReLU, 1x1 stride-2 identity branch without), both [N,OH,OW,cout] int8, in
+    one launch (lfd_conv2d_downsample_nhwc_i8): the two convs that open a stage-entry block"""
+    require_cuda(x, 'conv2d_downsample_i8')
+    if x.dtype != torch.int8 or not x.is_contiguous() or x.dim() != 4:
+        raise RuntimeError('conv2d_downsample_nhwc_i8: x must be contiguous int8 NHWC')
+    n, h, w_, cin = x.shape
+    oh, ow = (h - 1) // 2 + 1, (w_ - 1) // 2 + 1
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty((n, oh, ow, cout), dtype=torch.int8, device=x.device)
+        if ds_out is None:
+            ds_out = torch.empty((n, oh, ow, cout), dtype=torch.int8, device=x.device)
+        check(lib().lfd_conv2d_downsample_nhwc_i8(n, h, w_, cin, cout, ptr(x), ptr(w_packed), ptr(mult), ptr(biasq),
+                                                  ptr(ds_w_packed), ptr(ds_mult), ptr(ds_biasq), ptr(out), ptr(ds_out),
+                                                  stream_ptr()), 'lfd_conv2d_downsample_nhwc_i8')
+    return out, ds_out
+
+
 def quantize_f16_i8(x, inv_scale, out=None, channels=None):
     """fp16 tensor -> int8 of the same shape: clamp(rint(float(x) * inv_scale), -127, 127) (lfd_quantize_nhwc_f16_i8).
     channels > x.shape[-1]: the last axis is widened to `channels` with zeros (lfd_quantize_pad_nhwc_f16_i8)."""

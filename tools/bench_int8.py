@@ -1,16 +1,19 @@
-"""The INT8 deployment mode (lfd_amd.deployment, csrc/conv_i8.hip) against the 'fp16' mode, frames resident in device memory (NHWC
-fp16, 1920 x 1080 unless --size=HxW):
+"""The INT8 deployment mode (lfd_amd.deployment, csrc/conv_i8.hip, csrc/block_i8.hip), its fused route and its default layer-by-layer
+route, against the 'fp16' mode, frames resident in device memory (NHWC fp16, 1920 x 1080 unless --size=HxW):
 
     python tools/bench_int8.py [CONFIG ...] [--bs=8,1] [--size=1080x1920] [--out=FILE]
 
 per configuration (default WIDERFACE_LFD_S, WIDERFACE_LFD_XS, TT100K_LFD_L) and batch size:
-  * stages: the quantise launch + the int8 plan's layer-by-layer stage launches (Int8Plan.run_stages) against the fp16 plan's
-    stage launches (EnginePlan._run_convs: fused blocks, downsample pairs), eager launches on one stream;
-  * forward: Int8Engine.forward_resident against LFD.forward_resident in the 'fp16' mode, both as one graph replay;
-  * detect: forward + LFD.detect (decode, threshold, NMS on the device) behind each of the two forwards;
-  * layers: every distinct int8 launch of the plan at that frame size on its own -- microseconds per call and TOP/s
-    (2 * n * oh * ow * cout * cin * ks^2 integer operations of the padded layer over the call time).
-The pairs follow tools/bench_resnet.py: HIP events around `reps` back-to-back calls, alternating the two sides, the median of
+  * stages: the quantise launch + the int8 plan's stage launches (Int8Plan.run_stages), fused (build_int8_engine(...,
+    fused=True)) and layer by layer, against the fp16 plan's stage launches (EnginePlan._run_convs: fused blocks, downsample
+    pairs), eager launches on one stream;
+  * forward: Int8Engine.forward_resident of both routes against LFD.forward_resident in the 'fp16' mode, each as one graph replay;
+  * detect: forward + LFD.detect (decode, threshold, NMS on the device) behind each of the three forwards;
+  * layers: every distinct int8 launch of the layer-by-layer plan at that frame size on its own -- microseconds per call and
+    TOP/s (2 * n * oh * ow * cout * cin * ks^2 integer operations of the padded layer over the call time);
+  * fused_launches: every distinct lfd_block_i8_fused / lfd_conv2d_downsample_nhwc_i8 launch of the fused plan next to the two
+    layer-by-layer launches it replaces (their call times added), same units.
+The sides follow tools/bench_resnet.py: HIP events around `reps` back-to-back calls, alternating the sides, the median of
 `rounds` such windows divided by `reps` and max - min of the windows as the spread -- call times (kernel + launch), not profiler
 kernel times.  The calibration set is four seeded frames of a quarter of the size: scales do not change a launch's time.
 
@@ -68,10 +71,16 @@ def pair(*sides, reps=REPS):
     return [(float(np.median(t)), float(max(t) - min(t))) for t in ts]
 
 
-def both(tag8, tag16, got, unit=1.0, nd=4):
-    return {tag8: round(got[0][0] * unit, nd), tag8 + '_spread': round(got[0][1] * unit, nd),
-            tag16: round(got[1][0] * unit, nd), tag16 + '_spread': round(got[1][1] * unit, nd),
-            'int8_over_fp16': round(got[0][0] / got[1][0], 3)}
+def three(got, nd=4):
+    """got: (fused int8, layer-by-layer int8, fp16) sides of pair()"""
+    out = {}
+    for tag, (t, spread) in zip(('int8_fused', 'int8', 'fp16'), got):
+        out[tag] = round(t, nd)
+        out[tag + '_spread'] = round(spread, nd)
+    out['int8_fused_over_fp16'] = round(got[0][0] / got[2][0], 3)
+    out['int8_over_fp16'] = round(got[1][0] / got[2][0], 3)
+    out['int8_fused_over_int8'] = round(got[0][0] / got[1][0], 3)
+    return out
 
 
 with torch.no_grad():
@@ -82,15 +91,19 @@ with torch.no_grad():
         frames = (torch.rand(4, 3, H // 4, W // 4, generator=torch.Generator().manual_seed(5)) * 2 - 1).numpy()
         cache = os.path.join(tempfile.mkdtemp(prefix='bench_int8_'), 'cal.json')
         eng = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2))
-        plan8 = eng.plan
+        engf = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2), fused=True)      # from the cache just written
+        assert not engf.calibrated
+        plan8, planf = eng.plan, engf.plan
         plan16 = engine.get_plan(m, m._backbone, m._neck, m._head, torch.device('cuda', torch.cuda.current_device()))
-        ent = res['configs'][name] = dict(int8_launches=len(plan8.layers) + 1, fp16_stage_launches=len(plan16.convs))
+        ent = res['configs'][name] = dict(int8_launches=len(plan8.layers) + 1, int8_fused_launches=planf.int8_launches() + 1,
+                                        fp16_stage_launches=len(plan16.convs))
         for bs in BATCHES:
             x = (torch.rand(bs, H, W, 3, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1)) * 2 - 1).half()
             meta = torch.tensor([[float(W), float(H), 1.0]] * bs, device='cuda')
             fmt = engine.IN_NHWC_F16
-            st8, st16 = plan8.state_for(bs, H, W), plan16.state_for(bs, H, W)
+            st8, stf, st16 = plan8.state_for(bs, H, W), planf.state_for(bs, H, W), plan16.state_for(bs, H, W)
             plan8.run_all(x, fmt, st8)
+            planf.run_all(x, fmt, stf)
             plan16.run_all(x, fmt, st16)
             torch.cuda.synchronize()
             r = ent['bs%d' % bs] = {}
@@ -99,35 +112,69 @@ with torch.no_grad():
                 plan8.run_quantise(st8)
                 plan8.run_stages(st8)
 
-            r['stages_ms'] = both('int8', 'fp16', pair(stages8, lambda: plan16._run_convs(st16), reps=5))
+            def stagesf():
+                planf.run_quantise(stf)
+                planf.run_stages(stf)
+
+            assert torch.equal(stf.cls, st8.cls) and torch.equal(stf.reg, st8.reg), 'the fused route must equal the default bit for bit'
+            r['stages_ms'] = three(pair(stagesf, stages8, lambda: plan16._run_convs(st16), reps=5))
             save()
-            eng.use_graph = m.use_graph = True
-            r['forward_ms'] = both('int8', 'fp16', pair(lambda: eng.forward_resident(x), lambda: m.forward_resident(x)))
+            eng.use_graph = engf.use_graph = m.use_graph = True
+            r['forward_ms'] = three(pair(lambda: engf.forward_resident(x), lambda: eng.forward_resident(x), lambda: m.forward_resident(x)))
             save()
             thr = float(np.quantile(st16.cls.sigmoid().float().cpu().numpy(), 0.999)) if st16.cls.shape[2] == 1 else 0.5
-            r['detect_ms'] = both('int8', 'fp16', pair(lambda: eng.detect(x, meta, score_thr=thr),
-                                                      lambda: m.detect(m.forward_resident(x), meta, score_thr=thr)))
-            eng.use_graph = m.use_graph = False
+            r['detect_ms'] = three(pair(lambda: engf.detect(x, meta, score_thr=thr), lambda: eng.detect(x, meta, score_thr=thr),
+                                        lambda: m.detect(m.forward_resident(x), meta, score_thr=thr)))
+            eng.use_graph = engf.use_graph = m.use_graph = False
             save()
             # ---- every distinct int8 launch on its own
             layers = {}
-            for c in plan8.layers:
+
+            def layer_key(c):
                 src = st8.qbufs[c.src]
-                key = '%dto%d k%d s%d %dx%d%s%s' % (c.cin, c.cout, c.ks, c.stride, src.shape[1], src.shape[2],
-                                                     ' +res' if c.res is not None else '', ' +tap' if c.tap is not None else '')
+                return '%dto%d k%d s%d %dx%d%s%s' % (c.cin, c.cout, c.ks, c.stride, src.shape[1], src.shape[2],
+                                                      ' +res' if c.res is not None else '', ' +tap' if c.tap is not None else '')
+
+            def layer_ops(c):
+                return 2.0 * st8.qbufs[c.dst].numel() * c.cin * c.ks * c.ks
+
+            for c in plan8.layers:
+                key = layer_key(c)
                 if key in layers:
                     continue
                 (t, spread), = pair(lambda: plan8.run_layer(c, st8))
-                dst = st8.qbufs[c.dst]
-                ops_ = 2.0 * dst.numel() * c.cin * c.ks * c.ks
-                layers[key] = dict(us=round(1e3 * t, 2), spread_us=round(1e3 * spread, 2), TOPs=round(ops_ / (t * 1e-3) / 1e12, 1))
+                layers[key] = dict(us=round(1e3 * t, 2), spread_us=round(1e3 * spread, 2), TOPs=round(layer_ops(c) / (t * 1e-3) / 1e12, 1))
             r['layers'] = layers
             save()
-            del x, st8, st16
+            # ---- every distinct fused launch against the two layer-by-layer launches it replaces
+            fl = {}
+            for la in planf.launches:
+                if la.kind == 'conv':
+                    continue
+                ca, cb = [planf.layers[i] for i in la.layers]
+                pa, pb = [plan8.layers[i] for i in la.layers]
+                key = '%s: %s | %s' % (la.kind, layer_key(pa), layer_key(pb))
+                if key in fl:
+                    continue
+                run = (lambda: planf.run_pair(ca, cb, stf)) if la.kind == 'pair' else (lambda: planf.run_block(ca, cb, stf))
+
+                def two():
+                    plan8.run_layer(pa, st8)
+                    plan8.run_layer(pb, st8)
+
+                (tf, sf), (t2, s2) = pair(run, two)
+                ops_ = layer_ops(pa) + layer_ops(pb)
+                fl[key] = dict(fused_us=round(1e3 * tf, 2), fused_spread_us=round(1e3 * sf, 2), two_launches_us=round(1e3 * t2, 2),
+                               two_launches_spread_us=round(1e3 * s2, 2), fused_TOPs=round(ops_ / (tf * 1e-3) / 1e12, 1),
+                               fused_over_two=round(tf / t2, 3))
+            r['fused_launches'] = fl
+            save()
+            del x, st8, stf, st16
             plan8._shape_cache.clear()
+            planf._shape_cache.clear()
             plan16._shape_cache.clear()
             m.__dict__.get('_step_graphs', {}).clear()
             torch.cuda.empty_cache()
-        del m, eng, plan8, plan16
+        del m, eng, engf, plan8, planf, plan16
         torch.cuda.empty_cache()
 print(json.dumps(res))
