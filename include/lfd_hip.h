@@ -679,6 +679,29 @@ LFD_API int lfd_conv2d_downsample_nhwc_i8(int32_t n, int32_t h, int32_t w, int32
                                           const float* ds_mult, const float* ds_biasq, void* out_i8, void* ds_out_i8,
                                           lfd_stream_t stream);
 
+/* One-launch 64-channel stage-entry block (csrc/entry_i8.hip; the fused='full' route of lfd_amd/engine_i8.py): the 3x3 stride-2
+ * conv1 (ReLU), the 1x1 stride-2 identity branch (no ReLU) and the 3x3 stride-1 conv2 that adds it (ReLU), all 64 -> 64 (padded)
+ * channels, with the operands of the lfd_conv2d_downsample_nhwc_i8 + lfd_conv2d_nhwc_i8 launches it replaces (the same fragment
+ * order: nothing is repacked) and equal to them in every bit for finite inputs (finite in and in_inv_scale, finite epilogue
+ * constants): a NaN, which those launches turn into 0, becomes -127 or 127 here; +/-inf saturates alike in both.
+ * oh = (h - 1) / 2 + 1, ow = (w - 1) / 2 + 1.
+ *   in_format 0: in int8 [n,h,w,64], xq = in; in_channels must be 64, in_inv_scale is ignored
+ *   in_format 1: in fp16 [n,h,w,in_channels], in_channels in {32, 48, 64}; xq = clamp(rint((float)x * in_inv_scale), -127, 127)
+ *                in channels < in_channels and 0 above: lfd_quantize_nhwc_f16_i8 / lfd_quantize_pad_nhwc_f16_i8 on the way in
+ *   y1  = q(max(fmaf((float)acc1, mult1[c], biasq1[c]), 0)), 3x3 stride 2 pad 1 over xq, int8, never written to memory
+ *   id  = q(fmaf((float)accd, ds_mult[c], ds_biasq[c])), 1x1 stride 2, int8, never written to memory
+ *   v   = max(fmaf((float)id, res_mult, fmaf((float)acc2, mult2[c], biasq2[c])), 0), acc2 the 3x3 stride-1 pad-1 sum over y1 with
+ *         0 outside the oh x ow map (conv2's padding, not conv1 evaluated there)
+ *   out_i8 [n,oh,ow,64] = q(v), q(.) = clamp(rint(.), -127, 127).  There is no fp16 tap output.
+ * LFD_ERR_INVALID_ARGUMENT: a NULL pointer, a pointer that is not 16-byte aligned, n / h / w < 1, out_i8 == in.
+ * LFD_ERR_UNSUPPORTED: another format or channel count (lfd_entry_i8_fused_supported answers without launching), or
+ * h * w * 128 >= 2^31.  A refused call launches and writes nothing. */
+LFD_API int lfd_entry_i8_fused(int32_t n, int32_t h, int32_t w, int32_t in_format, int32_t in_channels, const void* in,
+                               float in_inv_scale, const void* w1_packed, const float* mult1, const float* biasq1,
+                               const void* ds_w_packed, const float* ds_mult, const float* ds_biasq, const void* w2_packed,
+                               const float* mult2, const float* biasq2, float res_mult, void* out_i8, lfd_stream_t stream);
+LFD_API int lfd_entry_i8_fused_supported(int32_t in_format, int32_t in_channels);
+
 /* ------------------------------------------------------------------------------------------
  * INT8 calibration histogram (csrc/calib_hist.hip; lfd_amd/calibration.py): the counts from which the percentile,
  * entropy and MSE thresholds are computed on the host.  Stands where the reference hands its calibration batches to

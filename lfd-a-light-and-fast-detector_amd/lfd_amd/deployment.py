@@ -156,6 +156,11 @@ class Int8Engine(object):
         output are the same either way"""
         return self.plan.fused
 
+    @property
+    def route(self):
+        """'layers' | 'fused' | 'full': how the stages are launched (build_int8_engine's fused = False | True | 'full')"""
+        return self.plan.route
+
     def _check_fresh(self):
         m = self.model
         if engine._param_signature(m._backbone, m._neck, m._head) != self.plan.param_sig:
@@ -203,7 +208,10 @@ def build_int8_engine(model, int8_calibrator, fused=False):
     """LFD model (eval mode, on the device) + INT8Calibrator -> Int8Engine.  Uses the calibrator's cache when it was written
     for these weights and this layer list; otherwise runs the calibration batches and writes it.  fused=True: the stages run
     the fused int8 launches (stage-entry pair, whole 64-channel block) where the layer list has them; layers, scales, cache
-    and every output bit are those of the default layer-by-layer route, and a cache written by either serves the other."""
+    and every output bit are those of the default layer-by-layer route, and a cache written by either serves the other.
+    fused='full': additionally every 64-channel stage-entry block is one launch (csrc/entry_i8.hip), the first of them reading
+    the fp16 stem map so that the quantise launch is gone; the same bits again for a finite stem map.  fused takes the bools
+    False and True themselves and 'full'; any other value, 1, 0 and numpy.bool_ included, is a ValueError."""
     assert int8_calibrator is not None, 'calibrator is not provided!'
     engine_i8.check_model(model)
     if model.training:

@@ -7,7 +7,9 @@ branches included, one lfd_conv2d_nhwc_i8 launch each (layer by layer, the defau
 stores the un-requantised fp16 map the parent's head kernels read.  Int8Plan(..., fused=True) runs the same layer list through
 lower_fused(): a stage-entry block's two stride-2 convs as one lfd_conv2d_downsample_nhwc_i8 launch, a 64-channel block without
 a downsample as one lfd_block_i8_fused launch (csrc/block_i8.hip), the rest as before -- the same bits in every tensor the route
-still writes (the int8 map between a fused block's convs stays on chip and has no buffer).
+still writes (the int8 map between a fused block's convs stays on chip and has no buffer).  fused='full' additionally runs a
+whole 64-channel stage-entry block as one lfd_entry_i8_fused launch (csrc/entry_i8.hip); the first of them reads the fp16 stem
+map and quantises on the way in, so the quantise launch and the int8 copy of the stem map are gone as well.
 
 Numeric contract (symmetric, range [-127, 127], no zero points):
   weights      BN-folded fp32 (engine.fold_conv_norm, channels zero-padded to 64 / 128); per output channel
@@ -78,15 +80,19 @@ class ConvI8(object):
 
 
 # a launch of the fused route over indices into the layer list: 'conv' (i,) one lfd_conv2d_nhwc_i8; 'pair' (downsample, conv1) one
-# lfd_conv2d_downsample_nhwc_i8; 'block' (conv1, conv2) one lfd_block_i8_fused
+# lfd_conv2d_downsample_nhwc_i8; 'block' (conv1, conv2) one lfd_block_i8_fused; 'entry' (downsample, conv1, conv2) one
+# lfd_entry_i8_fused (the 'full' route only)
 Launch = collections.namedtuple('Launch', 'kind layers')
 PAIR_KEYS = ((64, 64), (64, 128), (128, 128))     # (cin, cout) of lfd_conv2d_downsample_nhwc_i8
+ROUTES = ('layers', 'fused', 'full')              # Int8Plan.route for fused = False, True, 'full'
 
 
-def lower_fused(layers):
+def lower_fused(layers, entry=False):
     """the plan's layer list -> the launch list of the fused route (a pure function of the layers' shapes and buffer ids).
     entry block (downsample 1x1 s2, conv1 3x3 s2 of the same input, conv2 adding the downsample): 'pair' + 'conv';
-    block of two 3x3 s1 convs of 64 (padded) channels whose second adds the first's input: 'block'; everything else: 'conv'."""
+    block of two 3x3 s1 convs of 64 (padded) channels whose second adds the first's input: 'block'; everything else: 'conv'.
+    entry=True (the 'full' route): an entry block of 64 -> 64 (padded) channels whose conv2 is no tap and whose two intermediate
+    maps nothing else reads is one 'entry' launch."""
     def reads(buf, but):
         return [j for j, c in enumerate(layers) if j not in but and (c.src == buf or c.res == buf)]
 
@@ -98,6 +104,11 @@ def lower_fused(layers):
         if b is not None and c is not None and (a.ks, a.stride, a.relu, a.res, a.tap) == (1, 2, False, None, None) \
                 and (b.ks, b.stride, b.relu, b.res, b.tap) == (3, 2, True, None, None) and b.src == a.src \
                 and (a.cin, a.cout) == (b.cin, b.cout) and (a.cin, a.cout) in PAIR_KEYS and c.src == b.dst and c.res == a.dst:
+            if entry and (a.cin, a.cout) == (64, 64) and (c.ks, c.stride, c.relu, c.tap) == (3, 1, True, None) \
+                    and c.cin == c.cout == 64 and not reads(a.dst, (i + 2,)) and not reads(b.dst, (i + 2,)):
+                out.append(Launch('entry', (i, i + 1, i + 2)))
+                i += 3
+                continue
             out.append(Launch('pair', (i, i + 1)))
             i += 2
             continue
@@ -141,8 +152,12 @@ class Int8Plan(engine.EnginePlan):
     def __init__(self, backbone, neck=None, head=None, device=None, fused=False):
         self.layers = []
         self.scales = None
-        self.fused = bool(fused)
-        self.launches = None                                  # the fused route's launch list (lower_fused), else None
+        if not any(fused is v for v in (False, True)) and fused != 'full':
+            raise ValueError("Int8Plan: fused must be False, True or 'full', not %r" % (fused,))
+        self.fused = fused                                    # truthy for both fused routes
+        self.route = ROUTES[2 if fused == 'full' else int(fused)]
+        self.launches = None                                  # the fused routes' launch list (lower_fused), else None
+        self.entry_f16 = None                                 # index of the 'entry' launch that reads the fp16 stem map
         super().__init__(backbone, neck, head, device)
         self.stem_channels_real = netdesc.backbone_layers(backbone).stem[-1].conv.out_channels
 
@@ -213,8 +228,18 @@ class Int8Plan(engine.EnginePlan):
                 self.tap_ready_after.append(len(self.convs) + len(self.layers))
         self.unwritten = frozenset()                          # int8 buffers no launch of this plan's route writes
         if self.fused:
-            self.launches = lower_fused(self.layers)
-            self.unwritten = frozenset(self.layers[la.layers[0]].dst for la in self.launches if la.kind == 'block')
+            self.launches = lower_fused(self.layers, entry=self.route == 'full')
+            gone = [self.layers[la.layers[0]].dst for la in self.launches if la.kind == 'block']
+            for k, la in enumerate(self.launches):
+                if la.kind != 'entry':
+                    continue
+                gone += [self.layers[i].dst for i in la.layers[:2]]       # the identity map and conv1's map stay on chip
+                # the entry launch behind the stem takes the fp16 stem map itself: no quantise launch, no int8 copy of it
+                if self.layers[la.layers[0]].src == 0 and ops.entry_i8_fused_supported(1, self.buf_channels[cur]) \
+                        and not [c for j, c in enumerate(self.layers) if j not in la.layers[:2] and 0 in (c.src, c.res)]:
+                    self.entry_f16 = k
+                    gone.append(0)
+            self.unwritten = frozenset(gone)
             done = dict((la.layers[-1], len(self.convs) + k + 1) for k, la in enumerate(self.launches))
             self.tap_ready_after = [done[i] for i, c in enumerate(self.layers) if c.tap is not None]
 
@@ -314,9 +339,11 @@ class Int8Plan(engine.EnginePlan):
 
     # ---- execution
     def run_stem(self, x, fmt, st):
-        """the parent's stem launches into the fp16 buffer, then the quantise launch"""
+        """the parent's stem launches into the fp16 buffer, then the quantise launch (unless the first 'entry' launch of the
+        'full' route reads the fp16 map itself)"""
         engine.EnginePlan.run_backbone(self, x, fmt, st)
-        self.run_quantise(st)
+        if self.entry_f16 is None:
+            self.run_quantise(st)
 
     def run_quantise(self, st):
         src = st.bufs[self.stage_in]
@@ -351,6 +378,15 @@ class Int8Plan(engine.EnginePlan):
                                        ptr(st.bufs[c2.tap]) if c2.tap is not None else None, c2.s_out, stream_ptr()),
               'lfd_block_i8_fused')
 
+    def run_entry(self, d, c1, c2, st, f16):
+        """a whole 64-channel stage-entry block (d: the identity branch, c1, c2 adding d) in one launch; f16: the input is the
+        fp16 stem map, quantised on the way in"""
+        src = st.bufs[self.stage_in] if f16 else st.qbufs[c1.src]
+        check(lib().lfd_entry_i8_fused(st.n, src.shape[1], src.shape[2], 1 if f16 else 0, src.shape[3], ptr(src),
+                                       self.inv_stem_scale if f16 else 0.0, ptr(c1.w), ptr(c1.mult), ptr(c1.biasq), ptr(d.w),
+                                       ptr(d.mult), ptr(d.biasq), ptr(c2.w), ptr(c2.mult), ptr(c2.biasq), c2.res_mult,
+                                       ptr(st.qbufs[c2.dst]), stream_ptr()), 'lfd_entry_i8_fused')
+
     def run_stages(self, st, after=None):
         base = len(self.convs)
         if self.fused:
@@ -362,6 +398,8 @@ class Int8Plan(engine.EnginePlan):
                     self.run_pair(cs[0], cs[1], st)
                 elif la.kind == 'block':
                     self.run_block(cs[0], cs[1], st)
+                elif la.kind == 'entry':
+                    self.run_entry(cs[0], cs[1], cs[2], st, k == self.entry_f16)
                 else:
                     self.run_layer(cs[0], st)
             if after and base + len(self.launches) in after:

@@ -979,6 +979,30 @@ def conv2d_downsample_nhwc_i8(x, w_packed, mult, biasq, ds_w_packed, ds_mult, ds
     return out, ds_out
 
 
+def entry_i8_fused_supported(in_format, in_channels):
+    """does lfd_entry_i8_fused take this input (0: int8, 1: the fp16 stem map with its real channel count)?  Nothing launched."""
+    return lib().lfd_entry_i8_fused_supported(in_format, in_channels) == 0
+
+
+def entry_i8_fused(x, w1_packed, mult1, biasq1, ds_w_packed, ds_mult, ds_biasq, w2_packed, mult2, biasq2, res_mult, inv_scale=0.0,
+                   out=None):
+    """x [N,H,W,64] int8, or [N,H,W,32|48|64] fp16 quantised with inv_scale on the way in -> [N,OH,OW,64] int8: a whole
+    64-channel stage-entry block in one launch (lfd_entry_i8_fused), with the operands of the conv2d_downsample_nhwc_i8 +
+    conv2d_nhwc_i8 calls (and the quantize_f16_i8 call) it equals bit for bit; the two intermediate maps stay on chip"""
+    require_cuda(x, 'entry_i8_fused')
+    if x.dtype not in (torch.int8, torch.float16) or not x.is_contiguous() or x.dim() != 4:
+        raise RuntimeError('entry_i8_fused: x must be contiguous int8 or fp16 NHWC')
+    n, h, w_, cin = x.shape
+    oh, ow = (h - 1) // 2 + 1, (w_ - 1) // 2 + 1
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty((n, oh, ow, 64), dtype=torch.int8, device=x.device)
+        check(lib().lfd_entry_i8_fused(n, h, w_, 0 if x.dtype == torch.int8 else 1, cin, ptr(x), float(inv_scale), ptr(w1_packed),
+                                       ptr(mult1), ptr(biasq1), ptr(ds_w_packed), ptr(ds_mult), ptr(ds_biasq), ptr(w2_packed),
+                                       ptr(mult2), ptr(biasq2), float(res_mult), ptr(out), stream_ptr()), 'lfd_entry_i8_fused')
+    return out
+
+
 def quantize_f16_i8(x, inv_scale, out=None, channels=None):
     """fp16 tensor -> int8 of the same shape: clamp(rint(float(x) * inv_scale), -127, 127) (lfd_quantize_nhwc_f16_i8).
     channels > x.shape[-1]: the last axis is widened to `channels` with zeros (lfd_quantize_pad_nhwc_f16_i8)."""

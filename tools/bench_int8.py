@@ -1,18 +1,23 @@
-"""The INT8 deployment mode (lfd_amd.deployment, csrc/conv_i8.hip, csrc/block_i8.hip), its fused route and its default layer-by-layer
-route, against the 'fp16' mode, frames resident in device memory (NHWC fp16, 1920 x 1080 unless --size=HxW):
+"""The INT8 deployment mode (lfd_amd.deployment, csrc/conv_i8.hip, csrc/block_i8.hip, csrc/entry_i8.hip), its 'full' route, its
+fused route and its default layer-by-layer route, against the 'fp16' mode, frames resident in device memory (NHWC fp16,
+1920 x 1080 unless --size=HxW):
 
     python tools/bench_int8.py [CONFIG ...] [--bs=8,1] [--size=1080x1920] [--out=FILE]
 
 per configuration (default WIDERFACE_LFD_S, WIDERFACE_LFD_XS, TT100K_LFD_L) and batch size:
-  * stages: the quantise launch + the int8 plan's stage launches (Int8Plan.run_stages), fused (build_int8_engine(...,
-    fused=True)) and layer by layer, against the fp16 plan's stage launches (EnginePlan._run_convs: fused blocks, downsample
-    pairs), eager launches on one stream;
-  * forward: Int8Engine.forward_resident of both routes against LFD.forward_resident in the 'fp16' mode, each as one graph replay;
-  * detect: forward + LFD.detect (decode, threshold, NMS on the device) behind each of the three forwards;
+  * stages: the quantise launch (where the route has one) + the int8 plan's stage launches (Int8Plan.run_stages), full
+    (build_int8_engine(..., fused='full')), fused (fused=True) and layer by layer, against the fp16 plan's stage launches
+    (EnginePlan._run_convs: fused blocks, downsample pairs), eager launches on one stream;
+  * forward: Int8Engine.forward_resident of the three routes against LFD.forward_resident in the 'fp16' mode, each as one graph
+    replay;
+  * detect: forward + LFD.detect (decode, threshold, NMS on the device) behind each of the four forwards;
   * layers: every distinct int8 launch of the layer-by-layer plan at that frame size on its own -- microseconds per call and
     TOP/s (2 * n * oh * ow * cout * cin * ks^2 integer operations of the padded layer over the call time);
   * fused_launches: every distinct lfd_block_i8_fused / lfd_conv2d_downsample_nhwc_i8 launch of the fused plan next to the two
-    layer-by-layer launches it replaces (their call times added), same units.
+    layer-by-layer launches it replaces (their call times added), same units;
+  * entry_launches: every distinct lfd_entry_i8_fused launch of the full plan in the int8 input format next to the pair + conv
+    launches of the fused route it replaces, and the one behind the stem also in the fp16 input format next to quantise + pair
+    + conv.
 The sides follow tools/bench_resnet.py: HIP events around `reps` back-to-back calls, alternating the sides, the median of
 `rounds` such windows divided by `reps` and max - min of the windows as the spread -- call times (kernel + launch), not profiler
 kernel times.  The calibration set is four seeded frames of a quarter of the size: scales do not change a launch's time.
@@ -71,15 +76,17 @@ def pair(*sides, reps=REPS):
     return [(float(np.median(t)), float(max(t) - min(t))) for t in ts]
 
 
-def three(got, nd=4):
-    """got: (fused int8, layer-by-layer int8, fp16) sides of pair()"""
+def four(got, nd=4):
+    """got: (full int8, fused int8, layer-by-layer int8, fp16) sides of pair()"""
     out = {}
-    for tag, (t, spread) in zip(('int8_fused', 'int8', 'fp16'), got):
+    for tag, (t, spread) in zip(('int8_full', 'int8_fused', 'int8', 'fp16'), got):
         out[tag] = round(t, nd)
         out[tag + '_spread'] = round(spread, nd)
-    out['int8_fused_over_fp16'] = round(got[0][0] / got[2][0], 3)
-    out['int8_over_fp16'] = round(got[1][0] / got[2][0], 3)
-    out['int8_fused_over_int8'] = round(got[0][0] / got[1][0], 3)
+    out['int8_full_over_fp16'] = round(got[0][0] / got[3][0], 3)
+    out['int8_fused_over_fp16'] = round(got[1][0] / got[3][0], 3)
+    out['int8_over_fp16'] = round(got[2][0] / got[3][0], 3)
+    out['int8_fused_over_int8'] = round(got[1][0] / got[2][0], 3)
+    out['int8_full_over_fused'] = round(got[0][0] / got[1][0], 3)
     return out
 
 
@@ -92,18 +99,22 @@ with torch.no_grad():
         cache = os.path.join(tempfile.mkdtemp(prefix='bench_int8_'), 'cal.json')
         eng = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2))
         engf = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2), fused=True)      # from the cache just written
-        assert not engf.calibrated
-        plan8, planf = eng.plan, engf.plan
+        engF = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2), fused='full')
+        assert not engf.calibrated and not engF.calibrated
+        plan8, planf, planF = eng.plan, engf.plan, engF.plan
         plan16 = engine.get_plan(m, m._backbone, m._neck, m._head, torch.device('cuda', torch.cuda.current_device()))
         ent = res['configs'][name] = dict(int8_launches=len(plan8.layers) + 1, int8_fused_launches=planf.int8_launches() + 1,
+                                        int8_full_launches=planF.int8_launches() + (planF.entry_f16 is None),
                                         fp16_stage_launches=len(plan16.convs))
         for bs in BATCHES:
             x = (torch.rand(bs, H, W, 3, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1)) * 2 - 1).half()
             meta = torch.tensor([[float(W), float(H), 1.0]] * bs, device='cuda')
             fmt = engine.IN_NHWC_F16
             st8, stf, st16 = plan8.state_for(bs, H, W), planf.state_for(bs, H, W), plan16.state_for(bs, H, W)
+            stF = planF.state_for(bs, H, W)
             plan8.run_all(x, fmt, st8)
             planf.run_all(x, fmt, stf)
+            planF.run_all(x, fmt, stF)
             plan16.run_all(x, fmt, st16)
             torch.cuda.synchronize()
             r = ent['bs%d' % bs] = {}
@@ -116,17 +127,25 @@ with torch.no_grad():
                 planf.run_quantise(stf)
                 planf.run_stages(stf)
 
+            def stagesF():
+                if planF.entry_f16 is None:
+                    planF.run_quantise(stF)
+                planF.run_stages(stF)
+
             assert torch.equal(stf.cls, st8.cls) and torch.equal(stf.reg, st8.reg), 'the fused route must equal the default bit for bit'
-            r['stages_ms'] = three(pair(stagesf, stages8, lambda: plan16._run_convs(st16), reps=5))
+            assert torch.equal(stF.cls, st8.cls) and torch.equal(stF.reg, st8.reg), 'the full route must equal the default bit for bit'
+            r['stages_ms'] = four(pair(stagesF, stagesf, stages8, lambda: plan16._run_convs(st16), reps=5))
             save()
-            eng.use_graph = engf.use_graph = m.use_graph = True
-            r['forward_ms'] = three(pair(lambda: engf.forward_resident(x), lambda: eng.forward_resident(x), lambda: m.forward_resident(x)))
+            eng.use_graph = engf.use_graph = engF.use_graph = m.use_graph = True
+            r['forward_ms'] = four(pair(lambda: engF.forward_resident(x), lambda: engf.forward_resident(x),
+                                        lambda: eng.forward_resident(x), lambda: m.forward_resident(x)))
             save()
             thr = float(np.quantile(st16.cls.sigmoid().float().cpu().numpy(), 0.999)) if st16.cls.shape[2] == 1 else 0.5
-            r['detect_ms'] = three(pair(lambda: engf.detect(x, meta, score_thr=thr), lambda: eng.detect(x, meta, score_thr=thr),
-                                        lambda: m.detect(m.forward_resident(x), meta, score_thr=thr)))
-            eng.use_graph = engf.use_graph = m.use_graph = False
+            r['detect_ms'] = four(pair(lambda: engF.detect(x, meta, score_thr=thr), lambda: engf.detect(x, meta, score_thr=thr),
+                                       lambda: eng.detect(x, meta, score_thr=thr),
+                                       lambda: m.detect(m.forward_resident(x), meta, score_thr=thr)))
             save()
+            eng.use_graph = engf.use_graph = engF.use_graph = m.use_graph = False
             # ---- every distinct int8 launch on its own
             layers = {}
 
@@ -169,12 +188,43 @@ with torch.no_grad():
                                fused_over_two=round(tf / t2, 3))
             r['fused_launches'] = fl
             save()
-            del x, st8, stf, st16
+            # ---- every distinct entry launch against the launches of the fused route it replaces (the fused plan's buffers)
+            el = {}
+            for k, la in enumerate(planF.launches):
+                if la.kind != 'entry':
+                    continue
+                cd, c1, c2 = [planf.layers[i] for i in la.layers]
+                key = 'entry: %s | %s' % (layer_key(c1), layer_key(c2))
+                if key in el and k != planF.entry_f16:
+                    continue
+
+                def pair_conv():
+                    planf.run_pair(cd, c1, stf)
+                    planf.run_layer(c2, stf)
+
+                def quantise_pair_conv():
+                    planf.run_quantise(stf)
+                    pair_conv()
+
+                ops_ = layer_ops(cd) + layer_ops(c1) + layer_ops(c2)
+                (te, se), (tp, sp_) = pair(lambda: planf.run_entry(cd, c1, c2, stf, False), pair_conv)
+                e = el[key] = dict(entry_us=round(1e3 * te, 2), entry_spread_us=round(1e3 * se, 2), pair_conv_us=round(1e3 * tp, 2),
+                                   pair_conv_spread_us=round(1e3 * sp_, 2), entry_TOPs=round(ops_ / (te * 1e-3) / 1e12, 1),
+                                   entry_over_pair_conv=round(te / tp, 3))
+                if k == planF.entry_f16:
+                    (te, se), (tq, sq) = pair(lambda: planf.run_entry(cd, c1, c2, stf, True), quantise_pair_conv)
+                    e.update(entry_f16_us=round(1e3 * te, 2), entry_f16_spread_us=round(1e3 * se, 2),
+                             quantise_pair_conv_us=round(1e3 * tq, 2), quantise_pair_conv_spread_us=round(1e3 * sq, 2),
+                             entry_f16_over_quantise_pair_conv=round(te / tq, 3))
+            r['entry_launches'] = el
+            save()
+            del x, st8, stf, stF, st16
             plan8._shape_cache.clear()
             planf._shape_cache.clear()
+            planF._shape_cache.clear()
             plan16._shape_cache.clear()
             m.__dict__.get('_step_graphs', {}).clear()
             torch.cuda.empty_cache()
-        del m, eng, engf, plan8, planf, plan16
+        del m, eng, engf, engF, plan8, planf, planF, plan16
         torch.cuda.empty_cache()
 print(json.dumps(res))
