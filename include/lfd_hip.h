@@ -673,6 +673,15 @@ LFD_API int lfd_quantize_pad_nhwc_f16_i8(const void* in, void* out, int64_t pixe
 LFD_API int lfd_block_i8_fused(int32_t n, int32_t h, int32_t w, const void* in, const void* w1_packed, const float* mult1,
                                const float* biasq1, const void* w2_packed, const float* mult2, const float* biasq2,
                                float res_mult, void* out_i8, void* out_f16, float out_scale, lfd_stream_t stream);
+/* lfd_block128_i8_fused (csrc/block128_i8.hip; the block128 option of lfd_amd/engine_i8.py): the 128-channel sibling of
+ * lfd_block_i8_fused with the same signature and the same contract, 128 for 64: in, out_i8 and out_f16 are [n,h,w,128], the
+ * operands are those of the two 128 -> 128 lfd_conv2d_nhwc_i8 calls in the same fragment order, mid is int8, never written to
+ * memory and 0 outside the image, out_i8 = q(v), out_f16 = half(v * out_scale) with v in float64 (NULL: not written).  The
+ * requantisation is lfd_conv2d_nhwc_i8's own compare / select form, so the launch equals the two it replaces in every bit,
+ * NaN constants included.  Status codes as for lfd_block_i8_fused; a refused call launches and writes nothing. */
+LFD_API int lfd_block128_i8_fused(int32_t n, int32_t h, int32_t w, const void* in, const void* w1_packed, const float* mult1,
+                                  const float* biasq1, const void* w2_packed, const float* mult2, const float* biasq2,
+                                  float res_mult, void* out_i8, void* out_f16, float out_scale, lfd_stream_t stream);
 LFD_API int lfd_conv2d_downsample_nhwc_i8_supported(int32_t cin, int32_t cout);
 LFD_API int lfd_conv2d_downsample_nhwc_i8(int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, const void* in,
                                           const void* w_packed, const float* mult, const float* biasq, const void* ds_w_packed,

@@ -450,6 +450,7 @@ _SIGNATURES = {
     'lfd_quantize_nhwc_f16_i8': (C.c_int, [_P, _P, _I64, C.c_float, _P]),
     'lfd_quantize_pad_nhwc_f16_i8': (C.c_int, [_P, _P, _I64, _I32, _I32, C.c_float, _P]),
     'lfd_block_i8_fused': (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, C.c_float, _P]),
+    'lfd_block128_i8_fused': (C.c_int, [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P, C.c_float, _P]),
     'lfd_conv2d_downsample_nhwc_i8_supported': (C.c_int, [_I32, _I32]),
     'lfd_conv2d_downsample_nhwc_i8': (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'lfd_entry_i8_fused': (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P,

@@ -161,6 +161,12 @@ class Int8Engine(object):
         """'layers' | 'fused' | 'full': how the stages are launched (build_int8_engine's fused = False | True | 'full')"""
         return self.plan.route
 
+    @property
+    def block128(self):
+        """whether the 128-channel residual blocks run as one launch each (csrc/block128_i8.hip; build_int8_engine(...,
+        block128=True)); the bits of every output are the same either way"""
+        return self.plan.block128
+
     def _check_fresh(self):
         m = self.model
         if engine._param_signature(m._backbone, m._neck, m._head) != self.plan.param_sig:
@@ -204,14 +210,16 @@ class Int8Engine(object):
         return self.model.get_results(predict_outputs, *args)
 
 
-def build_int8_engine(model, int8_calibrator, fused=False):
+def build_int8_engine(model, int8_calibrator, fused=False, block128=False):
     """LFD model (eval mode, on the device) + INT8Calibrator -> Int8Engine.  Uses the calibrator's cache when it was written
     for these weights and this layer list; otherwise runs the calibration batches and writes it.  fused=True: the stages run
     the fused int8 launches (stage-entry pair, whole 64-channel block) where the layer list has them; layers, scales, cache
     and every output bit are those of the default layer-by-layer route, and a cache written by either serves the other.
     fused='full': additionally every 64-channel stage-entry block is one launch (csrc/entry_i8.hip), the first of them reading
     the fp16 stem map so that the quantise launch is gone; the same bits again for a finite stem map.  fused takes the bools
-    False and True themselves and 'full'; any other value, 1, 0 and numpy.bool_ included, is a ValueError."""
+    False and True themselves and 'full'; any other value, 1, 0 and numpy.bool_ included, is a ValueError.
+    block128=True (with fused=True or 'full'; a ValueError with fused=False): additionally every 128-channel residual block
+    without a downsample is one launch (csrc/block128_i8.hip), pyramid taps included; the same bits and the same cache."""
     assert int8_calibrator is not None, 'calibrator is not provided!'
     engine_i8.check_model(model)
     if model.training:
@@ -220,7 +228,7 @@ def build_int8_engine(model, int8_calibrator, fused=False):
     if device.type != 'cuda':
         raise RuntimeError('build_int8_engine: the model must be on the MI355X (got %s)' % device)
     with torch.no_grad():
-        plan = engine_i8.Int8Plan(model._backbone, model._neck, model._head, device, fused=fused)
+        plan = engine_i8.Int8Plan(model._backbone, model._neck, model._head, device, fused=fused, block128=block128)
     sha = state_sha256(model.state_dict())
     blob = int8_calibrator.read_calibration_cache()
     seen = [0]

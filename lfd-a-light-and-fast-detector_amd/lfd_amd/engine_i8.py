@@ -9,7 +9,9 @@ lower_fused(): a stage-entry block's two stride-2 convs as one lfd_conv2d_downsa
 a downsample as one lfd_block_i8_fused launch (csrc/block_i8.hip), the rest as before -- the same bits in every tensor the route
 still writes (the int8 map between a fused block's convs stays on chip and has no buffer).  fused='full' additionally runs a
 whole 64-channel stage-entry block as one lfd_entry_i8_fused launch (csrc/entry_i8.hip); the first of them reads the fp16 stem
-map and quantises on the way in, so the quantise launch and the int8 copy of the stem map are gone as well.
+map and quantises on the way in, so the quantise launch and the int8 copy of the stem map are gone as well.  block128=True (with
+either fused route) runs every 128-channel block without a downsample as one lfd_block128_i8_fused launch
+(csrc/block128_i8.hip), the same bits again.
 
 Numeric contract (symmetric, range [-127, 127], no zero points):
   weights      BN-folded fp32 (engine.fold_conv_norm, channels zero-padded to 64 / 128); per output channel
@@ -81,18 +83,20 @@ class ConvI8(object):
 
 # a launch of the fused route over indices into the layer list: 'conv' (i,) one lfd_conv2d_nhwc_i8; 'pair' (downsample, conv1) one
 # lfd_conv2d_downsample_nhwc_i8; 'block' (conv1, conv2) one lfd_block_i8_fused; 'entry' (downsample, conv1, conv2) one
-# lfd_entry_i8_fused (the 'full' route only)
+# lfd_entry_i8_fused (the 'full' route only); 'block128' (conv1, conv2) one lfd_block128_i8_fused (the block128 option only)
 Launch = collections.namedtuple('Launch', 'kind layers')
 PAIR_KEYS = ((64, 64), (64, 128), (128, 128))     # (cin, cout) of lfd_conv2d_downsample_nhwc_i8
 ROUTES = ('layers', 'fused', 'full')              # Int8Plan.route for fused = False, True, 'full'
 
 
-def lower_fused(layers, entry=False):
+def lower_fused(layers, entry=False, block128=False):
     """the plan's layer list -> the launch list of the fused route (a pure function of the layers' shapes and buffer ids).
     entry block (downsample 1x1 s2, conv1 3x3 s2 of the same input, conv2 adding the downsample): 'pair' + 'conv';
     block of two 3x3 s1 convs of 64 (padded) channels whose second adds the first's input: 'block'; everything else: 'conv'.
     entry=True (the 'full' route): an entry block of 64 -> 64 (padded) channels whose conv2 is no tap and whose two intermediate
-    maps nothing else reads is one 'entry' launch."""
+    maps nothing else reads is one 'entry' launch.
+    block128=True: a block of two 3x3 s1 convs of 128 (padded) channels under the conditions of 'block' (conv2 may be a tap) is
+    one 'block128' launch; with block128=False it stays two 'conv' launches."""
     def reads(buf, but):
         return [j for j, c in enumerate(layers) if j not in but and (c.src == buf or c.res == buf)]
 
@@ -113,9 +117,10 @@ def lower_fused(layers, entry=False):
             i += 2
             continue
         if b is not None and (a.ks, a.stride, a.relu, a.res, a.tap) == (3, 1, True, None, None) \
-                and (b.ks, b.stride, b.relu) == (3, 1, True) and a.cin == a.cout == b.cin == b.cout == 64 \
+                and (b.ks, b.stride, b.relu) == (3, 1, True) and a.cin == a.cout == b.cin == b.cout \
+                and a.cin in ((64, 128) if block128 else (64,)) \
                 and b.src == a.dst and b.res == a.src and not reads(a.dst, (i + 1,)):
-            out.append(Launch('block', (i, i + 1)))
+            out.append(Launch('block' if a.cin == 64 else 'block128', (i, i + 1)))
             i += 2
             continue
         out.append(Launch('conv', (i,)))
@@ -149,11 +154,17 @@ class Int8Plan(engine.EnginePlan):
     calibrate() measures the amax of every named tensor in fp16 (calibrate_histograms(): its magnitude histogram, for the
     clipping rules of lfd_amd/calibration.py), set_scales() turns one value per tensor into the launches' constants."""
 
-    def __init__(self, backbone, neck=None, head=None, device=None, fused=False):
+    def __init__(self, backbone, neck=None, head=None, device=None, fused=False, block128=False):
         self.layers = []
         self.scales = None
         if not any(fused is v for v in (False, True)) and fused != 'full':
             raise ValueError("Int8Plan: fused must be False, True or 'full', not %r" % (fused,))
+        if not any(block128 is v for v in (False, True)):
+            raise ValueError('Int8Plan: block128 must be False or True, not %r' % (block128,))
+        if block128 and fused is False:
+            raise ValueError("Int8Plan: block128=True needs fused=True or fused='full': the layer-by-layer route has no fused "
+                             'launches')
+        self.block128 = block128                              # 128-channel blocks as one lfd_block128_i8_fused launch each
         self.fused = fused                                    # truthy for both fused routes
         self.route = ROUTES[2 if fused == 'full' else int(fused)]
         self.launches = None                                  # the fused routes' launch list (lower_fused), else None
@@ -228,8 +239,8 @@ class Int8Plan(engine.EnginePlan):
                 self.tap_ready_after.append(len(self.convs) + len(self.layers))
         self.unwritten = frozenset()                          # int8 buffers no launch of this plan's route writes
         if self.fused:
-            self.launches = lower_fused(self.layers, entry=self.route == 'full')
-            gone = [self.layers[la.layers[0]].dst for la in self.launches if la.kind == 'block']
+            self.launches = lower_fused(self.layers, entry=self.route == 'full', block128=self.block128)
+            gone = [self.layers[la.layers[0]].dst for la in self.launches if la.kind in ('block', 'block128')]
             for k, la in enumerate(self.launches):
                 if la.kind != 'entry':
                     continue
@@ -378,6 +389,14 @@ class Int8Plan(engine.EnginePlan):
                                        ptr(st.bufs[c2.tap]) if c2.tap is not None else None, c2.s_out, stream_ptr()),
               'lfd_block_i8_fused')
 
+    def run_block128(self, c1, c2, st):
+        """a whole 128-channel residual block (c1 -> c2 + the block's input) in one launch, the tap on it if the block is one"""
+        src = st.qbufs[c1.src]
+        check(lib().lfd_block128_i8_fused(st.n, src.shape[1], src.shape[2], ptr(src), ptr(c1.w), ptr(c1.mult), ptr(c1.biasq),
+                                          ptr(c2.w), ptr(c2.mult), ptr(c2.biasq), c2.res_mult, ptr(st.qbufs[c2.dst]),
+                                          ptr(st.bufs[c2.tap]) if c2.tap is not None else None, c2.s_out, stream_ptr()),
+              'lfd_block128_i8_fused')
+
     def run_entry(self, d, c1, c2, st, f16):
         """a whole 64-channel stage-entry block (d: the identity branch, c1, c2 adding d) in one launch; f16: the input is the
         fp16 stem map, quantised on the way in"""
@@ -398,6 +417,8 @@ class Int8Plan(engine.EnginePlan):
                     self.run_pair(cs[0], cs[1], st)
                 elif la.kind == 'block':
                     self.run_block(cs[0], cs[1], st)
+                elif la.kind == 'block128':
+                    self.run_block128(cs[0], cs[1], st)
                 elif la.kind == 'entry':
                     self.run_entry(cs[0], cs[1], cs[2], st, k == self.entry_f16)
                 else:

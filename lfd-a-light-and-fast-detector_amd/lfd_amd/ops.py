@@ -954,6 +954,26 @@ def block_i8_fused(x, w1_packed, mult1, biasq1, w2_packed, mult2, biasq2, res_mu
     return out, out_f16
 
 
+def block128_i8_fused(x, w1_packed, mult1, biasq1, w2_packed, mult2, biasq2, res_mult, out_scale=None, out=None, out_f16=None):
+    """x [N,H,W,128] int8 -> (q_out [N,H,W,128] int8, fp16 map | None): a whole 128-channel residual block in one launch
+    (lfd_block128_i8_fused, csrc/block128_i8.hip), ReLU(conv2(ReLU(conv1(x))) + x) with the operands of the two conv2d_nhwc_i8
+    calls it equals bit for bit; the int8 map between the convs stays on chip.  out_scale not None: the fp16 pyramid tap is
+    stored as well."""
+    require_cuda(x, 'block128_i8_fused')
+    if x.dtype != torch.int8 or not x.is_contiguous() or x.dim() != 4 or x.shape[3] != 128:
+        raise RuntimeError('block128_i8_fused: x must be contiguous int8 NHWC with 128 channels')
+    n, h, w_, _ = x.shape
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = torch.empty((n, h, w_, 128), dtype=torch.int8, device=x.device)
+        if out_scale is not None and out_f16 is None:
+            out_f16 = torch.empty((n, h, w_, 128), dtype=torch.float16, device=x.device)
+        check(lib().lfd_block128_i8_fused(n, h, w_, ptr(x), ptr(w1_packed), ptr(mult1), ptr(biasq1), ptr(w2_packed), ptr(mult2),
+                                          ptr(biasq2), float(res_mult), ptr(out), ptr(out_f16),
+                                          float(out_scale if out_scale is not None else 0.0), stream_ptr()), 'lfd_block128_i8_fused')
+    return out, out_f16
+
+
 def conv2d_downsample_i8_supported(cin, cout):
     """does lfd_conv2d_downsample_nhwc_i8 have a kernel for this stage entry (channels as the plan pads them)?  Nothing
     launched."""

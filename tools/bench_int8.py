@@ -1,23 +1,25 @@
-"""The INT8 deployment mode (lfd_amd.deployment, csrc/conv_i8.hip, csrc/block_i8.hip, csrc/entry_i8.hip), its 'full' route, its
-fused route and its default layer-by-layer route, against the 'fp16' mode, frames resident in device memory (NHWC fp16,
+"""The INT8 deployment mode (lfd_amd.deployment, csrc/conv_i8.hip, csrc/block_i8.hip, csrc/entry_i8.hip, csrc/block128_i8.hip), its
+'full' route with and without the block128 option, its fused route and its default layer-by-layer route, against the 'fp16' mode, frames resident in device memory (NHWC fp16,
 1920 x 1080 unless --size=HxW):
 
     python tools/bench_int8.py [CONFIG ...] [--bs=8,1] [--size=1080x1920] [--out=FILE]
 
 per configuration (default WIDERFACE_LFD_S, WIDERFACE_LFD_XS, TT100K_LFD_L) and batch size:
-  * stages: the quantise launch (where the route has one) + the int8 plan's stage launches (Int8Plan.run_stages), full
-    (build_int8_engine(..., fused='full')), fused (fused=True) and layer by layer, against the fp16 plan's stage launches
+  * stages: the quantise launch (where the route has one) + the int8 plan's stage launches (Int8Plan.run_stages), full + block128
+    (build_int8_engine(..., fused='full', block128=True)), full (fused='full'), fused (fused=True) and layer by layer, against the fp16 plan's stage launches
     (EnginePlan._run_convs: fused blocks, downsample pairs), eager launches on one stream;
-  * forward: Int8Engine.forward_resident of the three routes against LFD.forward_resident in the 'fp16' mode, each as one graph
+  * forward: Int8Engine.forward_resident of the four int8 sides against LFD.forward_resident in the 'fp16' mode, each as one graph
     replay;
-  * detect: forward + LFD.detect (decode, threshold, NMS on the device) behind each of the four forwards;
+  * detect: forward + LFD.detect (decode, threshold, NMS on the device) behind each of the five forwards;
   * layers: every distinct int8 launch of the layer-by-layer plan at that frame size on its own -- microseconds per call and
     TOP/s (2 * n * oh * ow * cout * cin * ks^2 integer operations of the padded layer over the call time);
   * fused_launches: every distinct lfd_block_i8_fused / lfd_conv2d_downsample_nhwc_i8 launch of the fused plan next to the two
     layer-by-layer launches it replaces (their call times added), same units;
   * entry_launches: every distinct lfd_entry_i8_fused launch of the full plan in the int8 input format next to the pair + conv
     launches of the fused route it replaces, and the one behind the stem also in the fp16 input format next to quantise + pair
-    + conv.
+    + conv;
+  * block128_launches: every distinct lfd_block128_i8_fused launch of the full + block128 plan next to the two lfd_conv2d_nhwc_i8
+    launches it replaces, each with and without the fp16 tap, same protocol and units.
 The sides follow tools/bench_resnet.py: HIP events around `reps` back-to-back calls, alternating the sides, the median of
 `rounds` such windows divided by `reps` and max - min of the windows as the spread -- call times (kernel + launch), not profiler
 kernel times.  The calibration set is four seeded frames of a quarter of the size: scales do not change a launch's time.
@@ -33,7 +35,7 @@ for p in (ROOT, os.path.join(ROOT, 'lfd-a-light-and-fast-detector_amd')):
     sys.path.insert(0, p)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from lfd_amd import INT8Calibrator, build_int8_engine, configs, engine  # noqa: E402
+from lfd_amd import INT8Calibrator, build_int8_engine, configs, engine, ops  # noqa: E402
 
 
 def opt(name, default):
@@ -77,9 +79,9 @@ def pair(*sides, reps=REPS):
 
 
 def four(got, nd=4):
-    """got: (full int8, fused int8, layer-by-layer int8, fp16) sides of pair()"""
+    """got: (full int8, fused int8, layer-by-layer int8, fp16, full + block128 int8) sides of pair()"""
     out = {}
-    for tag, (t, spread) in zip(('int8_full', 'int8_fused', 'int8', 'fp16'), got):
+    for tag, (t, spread) in zip(('int8_full', 'int8_fused', 'int8', 'fp16', 'int8_full_b128'), got):
         out[tag] = round(t, nd)
         out[tag + '_spread'] = round(spread, nd)
     out['int8_full_over_fp16'] = round(got[0][0] / got[3][0], 3)
@@ -87,6 +89,10 @@ def four(got, nd=4):
     out['int8_over_fp16'] = round(got[2][0] / got[3][0], 3)
     out['int8_fused_over_int8'] = round(got[1][0] / got[2][0], 3)
     out['int8_full_over_fused'] = round(got[0][0] / got[1][0], 3)
+    out['int8_full_b128_over_fp16'] = round(got[4][0] / got[3][0], 3)
+    out['int8_full_b128_over_full'] = round(got[4][0] / got[0][0], 3)
+    # does full + block128 differ from full by more than both spreads?
+    out['b128_differs_from_full'] = bool(abs(got[4][0] - got[0][0]) > max(got[4][1], got[0][1]))
     return out
 
 
@@ -100,21 +106,24 @@ with torch.no_grad():
         eng = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2))
         engf = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2), fused=True)      # from the cache just written
         engF = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2), fused='full')
-        assert not engf.calibrated and not engF.calibrated
-        plan8, planf, planF = eng.plan, engf.plan, engF.plan
+        engB = build_int8_engine(m, INT8Calibrator(frames, cache, batch_size=2), fused='full', block128=True)
+        assert not engf.calibrated and not engF.calibrated and not engB.calibrated
+        plan8, planf, planF, planB = eng.plan, engf.plan, engF.plan, engB.plan
         plan16 = engine.get_plan(m, m._backbone, m._neck, m._head, torch.device('cuda', torch.cuda.current_device()))
         ent = res['configs'][name] = dict(int8_launches=len(plan8.layers) + 1, int8_fused_launches=planf.int8_launches() + 1,
                                         int8_full_launches=planF.int8_launches() + (planF.entry_f16 is None),
+                                        int8_full_b128_launches=planB.int8_launches() + (planB.entry_f16 is None),
                                         fp16_stage_launches=len(plan16.convs))
         for bs in BATCHES:
             x = (torch.rand(bs, H, W, 3, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1)) * 2 - 1).half()
             meta = torch.tensor([[float(W), float(H), 1.0]] * bs, device='cuda')
             fmt = engine.IN_NHWC_F16
             st8, stf, st16 = plan8.state_for(bs, H, W), planf.state_for(bs, H, W), plan16.state_for(bs, H, W)
-            stF = planF.state_for(bs, H, W)
+            stF, stB = planF.state_for(bs, H, W), planB.state_for(bs, H, W)
             plan8.run_all(x, fmt, st8)
             planf.run_all(x, fmt, stf)
             planF.run_all(x, fmt, stF)
+            planB.run_all(x, fmt, stB)
             plan16.run_all(x, fmt, st16)
             torch.cuda.synchronize()
             r = ent['bs%d' % bs] = {}
@@ -132,20 +141,28 @@ with torch.no_grad():
                     planF.run_quantise(stF)
                 planF.run_stages(stF)
 
+            def stagesB():
+                if planB.entry_f16 is None:
+                    planB.run_quantise(stB)
+                planB.run_stages(stB)
+
+            assert torch.equal(stB.cls, st8.cls) and torch.equal(stB.reg, st8.reg), 'block128 must equal the default bit for bit'
             assert torch.equal(stf.cls, st8.cls) and torch.equal(stf.reg, st8.reg), 'the fused route must equal the default bit for bit'
             assert torch.equal(stF.cls, st8.cls) and torch.equal(stF.reg, st8.reg), 'the full route must equal the default bit for bit'
-            r['stages_ms'] = four(pair(stagesF, stagesf, stages8, lambda: plan16._run_convs(st16), reps=5))
+            r['stages_ms'] = four(pair(stagesF, stagesf, stages8, lambda: plan16._run_convs(st16), stagesB, reps=5))
             save()
-            eng.use_graph = engf.use_graph = engF.use_graph = m.use_graph = True
+            eng.use_graph = engf.use_graph = engF.use_graph = engB.use_graph = m.use_graph = True
             r['forward_ms'] = four(pair(lambda: engF.forward_resident(x), lambda: engf.forward_resident(x),
-                                        lambda: eng.forward_resident(x), lambda: m.forward_resident(x)))
+                                        lambda: eng.forward_resident(x), lambda: m.forward_resident(x),
+                                        lambda: engB.forward_resident(x)))
             save()
             thr = float(np.quantile(st16.cls.sigmoid().float().cpu().numpy(), 0.999)) if st16.cls.shape[2] == 1 else 0.5
             r['detect_ms'] = four(pair(lambda: engF.detect(x, meta, score_thr=thr), lambda: engf.detect(x, meta, score_thr=thr),
                                        lambda: eng.detect(x, meta, score_thr=thr),
-                                       lambda: m.detect(m.forward_resident(x), meta, score_thr=thr)))
+                                       lambda: m.detect(m.forward_resident(x), meta, score_thr=thr),
+                                       lambda: engB.detect(x, meta, score_thr=thr)))
             save()
-            eng.use_graph = engf.use_graph = engF.use_graph = m.use_graph = False
+            eng.use_graph = engf.use_graph = engF.use_graph = engB.use_graph = m.use_graph = False
             # ---- every distinct int8 launch on its own
             layers = {}
 
@@ -218,13 +235,45 @@ with torch.no_grad():
                              entry_f16_over_quantise_pair_conv=round(te / tq, 3))
             r['entry_launches'] = el
             save()
-            del x, st8, stf, stF, st16
+            # ---- every distinct block128 launch against the two lfd_conv2d_nhwc_i8 launches it replaces, with and without the tap
+            bl = {}
+            for la in planB.launches:
+                if la.kind != 'block128':
+                    continue
+                c1, c2 = [plan8.layers[i] for i in la.layers]
+                src, mid, dst = st8.qbufs[c1.src], st8.qbufs[c1.dst], st8.qbufs[c2.dst]
+                shape_key = 'block128: %dx%d' % (src.shape[1], src.shape[2])
+                if shape_key + ' +tap' in bl:
+                    continue
+                tapbuf = st8.bufs[c2.tap] if c2.tap is not None else torch.empty(dst.shape, dtype=torch.float16, device='cuda')
+                ops_ = layer_ops(c1) + layer_ops(c2)
+                for tap in (True, False):
+                    sc, tb = (c2.s_out, tapbuf) if tap else (None, None)
+
+                    def one():
+                        ops.block128_i8_fused(src, c1.w, c1.mult, c1.biasq, c2.w, c2.mult, c2.biasq, c2.res_mult, out_scale=sc,
+                                              out=dst, out_f16=tb)
+
+                    def two():
+                        ops.conv2d_nhwc_i8(src, c1.w, c1.mult, c1.biasq, 128, 3, 1, True, out=mid)
+                        ops.conv2d_nhwc_i8(mid, c2.w, c2.mult, c2.biasq, 128, 3, 1, True, residual=src, res_mult=c2.res_mult,
+                                           out_scale=sc, out=dst, out_f16=tb)
+
+                    (tf, sf), (t2, s2) = pair(one, two)
+                    bl[shape_key + (' +tap' if tap else '')] = dict(
+                        block128_us=round(1e3 * tf, 2), block128_spread_us=round(1e3 * sf, 2), two_launches_us=round(1e3 * t2, 2),
+                        two_launches_spread_us=round(1e3 * s2, 2), block128_TOPs=round(ops_ / (tf * 1e-3) / 1e12, 1),
+                        block128_over_two=round(tf / t2, 3), in_plan=(c2.tap is not None) == tap)
+            r['block128_launches'] = bl
+            save()
+            del x, st8, stf, stF, stB, st16
             plan8._shape_cache.clear()
             planf._shape_cache.clear()
             planF._shape_cache.clear()
+            planB._shape_cache.clear()
             plan16._shape_cache.clear()
             m.__dict__.get('_step_graphs', {}).clear()
             torch.cuda.empty_cache()
-        del m, eng, engf, engF, plan8, planf, planF, plan16
+        del m, eng, engf, engF, engB, plan8, planf, planF, planB, plan16
         torch.cuda.empty_cache()
 print(json.dumps(res))
