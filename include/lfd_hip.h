@@ -972,6 +972,21 @@ LFD_API int lfd_stem_conv_f16(const void* in, int32_t in_format, int32_t n, int3
                               int32_t channels, const void* w1_packed, const float* b1,
                               const void* w2_packed, const float* b2, void* out, lfd_stream_t stream);
 
+/* The same unit writing the int8 map the INT8 mode's stages read (the stem_int8 option of lfd_amd/engine_i8.py): for
+ * every output element, with y the fp16 value lfd_stem_conv_f16 stores (after bias and ReLU),
+ *   out = clamp(rint((float)y * inv_scale), -127, 127), int8 NHWC [n, (h+1)/2, (w+1)/2, 64],
+ * rint half to even, (float)y * inv_scale one fp32 multiply: lfd_quantize_nhwc_f16_i8's expression, evaluated on the fp16
+ * value.  Equal in every bit to lfd_stem_conv_f16 followed by lfd_quantize_nhwc_f16_i8 for finite y and finite inv_scale; a
+ * NaN becomes 0, as it does there.  The fp16 map is not written.
+ * All three in_formats; channels == 64 and the chained 1x1 (w2_packed != NULL) only: everything else is LFD_ERR_UNSUPPORTED
+ * (lfd_stem_conv_i8_supported(in_format, channels, has_tail) answers without launching).  out, w1_packed, b1, w2_packed, b2:
+ * 16-byte aligned.  LFD_ERR_INVALID_ARGUMENT: a NULL in / w1_packed / b1 / out, w2_packed given without b2 or the reverse, a
+ * misaligned pointer, n / h / w < 1 -- checked on the host before any launch.  A refused call launches and writes nothing. */
+LFD_API int lfd_stem_conv_i8(const void* in, int32_t in_format, int32_t n, int32_t h, int32_t w, int32_t channels,
+                             const void* w1_packed, const float* b1, const void* w2_packed, const float* b2, float inv_scale,
+                             void* out, lfd_stream_t stream);
+LFD_API int lfd_stem_conv_i8_supported(int32_t in_format, int32_t channels, int32_t has_tail);
+
 /* First layer of the torchvision-style ResNet: conv7x7 stride 2 pad 3 (3 -> 64) + BatchNorm (folded on the host) + ReLU on a
  * frame (resnet.py:366-370, :470-473; csrc/stem7.hip).  in_format as lfd_stem_conv_f16 (uint8: simple_normalize on the load).
  * w_packed: [2 = co / 32][10 k-steps][64 lanes][8] fp16, lane (hk, co % 32) slot j of k-step s = tap slot k = 16 s + 8 hk + j:
@@ -1012,6 +1027,22 @@ LFD_API int lfd_stem_faster_fused_f16(const void* in, int32_t in_format, int32_t
                                       const void* w2_packed, const float* b2, const void* w3_packed,
                                       const float* b3, const void* w4_packed, const float* b4, void* out,
                                       lfd_stream_t stream);
+
+/* The one-launch 'faster' stem writing the int8 map (k_stem2x only; the stem_int8 option): with y the fp16 value
+ * lfd_stem_faster_fused_f16 stores for the same operands with the knob LFD_TUNE_STEM2X at its default of 1,
+ *   out = clamp(rint((float)y * inv_scale), -127, 127), int8 NHWC [n, ceil(ceil(h/2)/2), ceil(ceil(w/2)/2), 64],
+ * equal in every bit to that launch followed by lfd_quantize_nhwc_f16_i8 for finite y and finite inv_scale; a NaN becomes 0,
+ * as it does there.  The fp16 map is not written.  LFD_TUNE_X2_ALN and LFD_TUNE_X2_STAGGER act as in the fp16 entry point;
+ * LFD_TUNE_STEM2X does not (there is no int8 form of the older kernel).
+ * in_format 1 (NHWC fp16) and 2 (NHWC uint8), channels == 64: everything else -- NCHW fp32 frames, 32-channel stems -- is
+ * LFD_ERR_UNSUPPORTED (lfd_stem_faster_fused_i8_supported(in_format, channels) answers without launching).  out, the four
+ * filters and the four biases: 16-byte aligned.  LFD_ERR_INVALID_ARGUMENT: a NULL pointer, a misaligned pointer, n / h / w < 1
+ * -- checked on the host before any launch.  A refused call launches and writes nothing. */
+LFD_API int lfd_stem_faster_fused_i8(const void* in, int32_t in_format, int32_t n, int32_t h, int32_t w, int32_t channels,
+                                     const void* w1_packed, const float* b1, const void* w2_packed, const float* b2,
+                                     const void* w3_packed, const float* b3, const void* w4_packed, const float* b4,
+                                     float inv_scale, void* out, lfd_stream_t stream);
+LFD_API int lfd_stem_faster_fused_i8_supported(int32_t in_format, int32_t channels);
 
 /* ------------------------------------------------------------------------------------------
  * Training-mode conv stack.  The reference trains through PyTorch autograd over

@@ -250,18 +250,9 @@ __global__ __launch_bounds__(256) void k_quantize_f16_i8(const _Float16* __restr
   const long nvec = count >> 4;
   const long step = (long)gridDim.x * 256;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += step) {
-    union { uint4 u[2]; _Float16 h[16]; } x;
-    x.u[0] = *reinterpret_cast<const uint4*>(in + i * 16);
-    x.u[1] = *reinterpret_cast<const uint4*>(in + i * 16 + 8);
-    union { uint4 u; int8_t b[16]; } o;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      float r = __builtin_rintf((float)x.h[g] * inv_scale);
-      r = r > 127.f ? 127.f : r;
-      r = r < -127.f ? -127.f : r;
-      o.b[g] = (int8_t)(int)r;
-    }
-    *reinterpret_cast<uint4*>(out + i * 16) = o.u;
+    const uint4 lo = *reinterpret_cast<const uint4*>(in + i * 16);
+    const uint4 hi = *reinterpret_cast<const uint4*>(in + i * 16 + 8);
+    *reinterpret_cast<uint4*>(out + i * 16) = lfd_quant16_f16_i8(lo, hi, inv_scale);
   }
   const long tail = (nvec << 4) + (long)blockIdx.x * 256 + threadIdx.x;     // (count & 15 <= 15 elements: block 0 covers them)
   if (tail < count) {
@@ -284,19 +275,9 @@ __global__ __launch_bounds__(256) void k_quantize_pad_f16_i8(const _Float16* __r
     const int c0 = (int)(i - pix * per) << 4;
     const bool real = c0 < cin;
     const _Float16* src = in + (real ? pix * cin + c0 : 0);
-    union { uint4 u[2]; _Float16 h[16]; } x;
-    x.u[0] = *reinterpret_cast<const uint4*>(src);
-    x.u[1] = *reinterpret_cast<const uint4*>(src + 8);
-    union { uint4 u; int8_t b[16]; } o;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      float r = __builtin_rintf((float)x.h[g] * inv_scale);
-      r = r > 127.f ? 127.f : r;
-      r = r < -127.f ? -127.f : r;
-      o.b[g] = (int8_t)(int)r;
-    }
-    if (!real) o.u = make_uint4(0u, 0u, 0u, 0u);
-    *reinterpret_cast<uint4*>(out + pix * cout + c0) = o.u;
+    uint4 q = lfd_quant16_f16_i8(*reinterpret_cast<const uint4*>(src), *reinterpret_cast<const uint4*>(src + 8), inv_scale);
+    if (!real) q = make_uint4(0u, 0u, 0u, 0u);
+    *reinterpret_cast<uint4*>(out + pix * cout + c0) = q;
   }
 }
 

@@ -29,6 +29,7 @@ struct StemArgs {
   const float* b2;     // [C]
   int N, H, W, OH, OW;
   int tiles_x, tiles_y;
+  float inv_scale;     // OI8: out = clamp(rint((float)y * inv_scale), -127, 127)
 };
 
 template <int FMT>
@@ -44,9 +45,13 @@ __device__ __forceinline__ _Float16 load_px(const void* in, int n, int H, int W,
 }
 
 // NCT = C/32 (1 or 2).  4 waves: ct = wave % NCT, pg = wave / NCT; each wave: 2 x 32 px x 32 ch.
-template <int NCT, int FMT, bool TAIL>
+// OI8: the output format.  false: a.out is the fp16 map.  true: a.out is an int8 map of the same shape and every fp16 value is
+// quantised with a.inv_scale on its way out of the LDS staging tile; the fp16 map is not written.  Everything the int8 form
+// adds stands under `if constexpr (OI8)`.
+template <int NCT, int FMT, bool TAIL, bool OI8>
 __global__ __launch_bounds__(256) void k_stem(StemArgs a) {
   constexpr int C = NCT * 32;
+  static_assert(!OI8 || (C == 64 && TAIL), "int8 output: 64 channels with the 1x1 tail only");
   constexpr int PG = 4 / NCT, PT = 2, TW = 32, TH = PG * PT;
   constexpr int IH = 2 * TH + 1, IW = 2 * TW + 1;
   constexpr int RS = ((IW * 3 + 1) / 2) * 2;           // halfs per LDS input row (even)
@@ -204,19 +209,36 @@ __global__ __launch_bounds__(256) void k_stem(StemArgs a) {
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < TH * TW * MCPP; i += 256) {
-    const int pb = i / MCPP, c = i - pb * MCPP;
-    const int oy = ty0 * TH + pb / TW, ox = tx0 * TW + (pb % TW);
-    if (oy < a.OH && ox < a.OW) {
-      const int fm = (pb / MPPR) % MCPP;
-      const uint4 v = *reinterpret_cast<const uint4*>(s_out + pb * MPIXB + ((c ^ fm) * 16));
-      *reinterpret_cast<uint4*>(a.out + (((size_t)n * a.OH + oy) * a.OW + ox) * C + c * 8) = v;
+  if constexpr (OI8) {
+    // a lane takes two neighbouring fp16 chunks (16 channels) of a pixel and stores one 16-byte int8 chunk: 4 consecutive lanes
+    // write one whole 64-byte pixel line, 8 lanes a 128-byte line
+    constexpr int QCPP = C / 16;
+    int8_t* out8 = reinterpret_cast<int8_t*>(a.out);
+    for (int i = threadIdx.x; i < TH * TW * QCPP; i += 256) {
+      const int pb = i / QCPP, c = i - pb * QCPP;
+      const int oy = ty0 * TH + pb / TW, ox = tx0 * TW + (pb % TW);
+      if (oy < a.OH && ox < a.OW) {
+        const int fm = (pb / MPPR) % MCPP;
+        const uint4 lo = *reinterpret_cast<const uint4*>(s_out + pb * MPIXB + (((2 * c) ^ fm) * 16));
+        const uint4 hi = *reinterpret_cast<const uint4*>(s_out + pb * MPIXB + (((2 * c + 1) ^ fm) * 16));
+        *reinterpret_cast<uint4*>(out8 + (((size_t)n * a.OH + oy) * a.OW + ox) * C + c * 16) = lfd_quant16_f16_i8(lo, hi, a.inv_scale);
+      }
+    }
+  } else {
+    for (int i = threadIdx.x; i < TH * TW * MCPP; i += 256) {
+      const int pb = i / MCPP, c = i - pb * MCPP;
+      const int oy = ty0 * TH + pb / TW, ox = tx0 * TW + (pb % TW);
+      if (oy < a.OH && ox < a.OW) {
+        const int fm = (pb / MPPR) % MCPP;
+        const uint4 v = *reinterpret_cast<const uint4*>(s_out + pb * MPIXB + ((c ^ fm) * 16));
+        *reinterpret_cast<uint4*>(a.out + (((size_t)n * a.OH + oy) * a.OW + ox) * C + c * 8) = v;
+      }
     }
   }
   }  // persistent tile loop
 }
 
-template <int NCT, int FMT, bool TAIL>
+template <int NCT, int FMT, bool TAIL, bool OI8 = false>
 int launch_stem(StemArgs a, hipStream_t st) {
   constexpr int PG = 4 / NCT, TH = PG * 2, TW = 32;
   a.tiles_x = (a.OW + TW - 1) / TW;
@@ -224,7 +246,7 @@ int launch_stem(StemArgs a, hipStream_t st) {
   const long long ntiles = (long long)a.N * a.tiles_x * a.tiles_y;
   if (ntiles > 0x7fffffffLL) return LFD_ERR_UNSUPPORTED;
   const unsigned blocks = ntiles < 2048 ? (unsigned)ntiles : 2048u;   // 8 resident workgroups per CU
-  hipLaunchKernelGGL((k_stem<NCT, FMT, TAIL>), dim3(blocks), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((k_stem<NCT, FMT, TAIL, OI8>), dim3(blocks), dim3(256), 0, st, a);
   LFD_CHECK_LAUNCH();
   return LFD_OK;
 }
@@ -257,6 +279,33 @@ int lfd_stem_conv_f16(const void* in, int32_t in_format, int32_t n, int32_t h, i
   if (tail && !b2) return LFD_ERR_INVALID_ARGUMENT;
   if (channels == 64) return tail ? dispatch_fmt<2, true>(in_format, a, st) : dispatch_fmt<2, false>(in_format, a, st);
   return tail ? dispatch_fmt<1, true>(in_format, a, st) : dispatch_fmt<1, false>(in_format, a, st);
+}
+
+int lfd_stem_conv_i8_supported(int32_t in_format, int32_t channels, int32_t has_tail) {
+  if (in_format != IN_NCHW_F32 && in_format != IN_NHWC_F16 && in_format != IN_NHWC_U8) return LFD_ERR_UNSUPPORTED;
+  return (channels == 64 && has_tail) ? LFD_OK : LFD_ERR_UNSUPPORTED;
+}
+
+int lfd_stem_conv_i8(const void* in, int32_t in_format, int32_t n, int32_t h, int32_t w, int32_t channels,
+                     const void* w1_packed, const float* b1, const void* w2_packed, const float* b2, float inv_scale,
+                     void* out, lfd_stream_t stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!in || !w1_packed || !b1 || !out || n < 1 || h < 1 || w < 1) return LFD_ERR_INVALID_ARGUMENT;
+  if ((w2_packed != nullptr) != (b2 != nullptr)) return LFD_ERR_INVALID_ARGUMENT;
+  if (!lfd_aligned16(out) || !lfd_aligned16(w1_packed) || !lfd_aligned16(b1) || !lfd_aligned16(w2_packed) || !lfd_aligned16(b2))
+    return LFD_ERR_INVALID_ARGUMENT;
+  const int rc = lfd_stem_conv_i8_supported(in_format, channels, w2_packed != nullptr);
+  if (rc != LFD_OK) return rc;
+  StemArgs a{};
+  a.in = in; a.out = (_Float16*)out; a.w1 = (const half8*)w1_packed; a.b1 = b1;
+  a.w2 = (const half8*)w2_packed; a.b2 = b2;
+  a.N = n; a.H = h; a.W = w; a.OH = (h + 2 - 3) / 2 + 1; a.OW = (w + 2 - 3) / 2 + 1;
+  a.inv_scale = inv_scale;
+  switch (in_format) {
+    case IN_NCHW_F32: return launch_stem<2, IN_NCHW_F32, true, true>(a, st);
+    case IN_NHWC_F16: return launch_stem<2, IN_NHWC_F16, true, true>(a, st);
+    default: return launch_stem<2, IN_NHWC_U8, true, true>(a, st);
+  }
 }
 
 }  // extern "C"

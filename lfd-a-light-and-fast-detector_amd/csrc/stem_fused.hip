@@ -41,6 +41,7 @@ struct FusedArgs {
   int H2, W2;            // after pair 2 (output)
   int tiles_x, tiles_y, ntiles;
   int stagger;           // 1: de-phase the workgroups at start (k_stem2x)
+  float inv_scale;       // k_stem2x with int8 output: out = clamp(rint((float)y * inv_scale), -127, 127)
 };
 
 template <int FMT>
@@ -407,7 +408,10 @@ __device__ __forceinline__ half8 relu8(const f32x16& acc, int half) {
 // so the realignment shift, the LDS read offsets and the global addresses of a tile's chunks are compile-time / per-thread
 // constants instead of ~90 instructions per chunk -- with one wave per SIMD nothing hides them (fetch + store of the raw
 // tile were 2.4 k of the 14.3 k cycles of a tile).
-template <bool U8, bool ALN>
+// OI8: the output format.  false: a.out is the fp16 map.  true: a.out is an int8 map of the same shape; the last stage of a tile
+// quantises the wave's row with a.inv_scale on its way out of the staging tile and the fp16 map is not written.  Everything the
+// int8 form adds stands under `if constexpr (OI8)`.
+template <bool U8, bool ALN, bool OI8>
 __global__ __launch_bounds__(256, 1) void k_stem2x(FusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* s_raw = smem;
@@ -1032,7 +1036,23 @@ __global__ __launch_bounds__(256, 1) void k_stem2x(FusedArgs a) {
     X2_T(9);
 #endif
     // ---- this wave's output row leaves as whole 128-byte lines
-    {
+    if constexpr (OI8) {
+      // int8: the row is 32 pixels x 64 bytes = 2 KB.  Instruction jc: pixels 16jc..16jc+15, lane = (pixel, 16 channels): two
+      // neighbouring fp16 chunks 2c, 2c + 1 out of the staging tile (pixel p's chunk c8 sits at c8 ^ ((p >> 1) & 7), and
+      // (p >> 1) & 7 = (lane >> 3) & 7 for both jc) -> one 16-byte int8 chunk; 4 lanes write a pixel, 8 lanes a 128-byte line
+      const int oy = g_out.ty0 * X2::TH + wave;
+      char* ob = reinterpret_cast<char*>(a.out) + (((long)g_out.n * a.H2 + oy) * a.W2 + (long)g_out.tx0 * X2::TW) * 64 + lane * 16;
+      const int ox0 = g_out.tx0 * X2::TW + (lane >> 2);
+      const int key = (lane >> 3) & 7;
+      const int l0 = (lane >> 2) * 128 + (((2 * (lane & 3)) ^ key) * 16), l1 = (lane >> 2) * 128 + (((2 * (lane & 3) + 1) ^ key) * 16);
+#pragma unroll
+      for (int jc = 0; jc < 2; ++jc) {
+        const uint4 lo = *reinterpret_cast<const uint4*>(wst + jc * 2048 + l0);
+        const uint4 hi = *reinterpret_cast<const uint4*>(wst + jc * 2048 + l1);
+        const uint4 q = lfd_quant16_f16_i8(lo, hi, a.inv_scale);
+        if (oy < a.H2 && ox0 + jc * 16 < a.W2) *reinterpret_cast<uint4*>(ob + jc * 1024) = q;
+      }
+    } else {
       // instruction jc: pixels 8jc..8jc+7 x 8 chunks = 1 KB contiguous in the output row -> scalar row base
       // + lane * 16 + jc * 1024; LDS side: pixel p's chunk c8 sits at ((c8 ^ (p >> 1)) & 7) -- (p >> 1) & 7 =
       // 4 * (jc & 1) + (lane >> 4), two lane constants
@@ -1060,7 +1080,7 @@ extern "C" __attribute__((visibility("default"))) int lfd_debug_x2_timing(unsign
 namespace {
 #endif
 
-template <bool U8, bool ALN>
+template <bool U8, bool ALN, bool OI8 = false>
 int launch_stem2x(FusedArgs a, hipStream_t st) {
   a.tiles_x = (a.W2 + X2::TW - 1) / X2::TW;
   a.tiles_y = (a.H2 + X2::TH - 1) / X2::TH;
@@ -1070,7 +1090,7 @@ int launch_stem2x(FusedArgs a, hipStream_t st) {
   static unsigned long long done_mask = 0;
   const int done_dev = lfd_device_ordinal();
   if (LFD_ONCE_PER_DEVICE(done_mask, done_dev)) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_stem2x<U8, ALN>), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_stem2x<U8, ALN, OI8>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             X2::LDS_BYTES) != hipSuccess)
       return LFD_ERR_LAUNCH_FAILED;
     LFD_DONE_ON_DEVICE(done_mask, done_dev);
@@ -1080,7 +1100,7 @@ int launch_stem2x(FusedArgs a, hipStream_t st) {
   // (round 1's kernel gained 3 % from de-phasing the workgroups' memory bursts with a start delay of up to one tile time; with
   //  the round-2 staging -- one basic block of loads per tile -- the delay only costs: 178 vs 172 us at 8 x 1080p.  Opt-in.)
   a.stagger = lfd_tune(LFD_TUNE_X2_STAGGER) && a.ntiles >= 16 * blocks;
-  hipLaunchKernelGGL((k_stem2x<U8, ALN>), dim3(blocks), dim3(256), X2::LDS_BYTES, st, a);
+  hipLaunchKernelGGL((k_stem2x<U8, ALN, OI8>), dim3(blocks), dim3(256), X2::LDS_BYTES, st, a);
   LFD_CHECK_LAUNCH();
   return LFD_OK;
 }
@@ -1151,6 +1171,40 @@ int lfd_stem_faster_fused_f16(const void* in, int32_t in_format, int32_t n, int3
   }
   if (use_x2 && channels == 64 && in_format == IN_NHWC_U8) return aln ? launch_stem2x<true, true>(a, st) : launch_stem2x<true, false>(a, st);
   return channels == 64 ? dispatch_fmt<2>(in_format, a, st) : dispatch_fmt<1>(in_format, a, st);
+}
+
+int lfd_stem_faster_fused_i8_supported(int32_t in_format, int32_t channels) {
+  return ((in_format == IN_NHWC_F16 || in_format == IN_NHWC_U8) && channels == 64) ? LFD_OK : LFD_ERR_UNSUPPORTED;
+}
+
+int lfd_stem_faster_fused_i8(const void* in, int32_t in_format, int32_t n, int32_t h, int32_t w, int32_t channels,
+                             const void* w1_packed, const float* b1, const void* w2_packed, const float* b2,
+                             const void* w3_packed, const float* b3, const void* w4_packed, const float* b4,
+                             float inv_scale, void* out, lfd_stream_t stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!in || !out || !w1_packed || !b1 || !w2_packed || !b2 || !w3_packed || !b3 || !w4_packed || !b4)
+    return LFD_ERR_INVALID_ARGUMENT;
+  if (n < 1 || h < 1 || w < 1) return LFD_ERR_INVALID_ARGUMENT;
+  if (!lfd_aligned16(out) || !lfd_aligned16(w1_packed) || !lfd_aligned16(b1) || !lfd_aligned16(w2_packed) || !lfd_aligned16(b2) ||
+      !lfd_aligned16(w3_packed) || !lfd_aligned16(b3) || !lfd_aligned16(w4_packed) || !lfd_aligned16(b4))
+    return LFD_ERR_INVALID_ARGUMENT;
+  const int rc = lfd_stem_faster_fused_i8_supported(in_format, channels);
+  if (rc != LFD_OK) return rc;
+  FusedArgs a{};
+  a.in = in; a.out = (_Float16*)out;
+  a.w1 = (const half8*)w1_packed; a.b1 = b1; a.w2 = (const half8*)w2_packed; a.b2 = b2;
+  a.w3 = (const half8*)w3_packed; a.b3 = b3; a.w4 = (const half8*)w4_packed; a.b4 = b4;
+  a.N = n; a.H = h; a.W = w;
+  a.H1 = (h - 1) / 2 + 1; a.W1 = (w - 1) / 2 + 1;
+  a.H2 = (a.H1 - 1) / 2 + 1; a.W2 = (a.W1 - 1) / 2 + 1;
+  a.inv_scale = inv_scale;
+  // the kernel choice of lfd_stem_faster_fused_f16 for these formats (always k_stem2x: LFD_TUNE_STEM2X does not act here)
+  const bool aln = lfd_tune(LFD_TUNE_X2_ALN) && (w % 8) == 0;
+  if (in_format == IN_NHWC_F16) {
+    if (aln && (reinterpret_cast<uintptr_t>(in) & 15) == 0) return launch_stem2x<false, true, true>(a, st);
+    return launch_stem2x<false, false, true>(a, st);
+  }
+  return aln ? launch_stem2x<true, true, true>(a, st) : launch_stem2x<true, false, true>(a, st);
 }
 
 }  // extern "C"

@@ -456,6 +456,10 @@ _SIGNATURES = {
     'lfd_entry_i8_fused': (C.c_int, [_I32, _I32, _I32, _I32, _I32, _P, C.c_float, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P,
                                      _P]),
     'lfd_entry_i8_fused_supported': (C.c_int, [_I32, _I32]),
+    'lfd_stem_conv_i8': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, C.c_float, _P, _P]),
+    'lfd_stem_conv_i8_supported': (C.c_int, [_I32, _I32, _I32]),
+    'lfd_stem_faster_fused_i8': (C.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, C.c_float, _P, _P]),
+    'lfd_stem_faster_fused_i8_supported': (C.c_int, [_I32, _I32]),
     'lfd_abs_histogram_f16': (C.c_int, [_P, _I64, _I32, _I32, _P, _P]),
     'lfd_p32_conv_packed_weight_halfs': (_SZ, [_I32, _I32, _I32]),
     'lfd_p32_conv2d_nhwc_f32': (C.c_int, [C.POINTER(P32ConvDesc), _P, _P, _P, _P, _P, _P, _P]),

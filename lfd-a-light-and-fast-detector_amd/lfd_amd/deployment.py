@@ -167,6 +167,12 @@ class Int8Engine(object):
         block128=True)); the bits of every output are the same either way"""
         return self.plan.block128
 
+    @property
+    def stem_int8(self):
+        """whether the stem launch writes the int8 map itself where it can (build_int8_engine(..., stem_int8=True)); per call
+        it does for the frame formats in plan.stem_int8_formats, and the bits of every output are the same either way"""
+        return self.plan.stem_int8
+
     def _check_fresh(self):
         m = self.model
         if engine._param_signature(m._backbone, m._neck, m._head) != self.plan.param_sig:
@@ -210,7 +216,7 @@ class Int8Engine(object):
         return self.model.get_results(predict_outputs, *args)
 
 
-def build_int8_engine(model, int8_calibrator, fused=False, block128=False):
+def build_int8_engine(model, int8_calibrator, fused=False, block128=False, stem_int8=False):
     """LFD model (eval mode, on the device) + INT8Calibrator -> Int8Engine.  Uses the calibrator's cache when it was written
     for these weights and this layer list; otherwise runs the calibration batches and writes it.  fused=True: the stages run
     the fused int8 launches (stage-entry pair, whole 64-channel block) where the layer list has them; layers, scales, cache
@@ -219,7 +225,13 @@ def build_int8_engine(model, int8_calibrator, fused=False, block128=False):
     the fp16 stem map so that the quantise launch is gone; the same bits again for a finite stem map.  fused takes the bools
     False and True themselves and 'full'; any other value, 1, 0 and numpy.bool_ included, is a ValueError.
     block128=True (with fused=True or 'full'; a ValueError with fused=False): additionally every 128-channel residual block
-    without a downsample is one launch (csrc/block128_i8.hip), pyramid taps included; the same bits and the same cache."""
+    without a downsample is one launch (csrc/block128_i8.hip), pyramid taps included; the same bits and the same cache.
+    stem_int8=True (with every value of fused; the bools themselves, anything else is a ValueError): the stem launch writes the
+    int8 map the stages read (lfd_stem_conv_i8 for a 'fast' stem, every frame format; lfd_stem_faster_fused_i8 for a 'faster'
+    stem, NHWC fp16 / uint8 frames), so the fp16 stem map and the quantise launch -- under 'full' the fp16 read of the first
+    entry launch -- are gone; stems of 64 stored channels (48 real ones included) of RGB models only, plan.stem_int8_formats
+    lists the frame formats, and a call in any other format runs the launches it runs without the option.  The same bits for
+    a finite stem map, the same scales and the same cache."""
     assert int8_calibrator is not None, 'calibrator is not provided!'
     engine_i8.check_model(model)
     if model.training:
@@ -228,7 +240,8 @@ def build_int8_engine(model, int8_calibrator, fused=False, block128=False):
     if device.type != 'cuda':
         raise RuntimeError('build_int8_engine: the model must be on the MI355X (got %s)' % device)
     with torch.no_grad():
-        plan = engine_i8.Int8Plan(model._backbone, model._neck, model._head, device, fused=fused, block128=block128)
+        plan = engine_i8.Int8Plan(model._backbone, model._neck, model._head, device, fused=fused, block128=block128,
+                                    stem_int8=stem_int8)
     sha = state_sha256(model.state_dict())
     blob = int8_calibrator.read_calibration_cache()
     seen = [0]

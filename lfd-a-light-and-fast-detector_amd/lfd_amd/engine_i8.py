@@ -11,7 +11,9 @@ still writes (the int8 map between a fused block's convs stays on chip and has n
 whole 64-channel stage-entry block as one lfd_entry_i8_fused launch (csrc/entry_i8.hip); the first of them reads the fp16 stem
 map and quantises on the way in, so the quantise launch and the int8 copy of the stem map are gone as well.  block128=True (with
 either fused route) runs every 128-channel block without a downsample as one lfd_block128_i8_fused launch
-(csrc/block128_i8.hip), the same bits again.
+(csrc/block128_i8.hip), the same bits again.  stem_int8=True (with every route) lets the stem launch write the int8 map itself
+(lfd_stem_conv_i8 / lfd_stem_faster_fused_i8) for the frame formats in Int8Plan.stem_int8_formats: no fp16 stem map, no quantise
+launch, and the first 'entry' launch reads int8 -- the same bits once more.
 
 Numeric contract (symmetric, range [-127, 127], no zero points):
   weights      BN-folded fp32 (engine.fold_conv_norm, channels zero-padded to 64 / 128); per output channel
@@ -154,17 +156,22 @@ class Int8Plan(engine.EnginePlan):
     calibrate() measures the amax of every named tensor in fp16 (calibrate_histograms(): its magnitude histogram, for the
     clipping rules of lfd_amd/calibration.py), set_scales() turns one value per tensor into the launches' constants."""
 
-    def __init__(self, backbone, neck=None, head=None, device=None, fused=False, block128=False):
+    def __init__(self, backbone, neck=None, head=None, device=None, fused=False, block128=False, stem_int8=False):
         self.layers = []
         self.scales = None
         if not any(fused is v for v in (False, True)) and fused != 'full':
             raise ValueError("Int8Plan: fused must be False, True or 'full', not %r" % (fused,))
         if not any(block128 is v for v in (False, True)):
             raise ValueError('Int8Plan: block128 must be False or True, not %r' % (block128,))
+        if not any(stem_int8 is v for v in (False, True)):
+            raise ValueError('Int8Plan: stem_int8 must be False or True, not %r' % (stem_int8,))
         if block128 and fused is False:
             raise ValueError("Int8Plan: block128=True needs fused=True or fused='full': the layer-by-layer route has no fused "
                              'launches')
         self.block128 = block128                              # 128-channel blocks as one lfd_block128_i8_fused launch each
+        self.stem_int8 = stem_int8                            # the stem launch writes int8 buffer 0 where it can
+        self.stem_int8_formats = frozenset()                  # in_format values for which it does (filled by _build_stages)
+        self.front = None                                     # log of the launches in front of the stages (run_stem), not state
         self.fused = fused                                    # truthy for both fused routes
         self.route = ROUTES[2 if fused == 'full' else int(fused)]
         self.launches = None                                  # the fused routes' launch list (lower_fused), else None
@@ -181,6 +188,7 @@ class Int8Plan(engine.EnginePlan):
         self.qbuf_channels = {0: c_in}
         self.qbuf_scale = {0: self.buf_scale[cur]}
         self.tensor_names = [STEM]
+        self.stem_int8_formats = self._stem_int8_formats(cur) if self.stem_int8 else frozenset()
 
         def add(src, src_name, lay, name, relu, res=None, res_name=None, tap=False):
             c = ConvI8()
@@ -250,12 +258,32 @@ class Int8Plan(engine.EnginePlan):
                         and not [c for j, c in enumerate(self.layers) if j not in la.layers[:2] and 0 in (c.src, c.res)]:
                     self.entry_f16 = k
                     gone.append(0)
+            if self.stem_int8_formats:                        # the stem launch writes int8 buffer 0 for those formats
+                gone = [b for b in gone if b != 0]
             self.unwritten = frozenset(gone)
             done = dict((la.layers[-1], len(self.convs) + k + 1) for k, la in enumerate(self.launches))
             self.tap_ready_after = [done[i] for i, c in enumerate(self.layers) if c.tap is not None]
 
+    def _stem_int8_formats(self, cur):
+        """frame formats (in_format of lfd_stem_conv_f16) for which the launch that writes the stem map `cur` has an int8-output
+        form: a pure function of the model.  RGB stems whose last launch is the 'fast' unit (64 stored channels -- a 48-channel
+        stem runs zero-padded to 64 and its padded channels quantise to 0 -- with the 1x1 tail) or the one-launch 'faster' stem
+        (NHWC fp16 / uint8 frames; NCHW fp32 frames run its two-kernel form).  Gray models and 32-channel stems: none."""
+        if self.input_channels != 3 or self.buf_channels[cur] != self.qbuf_channels[0]:
+            return frozenset()
+        c0 = self.stem_first[0]
+        if self.stem_fused is not None:
+            if self.stem_fused[-1] != cur or self.convs:
+                return frozenset()
+            return frozenset(f for f in (1, 2) if ops.stem_faster_fused_i8_supported(f, c0))
+        if self.convs or cur != self.stem_out:                # further stem launches behind the first unit
+            return frozenset()
+        return frozenset(f for f in (0, 1, 2) if ops.stem_conv_i8_supported(f, c0, self.stem_first[3] is not None))
+
     def int8_launches(self):
-        """int8 launches of the stages per forward (the quantise launch not counted)"""
+        """int8 launches of the stages per forward.  Not counted: the launches in front of them -- the stem's and the quantise
+        launch, which is gone under fused='full' and, with stem_int8=True, for every frame format in stem_int8_formats (the
+        launch list and this count do not depend on stem_int8)"""
         return len(self.launches) if self.fused else len(self.layers)
 
     # ---- calibration (offline: fp16 kernels where they exist, torch otherwise)
@@ -337,6 +365,10 @@ class Int8Plan(engine.EnginePlan):
         st = super().state_for(n, h, w, slot)
         if not hasattr(st, 'qbufs'):
             st.qbufs = {}
+            if self.stem_int8_formats and slot != 'calibrate':
+                # the fp16 stem map (the largest tensor of the network) is only needed by a call in another frame format:
+                # stem_f16() allocates it on first use
+                del st.bufs[self.stage_in]
             with torch.cuda.device(self.device):
                 for b, sc in self.qbuf_scale.items():
                     if b in self.unwritten:                   # the map between a fused block's convs stays on chip
@@ -349,15 +381,49 @@ class Int8Plan(engine.EnginePlan):
         return st
 
     # ---- execution
+    def stem_f16(self, st):
+        """the fp16 stem map of this shape and slot (dropped by state_for under stem_int8: allocated on first use)"""
+        if self.stage_in not in st.bufs:
+            hh, ww = st.dims[self.stage_in]
+            with torch.cuda.device(self.device):
+                st.bufs[self.stage_in] = torch.empty((st.n, hh, ww, self.buf_channels[self.stage_in]), dtype=torch.float16,
+                                                     device=self.device)
+        return st.bufs[self.stage_in]
+
     def run_stem(self, x, fmt, st):
-        """the parent's stem launches into the fp16 buffer, then the quantise launch (unless the first 'entry' launch of the
-        'full' route reads the fp16 map itself)"""
+        """fmt in stem_int8_formats: the stem launch writes int8 buffer 0 itself (lfd_stem_conv_i8 / lfd_stem_faster_fused_i8
+        with inv_stem_scale), nothing else.  Otherwise the parent's stem launches into the fp16 buffer, then the quantise launch
+        (unless the first 'entry' launch of the 'full' route reads the fp16 map itself).  -> whether the stem wrote int8 buffer 0
+        itself; run_backbone hands that to run_stages.  self.front and st.front are a log of what was launched, nothing reads them
+        to decide a launch: {'stem': entry point, 'quantise': whether the quantise launch ran, 'entry_in_format': in_format of
+        the first 'entry' launch behind the stem under 'full' (filled by run_stages), else None}.  They are written when Python
+        runs these methods -- eagerly and while a graph is captured -- and NOT by a graph replay: after a replay they still show
+        the last eager or captured call."""
+        st.front = self.front = dict(stem=None, quantise=False, entry_in_format=None)
+        if fmt in self.stem_int8_formats:
+            l, sp = lib(), stream_ptr()
+            if self.stem_fused is not None:
+                c0, w1, b1, w2, b2, w3, b3, w4, b4, _dst = self.stem_fused
+                st.front['stem'] = 'lfd_stem_faster_fused_i8'
+                check(l.lfd_stem_faster_fused_i8(ptr(x), fmt, st.n, st.h, st.w, c0, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3),
+                                                 ptr(b3), ptr(w4), ptr(b4), self.inv_stem_scale, ptr(st.qbufs[0]), sp),
+                      'lfd_stem_faster_fused_i8')
+            else:
+                c0, w1, b1, w2, b2 = self.stem_first
+                st.front['stem'] = 'lfd_stem_conv_i8'
+                check(l.lfd_stem_conv_i8(ptr(x), fmt, st.n, st.h, st.w, c0, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
+                                         self.inv_stem_scale, ptr(st.qbufs[0]), sp), 'lfd_stem_conv_i8')
+            return True
+        st.front['stem'] = 'fp16'
+        self.stem_f16(st)
         engine.EnginePlan.run_backbone(self, x, fmt, st)
         if self.entry_f16 is None:
+            st.front['quantise'] = True
             self.run_quantise(st)
+        return False
 
     def run_quantise(self, st):
-        src = st.bufs[self.stage_in]
+        src = self.stem_f16(st)
         l, sp = lib(), stream_ptr()
         if src.shape[3] == self.qbuf_channels[0]:
             check(l.lfd_quantize_nhwc_f16_i8(ptr(src), ptr(st.qbufs[0]), src.numel(), self.inv_stem_scale, sp),
@@ -400,13 +466,15 @@ class Int8Plan(engine.EnginePlan):
     def run_entry(self, d, c1, c2, st, f16):
         """a whole 64-channel stage-entry block (d: the identity branch, c1, c2 adding d) in one launch; f16: the input is the
         fp16 stem map, quantised on the way in"""
-        src = st.bufs[self.stage_in] if f16 else st.qbufs[c1.src]
+        src = self.stem_f16(st) if f16 else st.qbufs[c1.src]
         check(lib().lfd_entry_i8_fused(st.n, src.shape[1], src.shape[2], 1 if f16 else 0, src.shape[3], ptr(src),
                                        self.inv_stem_scale if f16 else 0.0, ptr(c1.w), ptr(c1.mult), ptr(c1.biasq), ptr(d.w),
                                        ptr(d.mult), ptr(d.biasq), ptr(c2.w), ptr(c2.mult), ptr(c2.biasq), c2.res_mult,
                                        ptr(st.qbufs[c2.dst]), stream_ptr()), 'lfd_entry_i8_fused')
 
-    def run_stages(self, st, after=None):
+    def run_stages(self, st, after=None, stem_i8=False):
+        """the int8 launches of the stages.  stem_i8: the stem launch wrote int8 buffer 0 itself (run_stem's return value), so
+        the first 'entry' launch of the 'full' route reads it instead of the fp16 stem map"""
         base = len(self.convs)
         if self.fused:
             for k, la in enumerate(self.launches):
@@ -420,7 +488,10 @@ class Int8Plan(engine.EnginePlan):
                 elif la.kind == 'block128':
                     self.run_block128(cs[0], cs[1], st)
                 elif la.kind == 'entry':
-                    self.run_entry(cs[0], cs[1], cs[2], st, k == self.entry_f16)
+                    f16 = k == self.entry_f16 and not stem_i8
+                    if cs[0].src == 0 and getattr(st, 'front', None) is not None:
+                        st.front['entry_in_format'] = 1 if f16 else 0
+                    self.run_entry(cs[0], cs[1], cs[2], st, f16)
                 else:
                     self.run_layer(cs[0], st)
             if after and base + len(self.launches) in after:
@@ -436,5 +507,5 @@ class Int8Plan(engine.EnginePlan):
     def run_backbone(self, x, fmt, st, after=None):
         if self.scales is None:
             raise RuntimeError('Int8Plan: no scales yet (calibrate() + set_scales(), or deployment.build_int8_engine)')
-        self.run_stem(x, fmt, st)
-        self.run_stages(st, after)
+        stem_i8 = self.run_stem(x, fmt, st)
+        self.run_stages(st, after, stem_i8=stem_i8)

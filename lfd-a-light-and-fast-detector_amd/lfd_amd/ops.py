@@ -1023,6 +1023,18 @@ def entry_i8_fused(x, w1_packed, mult1, biasq1, ds_w_packed, ds_mult, ds_biasq, 
     return out
 
 
+def stem_conv_i8_supported(in_format, channels, has_tail):
+    """does lfd_stem_conv_i8 (the 'fast' stem unit writing the int8 map) take this frame format, stem width and tail?  Nothing
+    launched."""
+    return lib().lfd_stem_conv_i8_supported(in_format, channels, 1 if has_tail else 0) == 0
+
+
+def stem_faster_fused_i8_supported(in_format, channels):
+    """does lfd_stem_faster_fused_i8 (the one-launch 'faster' stem writing the int8 map) take this frame format and stem width?
+    Nothing launched."""
+    return lib().lfd_stem_faster_fused_i8_supported(in_format, channels) == 0
+
+
 def quantize_f16_i8(x, inv_scale, out=None, channels=None):
     """fp16 tensor -> int8 of the same shape: clamp(rint(float(x) * inv_scale), -127, 127) (lfd_quantize_nhwc_f16_i8).
     channels > x.shape[-1]: the last axis is widened to `channels` with zeros (lfd_quantize_pad_nhwc_f16_i8)."""
