@@ -649,8 +649,9 @@ LFD_API int lfd_quantize_nhwc_f16_i8(const void* in, void* out, int64_t count, f
 LFD_API int lfd_quantize_pad_nhwc_f16_i8(const void* in, void* out, int64_t pixels, int32_t cin, int32_t cout, float inv_scale,
                                          lfd_stream_t stream);
 
-/* Fused int8 launches (csrc/block_i8.hip; the fused=True route of lfd_amd/engine_i8.py).  Both equal the lfd_conv2d_nhwc_i8
- * launches they replace in every bit: the i32 sums are exact and the epilogues are the expressions above.
+/* Fused int8 launches (csrc/block_i8.hip and, the stride-2 pair, csrc/conv_i8.hip; the fused=True route of
+ * lfd_amd/engine_i8.py).  Both equal the lfd_conv2d_nhwc_i8 launches they replace in every bit: the i32 sums are exact and the
+ * epilogues are the expressions above (one definition, csrc/i8_impl.h).
  *
  * lfd_block_i8_fused: a whole residual block, y = ReLU(conv2(ReLU(conv1(x))) + x), both convs 3x3, stride 1, pad 1, 64 -> 64
  * channels.  in [n,h,w,64] int8; w1_packed / mult1 / biasq1 and w2_packed / mult2 / biasq2: the operands of the two

@@ -1,7 +1,7 @@
 // csrc/block128_i8.hip -- the INT8 deployment mode's one-launch 128-channel residual block (the block128 option):
 //   y = ReLU(conv2(ReLU(conv1(x))) + x), both convs 3x3 stride 1 pad 1, 128 -> 128, the int8 tensors and constants of the two
-// lfd_conv2d_nhwc_i8 calls it replaces.  The i32 sums are exact in any order and the epilogues below are conv_i8.hip's
-// expressions (the compare / select requantisation included), so the results are required to agree in every bit
+// lfd_conv2d_nhwc_i8 calls it replaces.  The i32 sums are exact in any order and the epilogue steps are the functions of
+// csrc/i8_impl.h that conv_i8.hip calls (the compare / select requantisation included), so the results are required to agree in every bit
 // (tests/test_gpu_block128_i8_exact.py).
 //
 // One filter is 147456 bytes: neither fits LDS next to a tile, and a producer / consumer cut like csrc/block_i8.hip's would leave
@@ -24,74 +24,22 @@
 //   * two barriers per tile.  The halo of the workgroup's next tile travels from memory in two halves of four 16-byte pieces
 //     per thread, one under each conv, into the other input buffer; the mid buffer is single (conv1 of the next tile writes it
 //     behind the next barrier).
-//   * v_mfma_i32_32x32x32_i8 with A = filter, B = pixels and the lane map of conv_i8.hip: a lane ends with 16 consecutive
+//   * v_mfma_i32_32x32x32_i8 with A = filter, B = pixels and the lane map of csrc/i8_impl.h: a lane ends with 16 consecutive
 //     channels of its pixel.
 //   * LDS: 2 x 34560 (input) + 25920 (mid) = 95040 bytes, dynamic.  hipcc reports 192 VGPRs + 240 AGPRs without the tap and
 //     256 + 254 with it (the float64 tap epilogue), no scratch in either; 1 wave per SIMD.
-#include "common.h"
+#include "i8_impl.h"
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int B128I8_MAX_WORKGROUPS = 256;  // one 256-thread workgroup per CU, one wave per SIMD
-
-// clamp(rint(v), -127, 127) of 16 values -> 16 bytes (conv_i8.hip's expression)
-__device__ __forceinline__ uint4 requant16(const float (&vv)[16]) {
-  union { uint4 u; int8_t b[16]; } o;
-#pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    float r = __builtin_rintf(vv[g]);
-    r = r > 127.f ? 127.f : r;
-    r = r < -127.f ? -127.f : r;
-    o.b[g] = (int8_t)(int)r;
-  }
-  return o.u;
-}
 
 // an MFMA's A operand may be an AGPR: this pins a filter fragment to the accumulator half of the unified register file where it
 // is used, so that the allocator keeps it there across the tile loop instead of copying it to a VGPR in front of every MFMA
 __device__ __forceinline__ void keep_in_agpr(i32x4& w) { asm("" : "+a"(w)); }
 
-__device__ __forceinline__ void load16f(const float* src, float (&dst)[16]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float4 f = *reinterpret_cast<const float4*>(src + 4 * j);
-    dst[4 * j + 0] = f.x; dst[4 * j + 1] = f.y; dst[4 * j + 2] = f.z; dst[4 * j + 3] = f.w;
-  }
-}
-
-struct B128I8Args {
-  const int8_t* in;        // [N,H,W,128]
-  const i32x4* w1;         // packed [4][36][64 lanes]
-  const float* mult1;      // [128]
-  const float* biasq1;
-  const i32x4* w2;
-  const float* mult2;
-  const float* biasq2;
-  int8_t* out_i8;          // [N,H,W,128]
-  _Float16* out_f16;       // [N,H,W,128] or NULL
-  float res_mult, out_scale;
-  int N, H, W;
-  int tiles_x, tiles_y, ntiles;
-};
-
-struct B128I8 {
-  static constexpr int C = 128;
-  static constexpr int TH = 8, TW = 16;                 // output tile
-  static constexpr int MH = TH + 2, MW = TW + 2;        // mid tile (conv1's output with conv2's halo)
-  static constexpr int MPIX = MH * MW;                  // 180
-  static constexpr int IH = TH + 4, IW = TW + 4;        // input halo tile
-  static constexpr int IPIX = IH * IW;                  // 240
-  static constexpr int PITCH = C + 16;                  // bytes per LDS pixel (16 of bank spread), input and mid
-  static constexpr int IN_BYTES = IPIX * PITCH;         // 34560
-  static constexpr int MID_BYTES = MPIX * PITCH;        // 25920
-  static constexpr int PIECES = IPIX * (C / 16);        // 16-byte pieces of the input halo
-  static constexpr int NIT = (PIECES + 255) / 256;      // per thread: 8,
-  static constexpr int NITH = NIT / 2;                  // in two halves of 4
-  static constexpr int NQ = C / 32;                     // k-steps per tap
-  static constexpr int NK = 9 * NQ;                     // k-steps of a 3x3x128 contraction
+struct B128I8 : BlockI8Cfg<128> {
+  static constexpr int NITH = NIT / 2;                  // the halo's 8 pieces per thread travel in two halves of 4
   static constexpr int NK2A = 24;                       // k-steps of conv2's slab held in AGPRs next to all of conv1's (240 of 256)
   static constexpr int MPAIRS = (MPIX + 63) / 64;       // pairs of MFMA pixel tiles of the mid tile: 3
   static constexpr int OPAIRS = TH / 4;                 // of the output tile: 2
@@ -146,7 +94,7 @@ __device__ __forceinline__ void contract2(const char* base, const int (&pb)[2], 
 }
 
 template <bool TAP>
-__global__ __launch_bounds__(256) void k_block128_i8(const B128I8Args a) {
+__global__ __launch_bounds__(256) void k_block128_i8(const BlockI8Args a) {
   using B = B128I8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, p = lane & 31, kh = lane >> 5;
@@ -156,32 +104,16 @@ __global__ __launch_bounds__(256) void k_block128_i8(const B128I8Args a) {
   const int my = (a.ntiles - (int)blockIdx.x + grid - 1) / grid;      // tiles of this workgroup (>= 1: grid <= ntiles)
 
   // half `part` of the input halo of tile t: memory -> registers -> LDS
-  auto load_halo = [&](int t, int part, uint4 (&v)[B::NITH]) {
-    const int tx = t % a.tiles_x;
-    const int tq = t / a.tiles_x;
-    const int ty = tq % a.tiles_y, n = tq / a.tiles_y;
-    const int8_t* in_img = a.in + (size_t)n * a.H * a.W * B::C;
-#pragma unroll
-    for (int it = 0; it < B::NITH; ++it) {
-      const int i = tid + 256 * (part * B::NITH + it);
-      const int pix = i >> 3, ck = i & 7;
-      const int iy = pix / B::IW, ix = pix - iy * B::IW;
-      const int gy = ty * B::TH - 2 + iy, gx = tx * B::TW - 2 + ix;
-      const bool ok = i < B::PIECES && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-      v[it] = *reinterpret_cast<const uint4*>(in_img + (ok ? (gy * a.W + gx) * B::C + ck * 16 : 0));
-      if (!ok) v[it] = make_uint4(0u, 0u, 0u, 0u);
-    }
+  auto load_halo = [&](int t, int part, I8Piece<> (&v)[B::NITH]) {
+    const I8Tile tl = i8_tile_of(t, a.tiles_x, a.tiles_y);
+    i8_halo_load<B::C, B::IW, B::PIECES, 2, 256, B::NITH>(v, a.in + (size_t)tl.n * a.H * a.W * B::C, tid, part * B::NITH,
+                                                             tl.ty * B::TH, tl.tx * B::TW, a.H, a.W);
   };
-  auto store_halo = [&](int buf, int part, const uint4 (&v)[B::NITH]) {
-    char* dst = smem + B::OFF_IN + buf * B::IN_BYTES;
-#pragma unroll
-    for (int it = 0; it < B::NITH; ++it) {
-      const int i = tid + 256 * (part * B::NITH + it);
-      if (i < B::PIECES) *reinterpret_cast<uint4*>(dst + (i >> 3) * B::PITCH + (i & 7) * 16) = v[it];
-    }
+  auto store_halo = [&](int buf, int part, const I8Piece<> (&v)[B::NITH]) {
+    i8_halo_store<B::C, B::PIECES, 256, B::NITH>(smem + B::OFF_IN + buf * B::IN_BYTES, v, tid, part * B::NITH);
   };
 
-  uint4 hv[B::NITH];
+  I8Piece<> hv[B::NITH];
   load_halo(blockIdx.x, 0, hv);
   store_halo(0, 0, hv);
   load_halo(blockIdx.x, 1, hv);
@@ -217,9 +149,7 @@ __global__ __launch_bounds__(256) void k_block128_i8(const B128I8Args a) {
   for (int s = 0; s < my; ++s) {
     __syncthreads();      // in[s & 1] is complete; every wave is done reading mid (conv2 of tile s - 1)
     const int t = (int)blockIdx.x + s * grid;
-    const int tx = t % a.tiles_x;
-    const int tq = t / a.tiles_x;
-    const int ty = tq % a.tiles_y, n = tq / a.tiles_y;
+    const I8Tile ti = i8_tile_of(t, a.tiles_x, a.tiles_y);
     const bool more = s + 1 < my;
     // the halo of the next tile travels in two halves, one under each conv, into in[(s + 1) & 1]: that buffer was last read in
     // step s - 1, before the barrier above
@@ -227,27 +157,20 @@ __global__ __launch_bounds__(256) void k_block128_i8(const B128I8Args a) {
     const char* in_t = smem + B::OFF_IN + (s & 1) * B::IN_BYTES;
 
     // ------------------------------------------------------------------------------------------ conv1: input halo -> mid
-    // mid pixel m = (2 pp + j) * 32 + p, linear over 10 x 18; mid (row, col), tap (dy, dx) = input tile (row + dy, col + dx)
+    // mid pixel m = (2 pp + j) * 32 + p
 #pragma unroll 1
     for (int pp = 0; pp < B::MPAIRS; ++pp) {
       int pbase[2], mrow[2], mcol[2];
       bool mval[2];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int m = (2 * pp + j) * 32 + p;
-        mval[j] = m < B::MPIX;
-        const int mc = mval[j] ? m : B::MPIX - 1;
-        mrow[j] = mc / B::MW;
-        mcol[j] = mc - mrow[j] * B::MW;
-        pbase[j] = (mrow[j] * B::IW + mcol[j]) * B::PITCH + kh * 16;
-      }
+      for (int j = 0; j < 2; ++j) i8_block_mid_pixel<B>((2 * pp + j) * 32 + p, kh, pbase[j], mrow[j], mcol[j], mval[j]);
       i32x16 acc[2];
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int g = 0; g < 16; ++g) acc[j][g] = 0;
       contract2<B::IW, B::NK>(in_t, pbase, w1s, acc);
-      // epilogue: mid = clamp(rint(max(fmaf(acc, mult1, biasq1), 0))); 0 outside the image (conv2's padding)
+      // epilogue: mid = requantised ReLU(conv1); 0 outside the image (conv2's padding)
       float mm[16], bb[16];
       load16f(a.mult1 + c0, mm);
       load16f(a.biasq1 + c0, bb);
@@ -255,12 +178,9 @@ __global__ __launch_bounds__(256) void k_block128_i8(const B128I8Args a) {
       for (int j = 0; j < 2; ++j) {
         float vv[16];
 #pragma unroll
-        for (int g = 0; g < 16; ++g) {
-          vv[g] = __builtin_fmaf((float)acc[j][g], mm[g], bb[g]);
-          vv[g] = vv[g] > 0.f ? vv[g] : 0.f;
-        }
-        uint4 o = requant16(vv);
-        const int gy = ty * B::TH - 1 + mrow[j], gx = tx * B::TW - 1 + mcol[j];
+        for (int g = 0; g < 16; ++g) vv[g] = i8_relu(i8_affine(acc[j][g], mm[g], bb[g]));
+        uint4 o = i8_requant16(vv);
+        const int gy = ti.ty * B::TH - 1 + mrow[j], gx = ti.tx * B::TW - 1 + mcol[j];
         if (gy < 0 || gy >= a.H || gx < 0 || gx >= a.W) o = make_uint4(0u, 0u, 0u, 0u);
         if (mval[j]) *reinterpret_cast<uint4*>(mid_t + ((2 * pp + j) * 32 + p) * B::PITCH + c0) = o;
       }
@@ -272,21 +192,15 @@ __global__ __launch_bounds__(256) void k_block128_i8(const B128I8Args a) {
     __syncthreads();      // mid is complete
 
     // ------------------------------------------------------------------------------------------ conv2: mid -> output
-    // MFMA pixel tile 2 pp + j = output rows 2 (2 pp + j), + 1 of the tile; out (y, x) reads mid (y + dy, x + dx)
+    // MFMA pixel tile 2 pp + j = output rows 2 (2 pp + j), + 1 of the tile
 #pragma unroll 1
     for (int pp = 0; pp < B::OPAIRS; ++pp) {
       int cbase[2];
       size_t opix[2];
       bool ook[2];
-      union { uint4 u; int8_t b[16]; } r[2];
+      I8x16 r[2];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int ly = 2 * (2 * pp + j) + (p >> 4), lx = p & 15;
-        cbase[j] = (ly * B::MW + lx) * B::PITCH + kh * 16;
-        const int oy = ty * B::TH + ly, ox = tx * B::TW + lx;
-        ook[j] = oy < a.H && ox < a.W;
-        opix[j] = ((size_t)n * a.H * a.W + (size_t)((ook[j] ? oy : 0) * a.W + (ook[j] ? ox : 0))) * B::C + c0;
-      }
+      for (int j = 0; j < 2; ++j) i8_block_out_pixel<B>(a, ti, 2 * (2 * pp + j) + (p >> 4), p & 15, kh, c0, cbase[j], opix[j], ook[j]);
       i32x16 acc[2];
 #pragma unroll
       for (int j = 0; j < 2; ++j)
@@ -303,21 +217,14 @@ __global__ __launch_bounds__(256) void k_block128_i8(const B128I8Args a) {
         r[j].u = *reinterpret_cast<const uint4*>(in_t + ((ly + 2) * B::IW + lx + 2) * B::PITCH + c0);
         float vv[16];
 #pragma unroll
-        for (int g = 0; g < 16; ++g) {
-          vv[g] = __builtin_fmaf((float)acc[j][g], mm[g], bb[g]);
-          vv[g] = __builtin_fmaf((float)r[j].b[g], a.res_mult, vv[g]);
-          vv[g] = vv[g] > 0.f ? vv[g] : 0.f;
-        }
-        const uint4 o = requant16(vv);
+        for (int g = 0; g < 16; ++g) vv[g] = i8_relu(i8_residual(i8_affine(acc[j][g], mm[g], bb[g]), r[j].b[g], a.res_mult));
+        const uint4 o = i8_requant16(vv);
         if (ook[j]) *reinterpret_cast<uint4*>(a.out_i8 + opix[j]) = o;
-        if (TAP) {              // a pyramid tap: evaluated in float64 and rounded once, as conv_i8.hip does
-          union { uint4 u[2]; _Float16 h[16]; } f;
+        if (TAP) {              // a pyramid tap
+          F16x16 f;
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
-            double dv = __builtin_fma((double)acc[j][g], (double)mm[g], (double)bb[g]);
-            dv = __builtin_fma((double)r[j].b[g], (double)a.res_mult, dv);
-            dv = dv > 0.0 ? dv : 0.0;
-            f.h[g] = (_Float16)(float)(dv * (double)a.out_scale);
+            f.h[g] = i8_tap(acc[j][g], mm[g], bb[g], true, r[j].b[g], a.res_mult, true, a.out_scale);
             if ((g & 3) == 3) __builtin_amdgcn_sched_barrier(0);      // four elements' float64 temporaries at a time
           }
           if (ook[j]) {
@@ -332,7 +239,7 @@ __global__ __launch_bounds__(256) void k_block128_i8(const B128I8Args a) {
 }
 
 template <bool TAP>
-int launch_block128_i8(const B128I8Args& a, hipStream_t st) {
+int launch_block128_i8(const BlockI8Args& a, int blocks, hipStream_t st) {
   static unsigned long long attr_set = 0;       // bit = device ordinal
   const int dev = lfd_device_ordinal();
   if (LFD_ONCE_PER_DEVICE(attr_set, dev)) {
@@ -341,7 +248,6 @@ int launch_block128_i8(const B128I8Args& a, hipStream_t st) {
       return LFD_ERR_LAUNCH_FAILED;
     LFD_DONE_ON_DEVICE(attr_set, dev);
   }
-  const int blocks = a.ntiles < B128I8_MAX_WORKGROUPS ? a.ntiles : B128I8_MAX_WORKGROUPS;
   hipLaunchKernelGGL(k_block128_i8<TAP>, dim3((unsigned)blocks), dim3(256), B128I8::LDS_BYTES, st, a);
   LFD_CHECK_LAUNCH();
   return LFD_OK;
@@ -353,23 +259,10 @@ extern "C" int lfd_block128_i8_fused(int32_t n, int32_t h, int32_t w, const void
                                      const float* biasq1, const void* w2_packed, const float* mult2, const float* biasq2,
                                      float res_mult, void* out_i8, void* out_f16, float out_scale, lfd_stream_t stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!in || !w1_packed || !mult1 || !biasq1 || !w2_packed || !mult2 || !biasq2 || !out_i8) return LFD_ERR_INVALID_ARGUMENT;
-  if (n < 1 || h < 1 || w < 1) return LFD_ERR_INVALID_ARGUMENT;
-  if (!lfd_aligned16(in) || !lfd_aligned16(w1_packed) || !lfd_aligned16(mult1) || !lfd_aligned16(biasq1) ||
-      !lfd_aligned16(w2_packed) || !lfd_aligned16(mult2) || !lfd_aligned16(biasq2) || !lfd_aligned16(out_i8) ||
-      !lfd_aligned16(out_f16))
-    return LFD_ERR_INVALID_ARGUMENT;
-  if (in == out_i8) return LFD_ERR_INVALID_ARGUMENT;
-  if ((long)h * w * 128 > 0x7fffffffL) return LFD_ERR_UNSUPPORTED;           // 32-bit offsets inside an image
-  B128I8Args a{};
-  a.in = (const int8_t*)in; a.w1 = (const i32x4*)w1_packed; a.mult1 = mult1; a.biasq1 = biasq1;
-  a.w2 = (const i32x4*)w2_packed; a.mult2 = mult2; a.biasq2 = biasq2;
-  a.out_i8 = (int8_t*)out_i8; a.out_f16 = (_Float16*)out_f16; a.res_mult = res_mult; a.out_scale = out_scale;
-  a.N = n; a.H = h; a.W = w;
-  a.tiles_x = (w + B128I8::TW - 1) / B128I8::TW;
-  a.tiles_y = (h + B128I8::TH - 1) / B128I8::TH;
-  const long tiles = (long)a.tiles_x * a.tiles_y * n;
-  if (tiles > 0x7fffffffL - B128I8_MAX_WORKGROUPS) return LFD_ERR_UNSUPPORTED;
-  a.ntiles = (int)tiles;
-  return out_f16 ? launch_block128_i8<true>(a, st) : launch_block128_i8<false>(a, st);
+  BlockI8Args a{};
+  int blocks = 0;
+  const int rc = i8_block_args<B128I8>(a, blocks, B128I8_MAX_WORKGROUPS, n, h, w, in, w1_packed, mult1, biasq1, w2_packed, mult2,
+                                       biasq2, res_mult, out_i8, out_f16, out_scale);
+  if (rc != LFD_OK) return rc;
+  return out_f16 ? launch_block128_i8<true>(a, blocks, st) : launch_block128_i8<false>(a, blocks, st);
 }

@@ -53,21 +53,25 @@ __device__ __forceinline__ uint32_t lfd_cvt_pk_max(float x, float y, uint32_t lo
   return r.u;
 }
 
+// The INT8 mode's requantisation, the reference expression: clamp(rint(v), -127, 127), rint half to even, a NaN becomes 0.  The
+// one definition: every int8 value the library writes is this expression or (csrc/i8_impl.h: i8_requant16_fast) a form proven
+// equal to it.
+__device__ __forceinline__ int8_t lfd_requant_i8(float v) {
+  float r = __builtin_rintf(v);
+  r = r > 127.f ? 127.f : r;
+  r = r < -127.f ? -127.f : r;
+  return (int8_t)(int)r;
+}
+
 // The INT8 mode's quantise step on 16 fp16 values (two 16-byte chunks) -> 16 int8 (one chunk), element by element:
-// q = clamp(rint((float)x * inv_scale), -127, 127), one fp32 multiply, rint half to even, a NaN becomes 0.  The one definition of
-// the expression: the quantise launches (csrc/conv_i8.hip) and the int8-output stem kernels (csrc/stem.hip, csrc/stem_fused.hip)
-// all call it, which is what their bit equality rests on.
+// q = lfd_requant_i8((float)x * inv_scale), one fp32 multiply.  The quantise launches (csrc/conv_i8.hip) and the int8-output stem
+// kernels (csrc/stem.hip, csrc/stem_fused.hip) all call it, which is what their bit equality rests on.
 __device__ __forceinline__ uint4 lfd_quant16_f16_i8(const uint4& lo, const uint4& hi, float inv_scale) {
   union { uint4 u[2]; _Float16 h[16]; } x;
   x.u[0] = lo; x.u[1] = hi;
   union { uint4 u; int8_t b[16]; } o;
 #pragma unroll
-  for (int g = 0; g < 16; ++g) {
-    float r = __builtin_rintf((float)x.h[g] * inv_scale);
-    r = r > 127.f ? 127.f : r;
-    r = r < -127.f ? -127.f : r;
-    o.b[g] = (int8_t)(int)r;
-  }
+  for (int g = 0; g < 16; ++g) o.b[g] = lfd_requant_i8((float)x.h[g] * inv_scale);
   return o.u;
 }
 

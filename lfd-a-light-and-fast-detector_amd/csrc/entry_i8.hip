@@ -3,8 +3,9 @@
 //   y1  = ReLU(conv1(xq)), 3x3 stride 2 pad 1          id = downsample(xq), 1x1 stride 2, no ReLU
 //   out = ReLU(conv2(y1) + id), 3x3 stride 1 pad 1
 // all three convs 64 -> 64 (padded) channels, the operands of lfd_conv2d_downsample_nhwc_i8 + lfd_conv2d_nhwc_i8 (and of the
-// quantise launch in front of them).  The i32 sums are exact in any order and the epilogues are conv_i8.hip's fp32 expressions,
-// so the launch is required to equal the launches it replaces in every bit (tests/test_gpu_entry_i8_exact.py).
+// quantise launch in front of them).  The i32 sums are exact in any order and the epilogue steps are the functions of
+// csrc/i8_impl.h that conv_i8.hip calls (the lane map and the LDS pixel pitch are stated there too), so the launch is required
+// to equal the launches it replaces in every bit (tests/test_gpu_entry_i8_exact.py).
 //
 // The cut is csrc/block_i8.hip's producer / consumer one, with a 4 x 16 output tile so that every LDS buffer can be doubled:
 //   * one 512-thread workgroup per CU, persistent, walking (image, tile) with stride gridDim.x (<= EI8_MAX_WORKGROUPS).  Waves
@@ -13,7 +14,7 @@
 //   * filters are stationary: a producer wave owns one 32-channel slab of conv1 (72 VGPRs) and of the 1x1 (8 VGPRs), a consumer
 //     wave one slab of conv2 (72 VGPRs), read once per workgroup in the ops.pack_conv_weight_i8 order.
 //   * per output tile the y1 tile is 6 x 18 (conv2's halo) = 108 pixels, numbered linearly over four 32-pixel MFMA tiles, two
-//     per producer pixel group, and the input halo is 13 x 37 pixels (80-byte LDS pixels as in conv_i8.hip).  y1 pixels outside
+//     per producer pixel group, and the input halo is 13 x 37 pixels (80-byte LDS pixels).  y1 pixels outside
 //     the oh x ow map are conv2's zero padding and are written as 0; input pixels outside the image are 0.
 //   * the 1x1 reads conv1's centre tap.  Producer wave w computes exactly the (pixel tile, channel slab) of id that consumer
 //     wave w + 4 adds, in the same lane layout, so id crosses as one 16-byte LDS slot per (wave, lane).
@@ -24,45 +25,11 @@
 //     y1 / id[s & 1] in step s - 1: both before this step's barrier.
 //   * LDS: 2 x 38480 (input) + 2 x 8640 (y1) + 2 x 4096 (id) = 102432 bytes, dynamic.  hipcc reports 166 VGPRs (format 0) and
 //     219 VGPRs (format 1), no AGPRs, no scratch.
-#include "common.h"
+#include "i8_impl.h"
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int EI8_MAX_WORKGROUPS = 256;     // one 512-thread workgroup per CU
-
-// clamp(rint(v), -127, 127) of 16 values -> 16 bytes: the value of conv_i8.hip's expression in three VALU instructions per
-// element and three per packed dword instead of ten.  The clamp comes first (rint is monotone and the bounds are integers, so
-// rint(clamp(v)) = clamp(rint(v))); c + 1.5 * 2^23 then lies in [2^23, 2^24), where fp32 has a spacing of 1, so the add's own
-// round-to-nearest-even IS rint(c), and the sum's low mantissa byte is that integer in two's complement.  LO = 0 folds a
-// preceding ReLU into the clamp (max(v, 0), -0 included, rounds to the same integer as v clamped at 0).  Finite v only: the
-// epilogue constants and the fp16 map are finite.
-template <int LO>
-__device__ __forceinline__ uint32_t q8bits(float v) {
-  return __builtin_bit_cast(uint32_t, __builtin_amdgcn_fmed3f(v, (float)LO, 127.f) + 12582912.f);
-}
-__device__ __forceinline__ uint32_t pack4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {       // the four low bytes
-  const uint32_t lo = __builtin_amdgcn_perm(b, a, 0x0c0c0400u), hi = __builtin_amdgcn_perm(d, c, 0x0c0c0400u);
-  return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
-}
-template <int LO>
-__device__ __forceinline__ uint4 requant16(const float (&vv)[16]) {
-  uint32_t o[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    o[j] = pack4(q8bits<LO>(vv[4 * j]), q8bits<LO>(vv[4 * j + 1]), q8bits<LO>(vv[4 * j + 2]), q8bits<LO>(vv[4 * j + 3]));
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-__device__ __forceinline__ void load16f(const float* src, float (&dst)[16]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float4 f = *reinterpret_cast<const float4*>(src + 4 * j);
-    dst[4 * j + 0] = f.x; dst[4 * j + 1] = f.y; dst[4 * j + 2] = f.z; dst[4 * j + 3] = f.w;
-  }
-}
 
 struct EI8Args {
   const void* in;          // FMT 0: int8 [N,H,W,64]; FMT 1: fp16 [N,H,W,cin]
@@ -102,9 +69,6 @@ struct EI8 {
 static_assert(EI8::LDS_BYTES <= 160 * 1024, "LDS capacity");
 static_assert(EI8::MPIX <= 4 * 32, "y1 tile over four MFMA pixel tiles");
 
-// a 16-channel piece of a halo pixel on its way from memory to LDS: 16 bytes of int8 (FMT 0) or 32 bytes of fp16 (FMT 1)
-template <int FMT> struct Piece { uint4 u[FMT == 0 ? 1 : 2]; };
-
 template <int FMT>
 __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -126,19 +90,21 @@ __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
 #pragma unroll
   for (int q = 0; q < 2; ++q) wd[q] = a.wd[(size_t)(ct * 2 + q) * 64 + lane];      // (the consumers never use theirs)
 
-  // input halo of tile t: memory -> registers (all 512 threads) -> LDS
-  auto load_halo = [&](int tid, int t, Piece<FMT> (&v)[EI8::NIT]) {
-    const int tx = t % a.tiles_x;
-    const int tq = t / a.tiles_x;
-    const int ty = tq % a.tiles_y, n = tq / a.tiles_y;
+  // input halo of tile t: memory -> registers (all 512 threads) -> LDS.  The load is i8_impl.h's i8_halo_load with an element size
+  // and a runtime channel count (chunks at or above a.cin are 0), and stands here as this kernel's own copy: called through the
+  // shared template -- in every shape tried, the element size and the narrow check as template arguments included -- hipcc
+  // evaluates the bounds checks in another order and the kernel's assembly changes, and this kernel is required to stay the
+  // parent's instruction for instruction (profiles/i8_impl_isa_equality.txt).  The LDS slot is the shared i8_halo_slot.
+  auto load_halo = [&](int tid, int t, I8Piece<FMT + 1> (&v)[EI8::NIT]) {
+    const I8Tile tl = i8_tile_of(t, a.tiles_x, a.tiles_y);
     const int esz = FMT == 0 ? 1 : 2;
-    const char* in_img = (const char*)a.in + (size_t)n * a.H * a.W * a.cin * esz;
+    const char* in_img = (const char*)a.in + (size_t)tl.n * a.H * a.W * a.cin * esz;
 #pragma unroll
     for (int it = 0; it < EI8::NIT; ++it) {
       const int i = tid + 512 * it;
       const int pix = i >> 2, ck = i & 3;
       const int iy = pix / EI8::IW, ix = pix - iy * EI8::IW;
-      const int gy = ty * EI8::TH * 2 - 3 + iy, gx = tx * EI8::TW * 2 - 3 + ix;
+      const int gy = tl.ty * EI8::TH * 2 - 3 + iy, gx = tl.tx * EI8::TW * 2 - 3 + ix;
       const bool ok = i < EI8::PIECES && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W && ck * 16 < a.cin;
       const char* src = in_img + (ok ? ((gy * a.W + gx) * a.cin + ck * 16) * esz : 0);     // < h * w * 128 < 2^31
       v[it].u[0] = *reinterpret_cast<const uint4*>(src);
@@ -149,7 +115,7 @@ __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
       }
     }
   };
-  auto store_halo = [&](int tid, int buf, const Piece<FMT> (&v)[EI8::NIT]) {
+  auto store_halo = [&](int tid, int buf, const I8Piece<FMT + 1> (&v)[EI8::NIT]) {
     char* dst = smem + EI8::OFF_IN + buf * EI8::IN_BYTES;
 #pragma unroll
     for (int it = 0; it < EI8::NIT; ++it) {
@@ -165,13 +131,13 @@ __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
         float p[16];
 #pragma unroll
         for (int g = 0; g < 16; ++g) p[g] = (float)x.h[g] * a.in_inv_scale;
-        o = requant16<-127>(p);
+        o = i8_requant16_fast<-127>(p);
       }
-      if (i < EI8::PIECES) *reinterpret_cast<uint4*>(dst + (i >> 2) * EI8::PITCH + (i & 3) * 16) = o;
+      if (i < EI8::PIECES) *reinterpret_cast<uint4*>(dst + i8_halo_slot<64>(i)) = o;
     }
   };
 
-  Piece<FMT> hv[EI8::NIT];
+  I8Piece<FMT + 1> hv[EI8::NIT];
   load_halo(tid, blockIdx.x, hv);
   store_halo(tid, 0, hv);
 
@@ -189,9 +155,7 @@ __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
     if (prod) {
       if (s < my) {
         // -------------------------------------------------------------------------------- producer: conv1 and 1x1 of tile s
-        const int t = (int)blockIdx.x + s * grid;
-        const int tx = t % a.tiles_x;
-        const int ty = (t / a.tiles_x) % a.tiles_y;
+        const I8Tile ti = i8_tile_of((int)blockIdx.x + s * grid, a.tiles_x, a.tiles_y);
         const char* in_t = smem + EI8::OFF_IN + (s & 1) * EI8::IN_BYTES;
         char* mid_t = smem + EI8::OFF_MID + (s & 1) * EI8::MID_BYTES;
         char* id_t = smem + EI8::OFF_ID + (s & 1) * EI8::ID_BYTES;
@@ -211,8 +175,8 @@ __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
           load16f(a.multd + c0, mm);
           load16f(a.biasqd + c0, bb);
 #pragma unroll
-          for (int g = 0; g < 16; ++g) vv[g] = __builtin_fmaf((float)accd[g], mm[g], bb[g]);
-          *reinterpret_cast<uint4*>(id_t + (tl & 255) * 16) = requant16<-127>(vv);
+          for (int g = 0; g < 16; ++g) vv[g] = i8_affine(accd[g], mm[g], bb[g]);
+          *reinterpret_cast<uint4*>(id_t + (tl & 255) * 16) = i8_requant16_fast<-127>(vv);
         }
 
         // y1 pixel m = (2 pg + pt) * 32 + p, linear over 6 x 18; y1 (row, col), tap (dy, dx) = halo (2 row + dy, 2 col + dx)
@@ -238,9 +202,9 @@ __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
           // epilogue: y1 = clamp(rint(max(fmaf(acc, mult1, biasq1), 0))); 0 outside the oh x ow map (conv2's padding)
           float vv[16];
 #pragma unroll
-          for (int g = 0; g < 16; ++g) vv[g] = __builtin_fmaf((float)acc[g], mm[g], bb[g]);
-          uint4 o = requant16<0>(vv);            // ReLU in the clamp
-          const int gy = ty * EI8::TH - 1 + mrow, gx = tx * EI8::TW - 1 + mcol;
+          for (int g = 0; g < 16; ++g) vv[g] = i8_affine(acc[g], mm[g], bb[g]);
+          uint4 o = i8_requant16_fast<0>(vv);            // ReLU in the clamp
+          const int gy = ti.ty * EI8::TH - 1 + mrow, gx = ti.tx * EI8::TW - 1 + mcol;
           if (gy < 0 || gy >= a.OH || gx < 0 || gx >= a.OW) o = make_uint4(0u, 0u, 0u, 0u);
           if (mval) *reinterpret_cast<uint4*>(mid_t + m * EI8::PITCH + c0) = o;
         }
@@ -248,10 +212,7 @@ __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
     } else {
       // ---------------------------------------------------------------------------- consumer: conv2 + store of tile s - 1
       if (s >= 1) {
-        const int t = (int)blockIdx.x + (s - 1) * grid;
-        const int tx = t % a.tiles_x;
-        const int tq = t / a.tiles_x;
-        const int ty = tq % a.tiles_y, n = tq / a.tiles_y;
+        const I8Tile ti = i8_tile_of((int)blockIdx.x + (s - 1) * grid, a.tiles_x, a.tiles_y);
         const char* mid_t = smem + EI8::OFF_MID + ((s - 1) & 1) * EI8::MID_BYTES;
         const char* id_t = smem + EI8::OFF_ID + ((s - 1) & 1) * EI8::ID_BYTES;
 
@@ -267,20 +228,17 @@ __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
           acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(ws[k], b, acc, 0, 0, 0);
         }
         // epilogue: lfd_conv2d_nhwc_i8's with a residual and ReLU; the identity is producer wave wv - 4's slot of this lane
-        union { uint4 u; int8_t b[16]; } r;
+        I8x16 r;
         r.u = *reinterpret_cast<const uint4*>(id_t + (tl & 255) * 16);
         float vv[16], mm[16], bb[16];
         load16f(a.mult2 + c0, mm);
         load16f(a.biasq2 + c0, bb);
 #pragma unroll
-        for (int g = 0; g < 16; ++g) {
-          vv[g] = __builtin_fmaf((float)acc[g], mm[g], bb[g]);
-          vv[g] = __builtin_fmaf((float)r.b[g], a.res_mult, vv[g]);
-        }
-        const uint4 o = requant16<0>(vv);        // ReLU in the clamp
-        const int oy = ty * EI8::TH + ly, ox = tx * EI8::TW + lx;
+        for (int g = 0; g < 16; ++g) vv[g] = i8_residual(i8_affine(acc[g], mm[g], bb[g]), r.b[g], a.res_mult);
+        const uint4 o = i8_requant16_fast<0>(vv);        // ReLU in the clamp
+        const int oy = ti.ty * EI8::TH + ly, ox = ti.tx * EI8::TW + lx;
         if (oy < a.OH && ox < a.OW)
-          *reinterpret_cast<uint4*>(a.out_i8 + ((size_t)n * a.OH * a.OW + (size_t)(oy * a.OW + ox)) * 64 + c0) = o;
+          *reinterpret_cast<uint4*>(a.out_i8 + ((size_t)ti.n * a.OH * a.OW + (size_t)(oy * a.OW + ox)) * 64 + c0) = o;
       }
     }
     if (more) store_halo(tl, (s + 1) & 1, hv);
@@ -288,7 +246,7 @@ __global__ __launch_bounds__(512) void k_entry_i8(const EI8Args a) {
 }
 
 template <int FMT>
-int launch_entry_i8(const EI8Args& a, hipStream_t st) {
+int launch_entry_i8(const EI8Args& a, int blocks, hipStream_t st) {
   static unsigned long long attr_set = 0;       // bit = device ordinal
   const int dev = lfd_device_ordinal();
   if (LFD_ONCE_PER_DEVICE(attr_set, dev)) {
@@ -297,7 +255,6 @@ int launch_entry_i8(const EI8Args& a, hipStream_t st) {
       return LFD_ERR_LAUNCH_FAILED;
     LFD_DONE_ON_DEVICE(attr_set, dev);
   }
-  const int blocks = a.ntiles < EI8_MAX_WORKGROUPS ? a.ntiles : EI8_MAX_WORKGROUPS;
   hipLaunchKernelGGL(k_entry_i8<FMT>, dim3((unsigned)blocks), dim3(512), EI8::LDS_BYTES, st, a);
   LFD_CHECK_LAUNCH();
   return LFD_OK;
@@ -335,10 +292,7 @@ extern "C" int lfd_entry_i8_fused(int32_t n, int32_t h, int32_t w, int32_t in_fo
   a.N = n; a.H = h; a.W = w; a.cin = in_channels;
   a.OH = (h - 1) / 2 + 1;
   a.OW = (w - 1) / 2 + 1;
-  a.tiles_x = (a.OW + EI8::TW - 1) / EI8::TW;
-  a.tiles_y = (a.OH + EI8::TH - 1) / EI8::TH;
-  const long tiles = (long)a.tiles_x * a.tiles_y * n;
-  if (tiles > 0x7fffffffL - EI8_MAX_WORKGROUPS) return LFD_ERR_UNSUPPORTED;
-  a.ntiles = (int)tiles;
-  return in_format == 0 ? launch_entry_i8<0>(a, st) : launch_entry_i8<1>(a, st);
+  const int blocks = i8_tile_grid(a, n, a.OH, a.OW, EI8::TH, EI8::TW, EI8_MAX_WORKGROUPS);
+  if (!blocks) return LFD_ERR_UNSUPPORTED;
+  return in_format == 0 ? launch_entry_i8<0>(a, blocks, st) : launch_entry_i8<1>(a, blocks, st);
 }

@@ -152,7 +152,7 @@ class Int8Engine(object):
 
     @property
     def fused(self):
-        """whether the stages run the fused launches of csrc/block_i8.hip (build_int8_engine(..., fused=True)); the bits of every
+        """whether the stages run the fused launches of csrc/block_i8.hip and csrc/conv_i8.hip (build_int8_engine(..., fused=True)); the bits of every
         output are the same either way"""
         return self.plan.fused
 

@@ -84,7 +84,7 @@ class ConvI8(object):
 
 
 # a launch of the fused route over indices into the layer list: 'conv' (i,) one lfd_conv2d_nhwc_i8; 'pair' (downsample, conv1) one
-# lfd_conv2d_downsample_nhwc_i8; 'block' (conv1, conv2) one lfd_block_i8_fused; 'entry' (downsample, conv1, conv2) one
+# lfd_conv2d_downsample_nhwc_i8 (csrc/conv_i8.hip); 'block' (conv1, conv2) one lfd_block_i8_fused; 'entry' (downsample, conv1, conv2) one
 # lfd_entry_i8_fused (the 'full' route only); 'block128' (conv1, conv2) one lfd_block128_i8_fused (the block128 option only)
 Launch = collections.namedtuple('Launch', 'kind layers')
 PAIR_KEYS = ((64, 64), (64, 128), (128, 128))     # (cin, cout) of lfd_conv2d_downsample_nhwc_i8

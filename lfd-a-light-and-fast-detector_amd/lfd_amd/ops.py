@@ -982,7 +982,7 @@ def conv2d_downsample_i8_supported(cin, cout):
 
 def conv2d_downsample_nhwc_i8(x, w_packed, mult, biasq, ds_w_packed, ds_mult, ds_biasq, cout, out=None, ds_out=None):
     """x [N,H,W,cin] int8 -> (3x3 stride-2 conv with ReLU, 1x1 stride-2 identity branch without), both [N,OH,OW,cout] int8, in
-    one launch (lfd_conv2d_downsample_nhwc_i8): the two convs that open a stage-entry block"""
+    one launch (lfd_conv2d_downsample_nhwc_i8, csrc/conv_i8.hip): the two convs that open a stage-entry block"""
     require_cuda(x, 'conv2d_downsample_i8')
     if x.dtype != torch.int8 or not x.is_contiguous() or x.dim() != 4:
         raise RuntimeError('conv2d_downsample_nhwc_i8: x must be contiguous int8 NHWC')

@@ -1,5 +1,6 @@
 """tests/golden/block_i8_cases.py -- shapes, seeded operands and the integer reference for csrc/block_i8.hip: lfd_block_i8_fused
-(a whole 64-channel residual block) and lfd_conv2d_downsample_nhwc_i8 (the two stride-2 convs of a stage-entry block), built on
+(a whole 64-channel residual block) and for csrc/conv_i8.hip's pair instances: lfd_conv2d_downsample_nhwc_i8 (the two stride-2 convs of
+a stage-entry block), built on
 tests/golden/conv_i8_cases.py.
 
 Operands are FULL-RANGE int8, independent per element.  The reference composes conv_i8_cases.acc_ref (exact integer sums over a
@@ -12,7 +13,7 @@ Two instruments, as for the single conv: exact_constants (powers of two: every v
 kernel must equal the reference bit for bit) and random_constants (arbitrary fp32: the kernel must equal the layer-by-layer
 launches bit for bit -- both sides evaluate the same fp32 expressions on the same exact sums, so there is no near-tie allowance).
 
-Launch geometry restated (csrc/block_i8.hip): the block kernel walks tiles of 8 x 16 output pixels with at most 256 workgroups
+Launch geometry restated (csrc/block_i8.hip, csrc/conv_i8.hip): the block kernel walks tiles of 8 x 16 output pixels with at most 256 workgroups
 (one per CU), the pair kernel tiles of 4 x 16 OUTPUT pixels with at most 1024; workgroup b runs tiles b, b + grid, ... of the
 order (image, tile row, tile column)."""
 import collections

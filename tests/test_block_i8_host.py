@@ -1,4 +1,4 @@
-"""Host side of the fused int8 launches (csrc/block_i8.hip, the fused=True route of lfd_amd/engine_i8.py): the reference of
+"""Host side of the fused int8 launches (csrc/block_i8.hip, csrc/conv_i8.hip, the fused=True route of lfd_amd/engine_i8.py): the reference of
 tests/golden/block_i8_cases.py against a plain int64 conv chain, what the shape tables claim, the lowering of the layer list into
 launches, and the status codes of refused calls.  No GPU: a refused call returns before any launch."""
 import ctypes as C

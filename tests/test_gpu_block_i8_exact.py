@@ -1,4 +1,4 @@
-"""csrc/block_i8.hip on the MI355X: lfd_block_i8_fused and lfd_conv2d_downsample_nhwc_i8 against the integer reference of
+"""csrc/block_i8.hip and the pair instances of csrc/conv_i8.hip on the MI355X: lfd_block_i8_fused and lfd_conv2d_downsample_nhwc_i8 against the integer reference of
 tests/golden/block_i8_cases.py (power-of-two constants: bit for bit) and against the lfd_conv2d_nhwc_i8 launches they replace
 (arbitrary fp32 constants: bit for bit as well -- the sums are exact and the fp32 expressions are the same, so there is no
 near-tie allowance), with and without the fp16 tap, on the 1 x 1 map, ragged maps and a tile walk past the grid cap; guard rows,

@@ -1,4 +1,4 @@
-"""The fused route of the INT8 deployment mode on the MI355X (build_int8_engine(..., fused=True); csrc/block_i8.hip)
+"""The fused route of the INT8 deployment mode on the MI355X (build_int8_engine(..., fused=True); csrc/block_i8.hip, csrc/conv_i8.hip)
 against the default layer-by-layer engine of the same model and the same calibration cache: cls / reg, every tap buffer and every
 int8 map both routes write must be equal bit for bit, eager and under graph replay; the launch counts; the default untouched.
 

@@ -1,4 +1,4 @@
-"""The INT8 deployment mode (lfd_amd.deployment, csrc/conv_i8.hip, csrc/block_i8.hip, csrc/entry_i8.hip, csrc/block128_i8.hip), its
+"""The INT8 deployment mode (lfd_amd.deployment, csrc/conv_i8.hip, csrc/block_i8.hip, csrc/entry_i8.hip, csrc/block128_i8.hip; csrc/i8_impl.h), its
 'full' route with and without the block128 and stem_int8 options, its fused route and its default layer-by-layer route, against the 'fp16' mode, frames resident in device memory (NHWC fp16,
 1920 x 1080 unless --size=HxW):
 

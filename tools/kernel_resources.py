@@ -1,7 +1,7 @@
 """Registers, LDS, scratch and occupancy of every kernel in csrc/, as the compiler reports them
 (hipcc -Rpass-analysis=kernel-resource-usage, gfx950) -> profiles/<tag>_kernel_resources.txt.  No GPU needed.
 
-    python tools/kernel_resources.py [tag]
+    python tools/kernel_resources.py [tag [file.hip ...]]        (files: only these of csrc/, default all)
 """
 import glob
 import os
@@ -25,7 +25,10 @@ def main():
     # one-wave-per-SIMD kernels: without it the fused stem reports 164 B of scratch that the shipped object does not have)
     mk = open(os.path.join(CSRC, 'Makefile')).read()
     per_file = {m.group(1): m.group(2).split() for m in re.finditer(r'^FLAGS_(\w+)\s*=\s*(.*)$', mk, re.M)}
+    only = sys.argv[2:]
     for src in sorted(glob.glob(os.path.join(CSRC, '*.hip'))):
+        if only and os.path.basename(src) not in only:
+            continue
         base = os.path.splitext(os.path.basename(src))[0]
         r = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-fno-fast-math',
                             '-DLFD_BUILDING', '-I' + os.path.join(ROOT, 'include')] + per_file.get(base, []) +
@@ -42,7 +45,7 @@ def main():
             elif cur is not None:
                 cur[k] = v
     names = demangle([r_['name'] for r_ in rows])
-    lines = ['# compiler-reported resources of every kernel, compiled with the flags of csrc/Makefile incl. the per-file ones (-Rpass-analysis=kernel-resource-usage; tools/kernel_resources.py)',
+    lines = ['# compiler-reported resources of every kernel%s, compiled with the flags of csrc/Makefile incl. the per-file ones (-Rpass-analysis=kernel-resource-usage; tools/kernel_resources.py)' % (' of ' + ', '.join(only) if only else ''),
              '# file | kernel | VGPRs | AGPRs | SGPRs | VGPR spill | scratch B/lane | LDS B/block (static) | occupancy waves/SIMD']
     for r_, n in zip(rows, names):
         n = re.sub(r'\(.*', '', n) if len(n) > 110 else n
